@@ -13,6 +13,12 @@ one NUTS transition of every chain of the rank.  `--config c2` runs the 100-dim 
 Chains shard embarrassingly: each rank owns 4096 chains with its own seeds ("weak"
 scaling); the only collective is the final gather of the last sample to rank 0 (RCCL over
 xGMI), which is inside the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run measures the headline only: set-up, warm-up, the timed steps, the line.  `--full`
+adds what takes runs of its own: the CPU baseline (the C restatement on this host's cores) and,
+for c3 at full size, the `secondary` workloads and the other configs (each in a child process).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float64; the
+inputs are seeded, so two builds can be compared output for output).
 """
 import argparse
 import json
@@ -107,6 +113,36 @@ def emit(obj, verbose=False):
                 break
     print(line)
     return line
+
+
+DUMP_LIMIT = 60_000_000  # bytes of the --dump-outputs arrays together (the files, .npy headers included, stay below 64 MB)
+
+
+def dump_outputs(path, info, extra=None):
+    """`--dump-outputs`: the Diagnostics of the last timed step (this rank's chains) and `extra` as <path>/<name>.npy,
+    float64 (integer and boolean fields are exact in it).  Per-chain fields are written whole; the [C, ...] fields are
+    cut to the rows of a fixed, seeded sample of chains -- written as `sampled_chains.npy` -- when all of them together
+    would exceed DUMP_LIMIT (c3: 3 x 4096 x 10^4 doubles)."""
+    st = info.state
+    fields = {"position": st.position, "momentum": st.momentum, "potential_energy": st.potential_energy,
+              "potential_energy_grad": st.potential_energy_grad, "acceptance_probability": info.acceptance_probability,
+              "num_doublings": info.num_doublings, "is_turning": info.is_turning, "is_diverging": info.is_diverging,
+              "n_leapfrog": info.n_leapfrog}
+    fields.update(extra or {})
+    fields = {k: torch.as_tensor(v).detach() for k, v in fields.items() if v is not None}
+    C = fields["position"].shape[0] if fields["position"].dim() else 1
+    wide = [k for k, v in fields.items() if v.dim() >= 2 and v.shape[0] == C]
+    total = sum(v.numel() * 8 for v in fields.values())
+    if wide and total > DUMP_LIMIT:
+        row_bytes = sum(fields[k][0].numel() * 8 for k in wide)
+        rows = max(1, min(C, (DUMP_LIMIT - (total - C * row_bytes)) // (row_bytes + 8)))
+        idx = np.sort(np.random.default_rng(0).choice(C, int(rows), replace=False))
+        for k in wide:
+            fields[k] = fields[k][torch.as_tensor(idx, device=fields[k].device)]
+        fields["sampled_chains"] = torch.as_tensor(idx)
+    os.makedirs(path, exist_ok=True)
+    for k, v in fields.items():
+        np.save(os.path.join(path, k + ".npy"), v.cpu().numpy().astype(np.float64))
 
 
 PMC_STALE = {}  # summary name -> why its counters were NOT used in this run's line
@@ -575,8 +611,12 @@ def main():
     ap.add_argument("--chains", type=int, default=None, help="chains per GPU (default: 4096; c5: 1024 = 8192 over 8 GPUs; "
                                                              "c4: 32768 / ranks)")
     ap.add_argument("--dim", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the diagonal-mass secondary lines")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the CPU baseline and, "
+                                                        "for c3 at full size, the secondary workloads and other configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary lines")
     ap.add_argument("--verbose", action="store_true", help="print the line with its explanatory `note` strings (longer than "
                                                            "the driver's stdout tail keeps)")
     ap.add_argument("--fp-contract", action="store_true",
@@ -698,13 +738,14 @@ def main():
     kern_ms, kern_n, kern_flops = eng.profile_read()
     eng.profile_enable(False)
     assert rank != 0 or gathered.shape[0] == C * world
-    # the gather moved every rank's rows bit for bit: per-rank checksums of the bit patterns against the same sums
-    # over the shards of the gathered array (outside the timed region)
-    sums = shard_checksums(state.position)
+    # --full: the gather moved every rank's rows bit for bit: per-rank checksums of the bit patterns against the same
+    # sums over the shards of the gathered array (outside the timed region)
     rows_match = None
-    if rank == 0:
-        got = torch.stack([gathered[r * C:(r + 1) * C].contiguous().view(torch.int64).sum() for r in range(world)])
-        rows_match = bool(torch.equal(got.cpu(), sums.cpu()))
+    if args.full:
+        sums = shard_checksums(state.position)
+        if rank == 0:
+            got = torch.stack([gathered[r * C:(r + 1) * C].contiguous().view(torch.int64).sum() for r in range(world)])
+            rows_match = bool(torch.equal(got.cpu(), sums.cpu()))
 
     if rank != 0:
         return
@@ -764,11 +805,13 @@ def main():
                                  "SIMD for 4 cycles; issue_ceiling = 1024 SIMDs x 2.4 GHz / (4 waves x 4 cycles x counted "
                                  "instructions per wave and transition)"}})
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, info)
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(args.config, D, q0, target, imm, eps)
     secondary = None
-    if args.config == "c3" and world == 1 and not args.no_secondary and D == 10_000:
+    if args.full and args.config == "c3" and world == 1 and not args.no_secondary and D == 10_000:
         del state, info, kernel, target, imm, gathered
         torch.cuda.empty_cache()
         secondary = bench_secondary(eng, device, max(args.steps, 3), 2)
@@ -815,6 +858,8 @@ def bench_c1(args):
         nl = int(info.n_leapfrog.item())
     kern_ms, kern_n, _ = eng.profile_read()
     eng.profile_enable(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, info)
     dt = sum(times[args.warmup:]) / max(args.steps, 1)
     # One wavefront walks the 136 leapfrogs of the tree one dependent instruction after the other: neither HBM nor the
     # matrix cores bound it, the ISSUE LATENCY of a lone wavefront does.  peak = clock / (issue cycles per leapfrog at
@@ -872,7 +917,7 @@ def bench_c5(args, rank, world, device):
     barrier(device)
     torch.cuda.synchronize(device)
     t0 = time.perf_counter()
-    _, info, _, _ = kernel.sample(state, eps, imm, args.steps, keep_samples=False)
+    _, info, acc_hist, div_hist = kernel.sample(state, eps, imm, args.steps, keep_samples=False)
     gathered = gather_samples(info.state.position)
     torch.cuda.synchronize(device)
     barrier(device)
@@ -885,8 +930,11 @@ def bench_c5(args, rank, world, device):
     if rank == 0:
         assert gathered.shape[0] == chains_total
         rate = total / elapsed
+        if args.dump_outputs:
+            # (the [T, C] histories chain axis first, as [C, T], so that a sample of chains would cut them too)
+            dump_outputs(args.dump_outputs, info, {"acceptance_history": acc_hist.T, "divergence_history": div_hist.T})
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline_c5(X, y, info, eps, imm)
         # The dominant kernel is k_nuts_linreg (the whole sample() call is ONE launch of it).  Neither HBM nor
         # MFMA bounds it: per leapfrog a chain needs 3 fp64 FMAs (6 flop) per data row, the rows (16 B each) come

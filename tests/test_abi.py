@@ -227,3 +227,32 @@ def test_bench_line_fits_the_drivers_stdout_tail(capsys):
         assert e["value"] == pytest.approx(f["value"], rel=1e-5) and "frac" in e["roofline"]
     assert "note" not in line
     assert len(bench.emit(full, verbose=True)) > bench.LINE_LIMIT  # --verbose keeps the prose
+
+
+def test_bench_dump_outputs_of_the_headline_shape_stay_under_64_mb(tmp_path):
+    """`bench.py --dump-outputs` at c3's shape (4096 chains x 10^4): three [C, D] fields are 983 MB in float64, so they
+    are cut to the same fixed, seeded sample of chains (written beside them) and every file together stays below 64 MB;
+    per-chain fields are written whole."""
+    import numpy as np
+    import torch
+
+    import bench
+    from aehmc_amd.integrators import IntegratorState
+    from aehmc_amd.trajectory import Diagnostics
+    C, D = 4096, 10_000
+    q = torch.arange(C, dtype=torch.float64)[:, None].expand(C, D)  # row c holds c: which rows were kept is visible
+    per_chain = torch.linspace(0, 1, C, dtype=torch.float64)
+    info = Diagnostics(IntegratorState(q, -q, per_chain, 2 * q), per_chain, torch.ones(C, dtype=torch.int64),
+                       torch.zeros(C, dtype=torch.bool), torch.ones(C, dtype=torch.bool), torch.full((C,), 57))
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), info)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64 << 20
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype == np.float64 for v in got.values())
+    idx = got["sampled_chains"]
+    assert 200 < len(idx) < C and np.array_equal(idx, np.load(tmp_path / "b" / "sampled_chains.npy"))
+    assert got["position"].shape == (len(idx), D) and np.array_equal(got["position"][:, 0], idx)
+    assert np.array_equal(got["potential_energy_grad"], 2 * got["position"]) and np.array_equal(got["momentum"], -got["position"])
+    assert np.array_equal(got["potential_energy"], per_chain.numpy()) and got["n_leapfrog"].tolist() == [57.0] * C
+    assert got["is_diverging"].sum() == C and got["is_turning"].sum() == 0

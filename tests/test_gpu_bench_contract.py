@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +33,7 @@ def _run(*args, env=None):
 
 
 def test_bench_c2_line():
-    d = _run("--config", "c2", "--steps", "3", "--warmup", "1")
+    d = _run("--config", "c2", "--steps", "3", "--warmup", "1", "--full")
     assert all(k in d for k in REQUIRED)
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64"
     assert d["scaling"] == "weak" and d["vs_baseline"] is None and d["higher_is_better"] is True
@@ -84,6 +85,26 @@ def test_bench_c3_small_line():
     assert d["config"]["leapfrogs_per_step"] > 0 and d["value"] > 0
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times the headline only: no CPU baseline, no secondary entries.  `--dump-outputs` writes
+    the last timed step's arrays as float64 .npy files; the inputs are seeded, so a second run writes the same arrays."""
+    args = ("--steps", "3", "--warmup", "1", "--chains", "256", "--dim", "1024")
+    runs = []
+    for name in ("a", "b"):
+        d = _run(*args, "--dump-outputs", str(tmp_path / name))
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["cpu_baseline"] is None and d.get("secondary") is None
+        files = sorted(os.listdir(tmp_path / name))
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) < 64 << 20
+        runs.append({f: np.load(tmp_path / name / f) for f in files})
+    a, b = runs
+    assert {"position.npy", "potential_energy.npy", "acceptance_probability.npy", "n_leapfrog.npy"} <= set(a)
+    assert a["position.npy"].shape == (256, 1024) and a["n_leapfrog.npy"].shape == (256,) and a["n_leapfrog.npy"].min() > 0
+    assert sorted(a) == sorted(b)
+    for f in a:
+        assert a[f].dtype == np.float64 and np.array_equal(a[f], b[f]), f
+
+
 def test_bench_gpus2_starts_two_ranks():
     """`python bench.py --gpus 2` (no launcher) must start two ranks itself and report n_gpus == 2.
     On a 1-GPU box both ranks share cuda:0 (AEHMC_BENCH_ONE_DEVICE=1) and the gather runs over gloo
@@ -91,7 +112,7 @@ def test_bench_gpus2_starts_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(AEHMC_BENCH_ONE_DEVICE="1", AEHMC_DIST_BACKEND="gloo")
     d = _run("--gpus", "2", "--steps", "2", "--warmup", "1", "--chains", "64", "--dim", "256",
-             "--no-cpu-baseline", env=env)
+             "--no-cpu-baseline", "--full", env=env)
     assert d["n_gpus"] == 2 and d["config"]["ranks_seen"] == 2 and d["config"]["chains_total"] == 128
     assert d["config"]["gather"]["bytes"] == 64 * 256 * 8 and d["value"] > 0
     assert d["config"]["gather"]["rows_match_ranks_bitwise"] is True
@@ -106,7 +127,8 @@ def test_bench_two_gpus_over_rccl():
         pytest.skip("needs two GPUs")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "AEHMC_BENCH_ONE_DEVICE",
                                                             "AEHMC_DIST_BACKEND")}
-    d = _run("--gpus", "2", "--config", "c4", "--dim", "2048", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", env=env)
+    d = _run("--gpus", "2", "--config", "c4", "--dim", "2048", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--full",
+             env=env)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["ranks_seen"] == 2
     g = d["config"]["gather"]
     assert g["backend"] == "nccl" and g["rows_match_ranks_bitwise"] is True and g["ms"] > 0
@@ -133,7 +155,7 @@ def test_bench_c4_and_c5_two_rank_dry_runs():
 def test_bench_default_line_has_its_good_secondary_entries():
     """The default line (c3 at full size) carries the diagonal-mass NUTS / HMC numbers, the mid-size dense problems and
     c2, c5, c1 as `secondary`: none of them may have degraded into an {"error": ...} entry."""
-    d = _run("--steps", "2", "--no-cpu-baseline")
+    d = _run("--steps", "2", "--no-cpu-baseline", "--full")
     assert len(_run.last_line) < 8000  # the whole line fits the ~8 kB of stdout the driver keeps
     assert all(k in d for k in REQUIRED) and d["roofline"]["bound"] == "mfma"
     assert d["config"]["dim"] == 10_000 and d["config"]["chains_total"] == 4096

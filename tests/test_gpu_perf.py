@@ -23,7 +23,7 @@ def test_c2_reaches_the_north_star_rate():
 
 
 def test_secondary_entries_keep_their_rates():
-    d = _bench("--steps", "2", "--no-cpu-baseline")
+    d = _bench("--steps", "2", "--no-cpu-baseline", "--full")
     by = {e["config"]: e for e in d["secondary"]}
     for k in ("dense-nuts-d100", "dense-nuts-d200"):
         assert by[k]["ms_per_transition"] < 1.5
