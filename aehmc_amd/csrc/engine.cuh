@@ -783,6 +783,9 @@ AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_nuts_fused(EngineArgs a)
 // 3 products per leapfrog).
 constexpr int FUSED_DENSE_MAX_D = 64;
 constexpr int JOINT_ROWS_MAX_D = 2048;  // joint (non-separable) user targets on the lock-step path: four wavefronts' position and gradient rows in 128 KB of LDS (k_target_joint_rows)
+// a joint density with its reverse-mode program above that: ONE chain's rows per workgroup (k_target_joint_wg, and the
+// AEHMC_T_JOINT instantiations of k_nuts_wide / k_hmc_wide: 2 (D + 1) doubles next to their static arrays in the CU's 160 KiB)
+constexpr int JOINT_WIDE_MAX_D = 10176;
 constexpr int FUSED_DENSE_BLOCK = 512;  // eight chains per workgroup share the matrices
 // y[i] = sum_k M[i][k] x[k] for i < D; MT = M transposed in LDS (MT[k * D + i] = M[i][k]); x, y rows in global memory,
 // element i read and written by lane i only
@@ -1315,6 +1318,29 @@ __device__ inline double joint_wg_eval(const EngineArgs &a, const double *q, dou
   for (int i = tid; i < D; i += 64 * W) g[i] = -gr[i];
   __threadfence_block();  // (wavefront 0 reads the row behind the caller's barrier)
   return -lp;
+}
+// U and dU/dq of every (live) chain, a workgroup per chain: k_target_joint_rows for D > JOINT_ROWS_MAX_D, where four
+// wavefronts' rows no longer fit the CU's LDS (new_state, and the lock-step path's target_ext: a shared dense metric, or
+// joint_wide = 0).  Same row_idx / n_rows compaction; U -> ctl[c].U_cur (leapfrog; finished chains are skipped) or U[c].
+template <int W>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_waves(W)))) void k_target_joint_wg(EngineArgs a, const double *q, double *g,
+                                                                                                         double *U, int to_ctl, const int *row_idx,
+                                                                                                         const int *n_rows) {
+  extern __shared__ __attribute__((aligned(16))) double joint_rows[];
+  long long c = blockIdx.x;
+  if (row_idx) {
+    if (c >= *n_rows) return;
+    c = row_idx[c];
+  } else if (c >= a.C) {
+    return;
+  }
+  if (to_ctl && a.ctl[c].done) return;  // (the whole workgroup: before the first barrier)
+  const size_t row = (size_t)c * a.D;
+  const double Uv = joint_wg_eval<W>(a, q + row, g + row, joint_rows, (int)threadIdx.x);
+  if (threadIdx.x == 0) {
+    if (to_ctl) a.ctl[c].U_cur = Uv;
+    else U[c] = Uv;
+  }
 }
 template <int W>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_waves(W)))) void k_nuts_joint_wg(EngineArgs a, NutsSampleArgs m) {

@@ -65,6 +65,7 @@ struct aehmc_ctx {
   int opt_joint_wg = 1;          // traced joint densities with long sweeps: a workgroup per chain (0 never, 1 when it pays, 2 always)
   int opt_wg_waves = 0;          // wavefronts per SIMD the workgroup-per-chain kernels are compiled for (0: four unless the program then spills, see wg_program; 3; 4)
   std::map<std::string, std::string> wg_choice;  // (wg_program: kernel -> the program variant that was picked)
+  int opt_joint_wide = 1;      // traced joint densities, scalar / diagonal metric: the workgroup-per-chain kernels (0 never, 1 above 2048 coordinates, 2 also from 513 on)
   int opt_joint_resident = 1;  // joint densities with a reverse-mode program, D <= 512: the register-resident NUTS kernel (0 never, 1 from 17 coordinates on or with long reductions, 2 always)
   bool opt_pc_dense = true;      // per-chain dense metrics, 64 < D <= 512: NUTS in one launch, a wavefront per chain streams its matrix
   int opt_block_dense = 1;       // mid-size dense problems (64 < D <= 512): one workgroup per 16 chains, whole call in one launch
@@ -337,9 +338,9 @@ static int rtc_function(aehmc_ctx *ctx, const std::string &which_full, const std
     src += "#line 1 \"custom_target\"\n" + ctx->custom_src + "\n";
     src += "#include \"engine.cuh\"\n";
     if (which == "nuts" || which == "jnuts") src += "#include \"nuts_resident.cuh\"\n";
-    if (which == "wide") src += "#include \"nuts_wide.cuh\"\n";
+    if (which == "wide" || which == "jwide") src += "#include \"nuts_wide.cuh\"\n";
     if (which == "block") src += "#include \"nuts_block_reg.cuh\"\n";
-    if (which == "hmc" || which == "jhmcf") src += "#include \"hmc_fused.cuh\"\n";
+    if (which == "hmc" || which == "jhmcf" || which == "jwide") src += "#include \"hmc_fused.cuh\"\n";
     if (which == "glm" || which == "glmk") src += "#include \"glm_rows.cuh\"\n";  // ("glmk": one instantiation of the one-launch kernels)
     const std::string inc = "-I" + ctx->custom_inc;
     const char *opts[] = {"--offload-arch=" AEHMC_GPU_ARCH, "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
@@ -569,14 +570,57 @@ static bool joint_wg_wanted(const aehmc_ctx *ctx, int64_t C) {
 }
 static const std::vector<std::string> RTC_JBASE = {"aehmc::k_new_state_joint", "aehmc::k_target_joint_rows", "aehmc::k_nuts_joint_rows",
                                                    "aehmc::k_hmc_joint_rows"};
+// above JOINT_ROWS_MAX_D (a density with its reverse-mode program only): U and dU/dq a workgroup per chain -- new_state and
+// the lock-step path's target evaluation; the kernels above would need four chains' rows in LDS
+static const std::vector<std::string> RTC_JTWG = {"aehmc::k_target_joint_wg<8>"};
+static bool joint_has_grad(const aehmc_ctx *ctx) { return ctx->custom_src.find("#define AEHMC_JOINT_GRAD") != std::string::npos; }
+// a traced joint density on the workgroup-per-chain NUTS / HMC kernels (k_nuts_wide / k_hmc_wide, AEHMC_T_JOINT): above
+// JOINT_ROWS_MAX_D by default ("joint_wide" 1), also from 513 coordinates on with "joint_wide" 2 (cross-checks), never with 0
+static bool joint_wide_wanted(const aehmc_ctx *ctx) {
+  const int64_t D = ctx->tgt.D;
+  if (ctx->tgt.kind != AEHMC_T_JOINT || !ctx->opt_joint_wide || ctx->met.ndim >= 2 || D > JOINT_WIDE_MAX_D || !joint_has_grad(ctx))
+    return false;
+  // (option 2 only where the workspace rows are padded for k_nuts_wide: ws_layout, wide_rows_padded)
+  return D > JOINT_ROWS_MAX_D || (ctx->opt_joint_wide == 2 && wide_rows_padded(D));
+}
+// the elements per thread of those instantiations (512 threads: the program runs as aehmc_logp_grad_t<8> on all of them)
+static int joint_wide_r(int64_t D) { return D <= 4096 ? 8 : D <= 8192 ? 16 : 20; }
+// LDS of a workgroup that holds ONE chain's position and gradient rows (`row` doubles each: D + 1 for the wide kernels,
+// D for k_target_joint_wg) next to the kernel's static arrays (`f`: the compiled kernel), against the CU's 160 KiB
+constexpr size_t CU_LDS_BYTES = 163840;
+static int joint_rows_lds(aehmc_ctx *ctx, hipFunction_t f, int64_t row, size_t *dyn) {
+  int stat = 0;
+  if (hipFuncGetAttribute(&stat, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, f) != hipSuccess || stat < 0)
+    FAIL("joint target: the static LDS size of the compiled kernel could not be read");
+  *dyn = (size_t)2 * row * sizeof(double);
+  if (*dyn + (size_t)stat > CU_LDS_BYTES)
+    FAIL("joint target: D = " + std::to_string(ctx->tgt.D) + " needs " + std::to_string(*dyn + stat) +
+         " bytes of LDS for one chain's position and gradient rows, the CU has " + std::to_string(CU_LDS_BYTES));
+  return 0;
+}
+// rtc_launch of a kernel that keeps one chain's rows in LDS, after the budget check above
+template <class... Args>
+static int joint_rows_launch(aehmc_ctx *ctx, const std::string &which, const std::vector<std::string> &names, const std::string &want,
+                             int64_t row, dim3 grid, dim3 block, hipStream_t st, Args... args) {
+  hipFunction_t f = nullptr;
+  if (int rc = rtc_function(ctx, which, names, want, &f)) return rc;
+  size_t dyn = 0;
+  if (int rc = joint_rows_lds(ctx, f, row, &dyn)) return rc;
+  return rtc_launch(ctx, which, names, want, grid, block, dyn, st, args...);
+}
 extern "C" int aehmc_set_custom_joint_target(aehmc_ctx *ctx, const char *source, int64_t D, const double *const *params,
                                              int32_t n_params, const char *include_dir) {
   if (!ctx || !source || !include_dir) return -2;
   HIPCHK(hipSetDevice(ctx->device));
-  // (D <= 64: one coordinate per lane, the single-launch kernels; above: the lock-step path, the position row in LDS)
-  if (D <= 0 || D > JOINT_ROWS_MAX_D)
-    FAIL("joint target: D must be in [1, " + std::to_string(JOINT_ROWS_MAX_D) + "]");
-  if (int rc = custom_bind(ctx, source, include_dir, params, n_params, "jbase", RTC_JBASE)) return rc;
+  // (D <= 64: one coordinate per lane, the single-launch kernels; above: the position row in LDS -- four chains' rows per
+  //  workgroup up to JOINT_ROWS_MAX_D, one chain's above, which takes the density's reverse-mode program)
+  const bool grad = strstr(source, "#define AEHMC_JOINT_GRAD") != nullptr;
+  const int64_t dmax = grad ? JOINT_WIDE_MAX_D : JOINT_ROWS_MAX_D;
+  if (D <= 0 || D > dmax)
+    FAIL("joint target: D must be in [1, " + std::to_string(dmax) + "]" +
+         (grad ? std::string() : " without a reverse-mode program (AEHMC_JOINT_GRAD: up to " + std::to_string(JOINT_WIDE_MAX_D) + ")"));
+  const bool big = D > JOINT_ROWS_MAX_D;
+  if (int rc = custom_bind(ctx, source, include_dir, params, n_params, big ? "jtwg" : "jbase", big ? RTC_JTWG : RTC_JBASE)) return rc;
   aehmc_target t{};
   t.kind = AEHMC_T_JOINT;
   t.D = D;
@@ -913,6 +957,11 @@ extern "C" int aehmc_set_option(aehmc_ctx *ctx, const char *name, int64_t value)
     ctx->opt_joint_resident = (int)value;
     return 0;
   }
+  if (!strcmp(name, "joint_wide")) {
+    if (value < 0 || value > 2) FAIL("joint_wide: 0 (never), 1 (default: above 2048 coordinates), 2 (also from 513 on)");
+    ctx->opt_joint_wide = (int)value;
+    return 0;
+  }
   if (!strcmp(name, "joint_wg")) {
     if (value < 0 || value > 2) FAIL("joint_wg: 0 (never), 1 (default: when it pays), 2 (always)");
     ctx->opt_joint_wg = (int)value;
@@ -931,7 +980,7 @@ static int64_t ws_layout(const aehmc_ctx *ctx, int64_t C, int64_t E, char *base,
   const bool md = ctx->has_met && ctx->met.ndim == 2;
   const int64_t D = ctx->has_tgt ? ctx->tgt.D : (ctx->has_met ? ctx->met.D : 0);
   // (rows padded to nuts_wide_ld(D) where the workgroup-per-chain NUTS kernel may run: D > 512)
-  const int64_t ldmax = D > 512 ? nuts_wide_ld(D) : D;
+  const int64_t ldmax = wide_rows_padded(D) ? nuts_wide_ld(D) : D;
   const size_t vec = (((size_t)C * ldmax * sizeof(double)) + 255) & ~(size_t)255;
   size_t off = 0;
   auto take = [&](size_t n) -> double * {
@@ -1172,10 +1221,11 @@ static int launch_glm(aehmc_ctx *ctx, const EngineArgs &a, const double *q, doub
     HIPCHK(hipGetLastError());                                                        \
   } while (0)
 
-static bool joint_has_grad(const aehmc_ctx *ctx) { return ctx->custom_src.find("#define AEHMC_JOINT_GRAD") != std::string::npos; }
 // joint user-defined target on the lock-step path: U and dU/dq of the (live) chains from their position rows
 static int launch_joint_rows(aehmc_ctx *ctx, const EngineArgs &a, const double *q, double *g, double *U, int to_ctl,
                              hipStream_t st, const int *ri, const int *nr) {
+  if (a.D > JOINT_ROWS_MAX_D)  // a workgroup per chain (k_target_joint_wg)
+    return joint_rows_launch(ctx, "jtwg", RTC_JTWG, RTC_JTWG[0], a.D, dim3((unsigned)a.C), dim3(512), st, a, q, g, U, to_ctl, ri, nr);
   return rtc_launch(ctx, "jbase", RTC_JBASE, RTC_JBASE[1], chain_grid(a.C), dim3(256), (size_t)8 * a.D * sizeof(double), st, a, q, g, U,
                     to_ctl, ri, nr);
 }
@@ -1369,8 +1419,13 @@ static int nuts_path(const aehmc_ctx *ctx, int64_t C, int64_t max_num_expansions
   if (want_resident && nuts_wide_supported(tkind, nd, D)) return NUTS_PATH_WIDE;
   // small dense problems (shared dense metric and / or dense-precision target, D <= 64): one launch, the products
   // inside the wavefront (k_nuts_resident's DENSE instantiations)
+  // a traced joint density above 2048 coordinates, scalar / diagonal metric: the workgroup-per-chain kernel with the
+  // program's rows in LDS (k_nuts_wide<512, R, true, AEHMC_T_JOINT>, run-time compiled; "joint_wide" option)
+  if (want_resident && joint_wide_wanted(ctx)) return NUTS_PATH_WIDE;
+  // (none of the joint routes below is taken above JOINT_ROWS_MAX_D: there the lock-step path evaluates the density a
+  //  workgroup per chain, k_target_joint_wg)
   // a traced joint density with long data sweeps and few chains: a workgroup per chain (k_nuts_joint_wg, run-time compiled)
-  if (want_resident && tkind == AEHMC_T_JOINT && nd < 2 && joint_wg_wanted(ctx, C)) return NUTS_PATH_JOINT_WG;
+  if (want_resident && tkind == AEHMC_T_JOINT && nd < 2 && D <= JOINT_ROWS_MAX_D && joint_wg_wanted(ctx, C)) return NUTS_PATH_JOINT_WG;
   // a joint density with a reverse-mode program (a traced Python logprob_fn), scalar / diagonal metric: the register-resident
   // kernel with the program's rows in LDS -- from 17 coordinates on, or when its reductions are long, it beats the 64
   // forward passes side by side of the dense-path kernel below (funnel, 4096 chains: D = 32 2.5 -> 3.5e8 leapfrog/s, D = 64
@@ -1392,7 +1447,7 @@ static int nuts_path(const aehmc_ctx *ctx, int64_t C, int64_t max_num_expansions
       ctx->custom_src.find("#define AEHMC_JOINT_GRAD") != std::string::npos)
     return NUTS_PATH_TEAMS;
   // (... costs O(D / 64) per gradient: one launch whatever D)
-  if (want_resident && tkind == AEHMC_T_JOINT && nd < 2 &&
+  if (want_resident && tkind == AEHMC_T_JOINT && nd < 2 && D <= JOINT_ROWS_MAX_D &&
       (D <= 192 || ctx->custom_src.find("#define AEHMC_JOINT_GRAD") != std::string::npos))
     return NUTS_PATH_JOINT_ROWS;
   if (want_resident && nuts_resident_dense_supported(tkind, nd, D))
@@ -1445,6 +1500,8 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
     bool p = false;
     if (int rc = prof_begin(ctx, st, p)) return rc;
     if (path == NUTS_PATH_WIDE) {  // one workgroup per chain (nuts_wide.cuh): momentum drawn at one wavefront per chain first
+      if (!wide_rows_padded(a.D))  // (rows of nuts_wide_ld(D) would run past the workspace's vectors)
+        FAIL("internal: the workgroup-per-chain NUTS kernel needs D > 512, got D = " + std::to_string(a.D));
       a.ldw = nuts_wide_ld(a.D);
       hipLaunchKernelGGL(k_draw_momentum, chain_grid(C), dim3(256), 0, st, a.rng, a.nsites, (long long)C,
                          (long long)a.D, a.sqrt_mass, (long long)a.imm_cs, a.met_ndim, a.zbuf, a.ldw, 1);
@@ -1457,6 +1514,10 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
                                  (qgl ? "true" : "false") + ", " + std::to_string((int)AEHMC_T_CUSTOM) + ">";
         const size_t dyn = qgl ? (size_t)2 * (D + 1) * sizeof(double) : 0;  // (q and dU/dq in LDS)
         if (int rc = rtc_launch(ctx, "wide", {name}, name, dim3((unsigned)C), dim3(T), dyn, st, a)) return rc;
+      } else if (a.tkind == AEHMC_T_JOINT) {  // traced joint density: the rows of its program (q, dU/dq) in LDS at every D
+        const std::string name = "aehmc::k_nuts_wide<512, " + std::to_string(joint_wide_r(a.D)) + ", true, " +
+                                 std::to_string((int)AEHMC_T_JOINT) + ">";
+        if (int rc = joint_rows_launch(ctx, "jwide", {name}, name, a.D + 1, dim3((unsigned)C), dim3(512), st, a)) return rc;
       } else {
         HIPCHK(tu::nuts_wide(a, st));
       }
@@ -1825,7 +1886,7 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
   // traced joint density with its reverse-mode program, 64 < D <= 1024 (round 6): the same fused kernel with the position
   // and gradient rows of the generated program in LDS ("joint_resident" option; D <= 64 stays on k_hmc_fused_dense)
   if (ctx->opt_fused_hmc && ctx->opt_joint_resident && ctx->tgt.kind == AEHMC_T_JOINT && joint_has_grad(ctx) && ctx->met.ndim < 2 &&
-      D > FUSED_DENSE_MAX_D && D <= 1024 && !joint_wg_wanted(ctx, C)) {
+      D > FUSED_DENSE_MAX_D && D <= 1024 && !joint_wg_wanted(ctx, C) && !joint_wide_wanted(ctx)) {
     if (int rc = check_per_chain(ctx, C)) return rc;
     HmcFusedArgs f{};
     f.C = C; f.D = D; f.L = L; f.eps = step_size; f.thr = divergence_threshold;
@@ -1864,7 +1925,9 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
   if (int rc = fill_args(ctx, C, 1, a)) return rc;
   // (a user-defined coordinate-wise target: the same kernel compiled against the user's function at run time, round 5)
   const bool custom_wide = ctx->tgt.kind == AEHMC_T_CUSTOM && ctx->met.ndim < 2 && D > 1024 && D <= 10240;
-  if (ctx->opt_fused_hmc && (custom_wide || hmc_resident_supported(ctx->tgt.kind, ctx->met.ndim, D))) {
+  // (a traced joint density above 2048 coordinates: the AEHMC_T_JOINT instantiation, the program's rows in LDS)
+  const bool joint_wide = joint_wide_wanted(ctx);
+  if (ctx->opt_fused_hmc && (custom_wide || joint_wide || hmc_resident_supported(ctx->tgt.kind, ctx->met.ndim, D))) {
     HmcFusedArgs f{};
     f.C = C; f.D = D; f.L = L; f.eps = step_size; f.thr = divergence_threshold;
     f.met_ndim = ctx->met.ndim; f.imm = ctx->met.imm; f.sqrt_mass = ctx->met.sqrt_mass;
@@ -1906,6 +1969,11 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
         const std::string name = "aehmc::k_hmc_wide<" + std::to_string(TT) + ", " + std::to_string(R) + ", " +
                                  std::to_string((int)AEHMC_T_CUSTOM) + ", " + (f.fc ? "true" : "false") + ">";
         if (int rc = rtc_launch(ctx, "hmc", {name}, name, dim3((unsigned)C), dim3(TT), 0, st, f, (const double *)zall, nt))
+          return rc;
+      } else if (joint_wide) {  // k_nuts_wide's table: 512 threads (the program's workgroup), q and dU/dq in LDS only
+        const std::string name = "aehmc::k_hmc_wide<512, " + std::to_string(joint_wide_r(D)) + ", " +
+                                 std::to_string((int)AEHMC_T_JOINT) + ", false>";
+        if (int rc = joint_rows_launch(ctx, "jwide", {name}, name, D + 1, dim3((unsigned)C), dim3(512), st, f, (const double *)zall, nt))
           return rc;
       } else {
         HIPCHK(tu::hmc_resident(f, zall, nt, st));
@@ -1978,7 +2046,7 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
     return 0;
   }
   // traced joint density with long data sweeps, few chains: a workgroup per chain (k_hmc_joint_wg)
-  if (ctx->opt_fused_hmc && tjoint && a.met_ndim < 2 && joint_wg_wanted(ctx, C)) {
+  if (ctx->opt_fused_hmc && tjoint && a.met_ndim < 2 && D <= JOINT_ROWS_MAX_D && joint_wg_wanted(ctx, C)) {
     bool p = false;
     if (int rc = prof_begin(ctx, st, p)) return rc;
     std::string prog;
@@ -1992,7 +2060,7 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
   }
   // joint target of more than 64 coordinates, scalar / diagonal metric: all T transitions in one launch, the lock-step
   // loop of a chain in one wavefront (k_hmc_joint_rows)
-  if (ctx->opt_fused_hmc && tjoint && a.met_ndim < 2) {
+  if (ctx->opt_fused_hmc && tjoint && a.met_ndim < 2 && D <= JOINT_ROWS_MAX_D) {
     bool p = false;
     if (int rc = prof_begin(ctx, st, p)) return rc;
     if (int rc = rtc_launch(ctx, "jbase", RTC_JBASE, RTC_JBASE[3], chain_grid(C), dim3(256), (size_t)8 * D * sizeof(double), st, a,

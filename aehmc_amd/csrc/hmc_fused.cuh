@@ -330,11 +330,17 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
   // aehmc_custom_elem; dU/dq kept beside q and the caller's arrays as the fall-back state, as for the diagonal
   // Gaussian, but no parameters of the engine's own in LDS
   constexpr bool CU = TK == AEHMC_T_CUSTOM;
-  constexpr bool DG = TK == AEHMC_T_DIAG_GAUSSIAN || CU;  // otherwise dU/dq == q, no separate copy
-  constexpr bool DGP = DG && !CU;                          // sigma / mu in LDS
+  // TK == AEHMC_T_JOINT: the run-time compiled copy of a traced joint density (AEHMC_JOINT_GRAD, D > 2048 by default).
+  // q and dU/dq live in LDS only -- the position and gradient rows of the generated program, D + 1 entries each (entry
+  // D: the dummy of the slots past D, always 0) -- and the caller's arrays are the fall-back state, as for CU; p and imm
+  // stay in registers.  Per leapfrog: p_half, q' into the row | one sweep of the program by the whole workgroup | p'.
+  constexpr bool JT = TK == AEHMC_T_JOINT;
+  constexpr bool DG = TK == AEHMC_T_DIAG_GAUSSIAN || CU || JT;  // otherwise dU/dq == q, no separate copy
+  constexpr bool DGP = DG && !CU && !JT;                         // sigma / mu in LDS
   __shared__ double red[2][2 * NW];
   extern __shared__ __attribute__((aligned(16))) double wide_save[];  // q [D] at the transition's start; DG: sigma [D], mu [D]
   double *const psig = wide_save, *const pmu = wide_save + a.D;       // (diagonal-Gaussian target only)
+  double *const jq = wide_save, *const jg = wide_save + a.D + 1;      // (joint target only: the program's rows)
   int flip = 0;
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -352,6 +358,7 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
 #define EI(r) (((tb + T * (r)) < last) ? (tb + T * (r)) : last)
 #define VALID(r) ((tb + T * (r)) <= last)
 #define MASK(r) (VALID(r) ? 1.0 : 0.0)
+#define EJ(r) (VALID(r) ? (tb + T * (r)) : (unsigned)a.D) /* joint target: LDS index, dummy entry D past the end */
   auto sum2 = [&](double &x, double &y) {
     x = wave_sum(x);
     y = wave_sum(y);
@@ -373,13 +380,20 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
     y = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(sy)),
                          __builtin_amdgcn_readfirstlane(__double2loint(sy)));
   };
-  double q[R], p[R], g[DG ? R : 1], im[R];
+  double q[JT ? 1 : R], p[R], g[(DG && !JT) ? R : 1], im[R];
+#define QI(r) (JT ? 0 : (r)) /* (register arrays that a joint target does not have: index 0 in its dead code) */
+#define GI(r) ((DG && !JT) ? (r) : 0)
   const double *qrow = a.q + row, *grow = a.g + row, *zrow = zbuf + row;
 #pragma unroll
   for (int r = 0; r < R; r++) {  // every load is issued before the first use
-    q[r] = qrow[EI(r)];
+    if (JT) {
+      jq[EJ(r)] = VALID(r) ? qrow[EI(r)] : 0.0;
+      jg[EJ(r)] = VALID(r) ? grow[EI(r)] : 0.0;
+    } else {
+      q[QI(r)] = qrow[EI(r)];
+    }
     p[r] = zrow[EI(r)];
-    if (DG) g[r] = grow[EI(r)];
+    if (DG && !JT) g[GI(r)] = grow[EI(r)];
     im[r] = a.imm[imo + (a.met_ndim == 0 ? 0 : EI(r))];
     if (DGP) {  // (a thread reads back only the entries it wrote: no barrier)
       const double sd0 = a.sigma[EI(r)];
@@ -387,12 +401,18 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
       pmu[EI(r)] = a.mu[EI(r)];
     }
   }
-#define GR(r) (DG ? g[DG ? (r) : 0] : q[r])
+  if (JT && t == 0) {  // (also when no slot maps to the dummy entries)
+    jq[a.D] = 0.0;
+    jg[a.D] = 0.0;
+  }
+#define GR(r) (DG ? g[GI(r)] : q[QI(r)])
+#define QV(r) (JT ? jq[EJ(r)] : q[QI(r)]) /* q of slot r wherever it lives */
+#define GV(r) (JT ? jg[EJ(r)] : GR(r))
   double U = a.U[c];
   Pcg64 g2 = pcg_load(a.rng + (size_t)c * 8 + 4);  // site #2: accept (hmc.py:194)
   const double eps = a.eps_c ? a.eps_c[c] : a.eps;
   const double b = 0.5 * eps, aa = 1 * eps;
-  double pa = 0.0;
+  double pa = 0.0, U_joint = 0.0;
   int is_div = 0, acc = 0, any_acc = 0;
   for (int tt = 0; tt < nt; tt++) {
     const bool last_t = tt == nt - 1;
@@ -401,13 +421,13 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
 #pragma unroll
     for (int r = 0; r < R; r++) {
       kd += MASK(r) * ((im[r] * p[r]) * p[r]);
-      if (!DG) wide_save[EI(r)] = q[r];
+      if (!DG) wide_save[EI(r)] = q[QI(r)];
       // only the last transition's momentum is observable: the initial one is kept on rejection
       if (last_t && a.out.momentum && VALID(r)) (a.out.momentum + row)[EI(r)] = p[r];
     }
     sum2(kd, zero);
     const double H0 = U + 0.5 * kd;  // hmc.py:187
-    if (FC) {  // fast arithmetic (see k_hmc_fused): fused multiply-adds, eps * imm formed once, inner half kicks merged
+    if (FC && !JT) {  // fast arithmetic (see k_hmc_fused): fused multiply-adds, eps * imm formed once, inner half kicks merged
       if (a.L > 0) {
         double aim[FC ? R : 1];
 #pragma unroll
@@ -421,12 +441,12 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
           if (DG) RENEW_TB();
 #pragma unroll
           for (int r = 0; r < R; r++) {
-            q[r] = __builtin_fma(aim[FC ? r : 0], p[r], q[r]);
+            q[QI(r)] = __builtin_fma(aim[FC ? r : 0], p[r], q[QI(r)]);
             if (CU) {
               double u_;
-              AEHMC_CUSTOM_ELEM(q[r], (long long)EI(r), u_, g[DG ? r : 0]);
+              AEHMC_CUSTOM_ELEM(q[QI(r)], (long long)EI(r), u_, g[GI(r)]);
             } else if (DG) {
-              g[DG ? r : 0] = (q[r] - pmu[EI(r)]) * psig[EI(r)];  // psig holds 1 / sigma^2 in this mode
+              g[GI(r)] = (q[QI(r)] - pmu[EI(r)]) * psig[EI(r)];  // psig holds 1 / sigma^2 in this mode
             }
             p[r] = __builtin_fma(neg_eps, GR(r), p[r]);
           }
@@ -434,23 +454,50 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
         if (DG) RENEW_TB();
 #pragma unroll
         for (int r = 0; r < R; r++) {  // last drift, half kick
-          q[r] = __builtin_fma(aim[FC ? r : 0], p[r], q[r]);
+          q[QI(r)] = __builtin_fma(aim[FC ? r : 0], p[r], q[QI(r)]);
           if (CU) {
             double u_;
-            AEHMC_CUSTOM_ELEM(q[r], (long long)EI(r), u_, g[DG ? r : 0]);
+            AEHMC_CUSTOM_ELEM(q[QI(r)], (long long)EI(r), u_, g[GI(r)]);
           } else if (DG) {
-            g[DG ? r : 0] = (q[r] - pmu[EI(r)]) * psig[EI(r)];
+            g[GI(r)] = (q[QI(r)] - pmu[EI(r)]) * psig[EI(r)];
           }
           p[r] = __builtin_fma(-b, GR(r), p[r]);
         }
       }
+#ifdef AEHMC_JOINT_GRAD
+    } else if (JT) {
+      for (long long l = 0; l < a.L; l++) {  // trajectory.py:86-95, integrators.py:54-73
+        RENEW_TB();
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+          const double pp = p[r] - b * jg[EJ(r)];
+          const double qq = jq[EJ(r)] + aa * (im[r] * pp);
+          p[r] = pp;
+          if (VALID(r)) {
+            jq[EJ(r)] = qq;
+            jg[EJ(r)] = 0.0;
+          }
+        }
+        __syncthreads();
+        const double lp = aehmc_logp_grad_t<NW>(jq, jg, t, a.cparams);
+        __syncthreads();
+        RENEW_TB();
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+          const double gg = -jg[EJ(r)];
+          if (VALID(r)) jg[EJ(r)] = gg;  // the row holds dU/dq from here to the next leapfrog
+          p[r] = p[r] - b * gg;
+        }
+        U_joint = -lp;
+      }
+#endif
     } else if (DG) {
       for (long long l = 0; l < a.L; l++) {  // trajectory.py:86-95, integrators.py:54-73
         RENEW_TB();
 #pragma unroll
         for (int r = 0; r < R; r++) {
           double pp = p[r] - b * GR(r);
-          const double qq = q[r] + aa * (im[r] * pp);
+          const double qq = q[QI(r)] + aa * (im[r] * pp);
           double gg;
           if (CU) {
             double u_;
@@ -460,21 +507,21 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
             gg = ((qq - pmu[EI(r)]) / sd) / sd;
           }
           pp = pp - b * gg;
-          q[r] = qq;
-          g[DG ? r : 0] = gg;
+          q[QI(r)] = qq;
+          g[GI(r)] = gg;
           p[r] = pp;
         }
       }
     } else {  // dU/dq == q; b * q' ends one leapfrog and starts the next (same product, computed once)
       double bq[R];
 #pragma unroll
-      for (int r = 0; r < R; r++) bq[r] = b * q[r];
+      for (int r = 0; r < R; r++) bq[r] = b * q[QI(r)];
       for (long long l = 0; l < a.L; l++) {
 #pragma unroll
         for (int r = 0; r < R; r++) {
           p[r] = p[r] - bq[r];
-          q[r] = q[r] + aa * (im[r] * p[r]);
-          bq[r] = b * q[r];
+          q[QI(r)] = q[QI(r)] + aa * (im[r] * p[r]);
+          bq[r] = b * q[QI(r)];
           p[r] = p[r] - bq[r];
         }
       }
@@ -484,9 +531,10 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
     RENEW_TB();
 #pragma unroll
     for (int r = 0; r < R; r++) {
-      const double qq = q[r];
-      double u;
-      if (TK == AEHMC_T_STD_NORMAL) u = 0.5 * (qq * qq) + AEHMC_LOG_SQRT_2PI;
+      const double qq = JT ? 0.0 : q[QI(r)];  // (a joint target has no q in registers)
+      double u = 0.0;
+      if (JT) {  // (U = -logp of the last leapfrog: U_joint)
+      } else if (TK == AEHMC_T_STD_NORMAL) u = 0.5 * (qq * qq) + AEHMC_LOG_SQRT_2PI;
       else if (TK == AEHMC_T_ISO_GAUSSIAN) u = qq * qq;
       else if (CU) {  // (the potential is needed at the trajectory's end only: one more evaluation per transition)
         double g_;
@@ -510,7 +558,7 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
       for (int r = 0; r < R; r++) p[r] = zn[EI(r)];
     }
     sum2(usum, kd);
-    const double Unew = a.L > 0 ? (TK == AEHMC_T_ISO_GAUSSIAN ? 0.5 * usum : usum) : U;
+    const double Unew = a.L > 0 ? (JT ? U_joint : TK == AEHMC_T_ISO_GAUSSIAN ? 0.5 * usum : usum) : U;
     double delta = H0 - (Unew + 0.5 * kd);
     if (isnan(delta)) delta = -INFINITY;
     is_div = fabs(delta) > a.thr;
@@ -526,18 +574,23 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
 #pragma unroll
         for (int r = 0; r < R; r++) {
           if (!VALID(r)) continue;
-          (a.q + row)[EI(r)] = q[r];
-          (a.g + row)[EI(r)] = g[DG ? r : 0];
+          (a.q + row)[EI(r)] = QV(r);
+          (a.g + row)[EI(r)] = GV(r);
         }
       }
     } else {  // back to the transition's start
 #pragma unroll
       for (int r = 0; r < R; r++) {
-        if (DG) {
-          q[r] = qrow[EI(r)];
-          g[DG ? r : 0] = grow[EI(r)];
+        if (JT) {  // (own entries only: the next leapfrog reads them before its barrier)
+          if (VALID(r)) {
+            jq[EJ(r)] = qrow[EI(r)];
+            jg[EJ(r)] = grow[EI(r)];
+          }
+        } else if (DG) {
+          q[QI(r)] = qrow[EI(r)];
+          g[GI(r)] = grow[EI(r)];
         } else {
-          q[r] = wide_save[EI(r)];
+          q[QI(r)] = wide_save[EI(r)];
         }
       }
     }
@@ -545,7 +598,7 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
       double *dst = a.samples + (size_t)tt * tstride + row;
 #pragma unroll
       for (int r = 0; r < R; r++)
-        if (VALID(r)) dst[EI(r)] = q[r];
+        if (VALID(r)) dst[EI(r)] = QV(r);
     }
     if (t == 0) {
       if (a.acc_hist) a.acc_hist[(size_t)tt * a.C + c] = pa;
@@ -557,7 +610,7 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
 #pragma unroll
     for (int r = 0; r < R; r++) {
       if (!VALID(r)) continue;
-      (a.q + row)[EI(r)] = q[r];
+      (a.q + row)[EI(r)] = q[QI(r)];
       (a.g + row)[EI(r)] = GR(r);
     }
   }
@@ -575,6 +628,11 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
     if (a.out.is_turning) a.out.is_turning[c] = acc;  // HMC: reused as the accept flag
   }
 #undef GR
+#undef QV
+#undef GV
+#undef QI
+#undef GI
+#undef EJ
 #undef EI
 #undef VALID
 #undef MASK

@@ -68,7 +68,12 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
   // TK == AEHMC_T_CUSTOM exists only in the run-time compiled copy (aehmc_set_custom_target): the user's aehmc_custom_elem,
   // dU/dq kept beside q as for the diagonal Gaussian, no parameters of the engine's own to stream
   constexpr bool CU = TK == AEHMC_T_CUSTOM;
-  constexpr bool DG = TK == AEHMC_T_DIAG_GAUSSIAN || CU;  // otherwise dU/dq == q: no separate copy
+  // TK == AEHMC_T_JOINT exists only in the run-time compiled copy of a traced joint density (aehmc_set_custom_joint_target,
+  // AEHMC_JOINT_GRAD; D > 2048 by default): q and dU/dq are the position and gradient rows of the generated program, always
+  // in LDS, and the leapfrog's element pass splits in two around one sweep of the program by the whole workgroup
+  constexpr bool JT = TK == AEHMC_T_JOINT;
+  static_assert(!JT || QGL, "a joint density reads the position row from LDS");
+  constexpr bool DG = TK == AEHMC_T_DIAG_GAUSSIAN || CU || JT;  // otherwise dU/dq == q: no separate copy
   constexpr bool ISO = TK == AEHMC_T_ISO_GAUSSIAN;
   constexpr bool PAR_REG = R <= 8;          // per-element parameters live in VGPRs
   constexpr bool IM_LDS = !PAR_REG && !DG;  // imm in the LDS half that dU/dq does not need
@@ -156,7 +161,7 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
     const bool on = ON(r);
     const double im = imrow[im_scalar ? 0u : i];
     x.im = on ? im : 1.0;
-    if (DG && !CU) {
+    if (DG && !CU && !JT) {
       const double mu = a.mu[i], sd = a.sigma[i], ls = a.log_sigma[i];
       x.mu = on ? mu : 0.0;
       x.sd = on ? sd : 1.0;
@@ -206,6 +211,10 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
       GSET(r, gv);
       kd += (im * pv) * pv;
     }
+  }
+  if (JT && t == 0) {  // (the dummy entries, also when no slot maps to them: the program must never see anything but 0 there)
+    sq[D] = 0.0;
+    sg[D] = 0.0;
   }
   ChainRng rng = rng_load(a, c);
   ChainCtl ct = {};
@@ -322,6 +331,57 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
         if (R > 8) __builtin_amdgcn_sched_barrier(0);
       }
     };
+#ifdef AEHMC_JOINT_GRAD
+    // joint density: pass A (p_half, q' into the LDS row, the gradient row zeroed) | the program, run by every thread of
+    // the workgroup | pass B (p' from the gradient row, then what the single pass does after the target).  U = -logp,
+    // handed to the reduction by thread 0 alone (x + 0 == x: the same bits in every thread after sum4).
+    auto jpass = [&](auto fwd_tag) {
+      constexpr bool FWD = decltype(fwd_tag)::value;
+      double ph[JT ? R : 1];
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        if (r < nslots) {
+          const double pp = p[r] - b * sg[EL(r)];              // integrators.py:59-60
+          const double qq = sq[EL(r)] + aa * (IMOF(r) * pp);  // integrators.py:62-64
+          ph[JT ? r : 0] = pp;
+          if (ON(r)) {  // (a slot past D stays at the fixed point: entry D of both rows stays 0)
+            sq[EW(r)] = qq;
+            sg[EW(r)] = 0.0;
+          }
+        }
+      }
+      __syncthreads();
+      const double lp = aehmc_logp_grad_t<NW>(sq, sg, t, a.cparams);
+      __syncthreads();
+      usum = t == 0 ? -lp : 0.0;
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        if (r < nslots) {
+          const double im = IMOF(r);
+          const double gg = -sg[EL(r)];
+          if (ON(r)) sg[EW(r)] = gg;  // the row holds dU/dq from here to the next pass A
+          const double p_old = p[r], pb_old = pb[r];
+          const double pp = ph[JT ? r : 0] - b * gg;  // integrators.py:67-69
+          p[r] = pp;
+          const double v = im * pp;
+          const double s = pb_old + pp;  // trajectory.py:243
+          pb[r] = s;
+          kd += v * pp;
+          if (FWD) {  // termination.py:160-173 for level idx_max, from registers
+            const double pl = p_old, vl = im * pl;
+            const double sub = s - pb_old + pl;
+            const double rho = sub - (pp + pl) / 2;
+            d_l += vl * rho;
+            d_r += v * rho;
+          }
+        }
+      }
+    };
+    if (JT) {
+      if (fwd) jpass(WideTagTrue{});
+      else jpass(WideTagFalse{});
+    } else
+#endif
     if (fwd) pass(WideTagTrue{});
     else pass(WideTagFalse{});
     if (ck_store) {  // every fourth step: the checkpoint pair, straight from the registers
@@ -599,6 +659,8 @@ inline hipError_t launch_nuts_wide_tr(const EngineArgs &a, hipStream_t st) {
 }
 // row stride of the engine's work arrays on this path (a multiple of every team size)
 inline long long nuts_wide_ld(long long D) { return (D + 511) / 512 * 512; }
+// the engine's workspace has rows of nuts_wide_ld(D) -- what this kernel indexes -- only above D = 512 (ws_layout)
+inline bool wide_rows_padded(long long D) { return D > 512; }
 // the momentum of site #1 must already be in a.zbuf (k_draw_momentum, rows of a.ldw, zero padded)
 inline hipError_t launch_nuts_wide(const EngineArgs &a, hipStream_t st) {
   const long long D = a.D;

@@ -146,8 +146,11 @@ class Custom(Target):
         return {f"p{k}": v for k, v in enumerate(self.param_list)}
 
 
+JOINT_MAX_DIM = 10176  # a joint density with its reverse-mode program: one chain's rows in a CU's LDS (csrc/engine.cuh JOINT_WIDE_MAX_D)
+
+
 class CustomJoint(Target):
-    """A user-defined JOINT (non-separable) ``logprob_fn`` of up to 2048 coordinates -- hierarchical models, funnels:
+    """A user-defined JOINT (non-separable) ``logprob_fn`` -- hierarchical models, funnels, random effects:
     what the reference samples through aeppl's ``joint_logprob`` (tests/test_hmc.py:170-264).  ``source`` is HIP source
     defining the log-DENSITY only,
 
@@ -169,15 +172,24 @@ class CustomJoint(Target):
     lock-step path: the chain's row waits in LDS and the wavefront evaluates the density ceil(dim / 64) times per
     gradient, lane l seeding coordinate l + 64 k in pass k -- O(dim^2 / 64) density terms per leapfrog and chain.
     A density traced from a Python function (``from_callable``) brings its reverse-mode program (``grad_source``):
-    one sweep per gradient whatever the dimension, its loops spread over the wavefront's lanes."""
+    one sweep per gradient whatever the dimension, its loops spread over the wavefront's lanes.
+
+    ``dim`` goes up to 2048 for a hand-written density (forward mode only) and up to 10176 with a ``grad_source``.  Above
+    2048 NUTS and HMC with a scalar or diagonal metric run a workgroup per chain, the chain's position and gradient rows in
+    LDS (the engine's "joint_wide" option); a shared dense metric takes the lock-step path.  A dense metric per chain
+    (``is_mass_matrix_full`` adaptation) stays limited to 2048 coordinates."""
 
     kind = T_JOINT
 
     def __init__(self, source: str, dim: int, params=(), grad_source=None):
         if "aehmc_logp" not in source:
             raise ValueError("CustomJoint: the source must define aehmc_logp(const V &q, const double *const *prm)")
-        if not 1 <= int(dim) <= 2048:
-            raise ValueError("CustomJoint: 1 <= dim <= 2048")
+        if grad_source is not None:
+            if not 1 <= int(dim) <= JOINT_MAX_DIM:
+                raise ValueError(f"CustomJoint: 1 <= dim <= {JOINT_MAX_DIM} for a density with a reverse-mode program, got {int(dim)}")
+        elif not 1 <= int(dim) <= 2048:
+            raise ValueError("CustomJoint: 1 <= dim <= 2048 for a density without a reverse-mode program (a traced Python "
+                             f"function goes up to {JOINT_MAX_DIM})")
         self.user_source = str(source)
         # grad_source: the density's reverse-mode program (aehmc_logp_grad + AEHMC_JOINT_GRAD), emitted by
         # aehmc_amd/tracing.py for a traced Python function: above 64 coordinates ONE sweep per gradient
@@ -242,7 +254,7 @@ def from_callable(fn, dim, scalar=False, args=(), reverse="auto"):
     Target: ``fn`` is called ONCE on a proxy of one chain's position (a scalar proxy if ``scalar``, else a vector of
     ``dim`` entries; see ``aehmc_amd.tracing`` for what it may do with it) and the recorded expression is emitted as the
     ``aehmc_logp`` template -- a sum of per-coordinate terms becomes a ``Custom`` target (every kernel family),
-    anything else a ``CustomJoint`` target (dim <= 2048).  numpy arrays the function closes over are captured as the
+    anything else a ``CustomJoint`` target (dim <= 10176 with its reverse-mode program, 2048 with ``reverse=False``).  numpy arrays the function closes over are captured as the
     target's parameter arrays AT TRACE TIME (trace again after changing them).  An operation that cannot be traced
     raises ``TypeError`` here, not in the compiler.
 

@@ -53,8 +53,8 @@ enum aehmc_target_kind {
   AEHMC_T_LINREG = 4,       /* examples/LinearRegression.ipynb:126-166, q = [w, log n] */
   AEHMC_T_CUSTOM = 5,       /* user-defined coordinate-wise target, compiled at run time: aehmc_set_custom_target */
   AEHMC_T_GLM = 6,          /* user-defined row-reduction target over a data matrix: aehmc_set_custom_glm_target */
-  AEHMC_T_JOINT = 7         /* user-defined JOINT (non-separable) log-density, D <= 2048, differentiated by the engine:
-                               aehmc_set_custom_joint_target */
+  AEHMC_T_JOINT = 7         /* user-defined JOINT (non-separable) log-density, D <= 2048 (10176 with a reverse-mode
+                               program), differentiated by the engine: aehmc_set_custom_joint_target */
 };
 
 typedef struct {
@@ -171,7 +171,11 @@ int aehmc_set_custom_glm_target(aehmc_ctx *ctx, const char *source, int64_t D, i
  * between the stage kernels (k_target_joint_rows: the chain's row in LDS, ceil(D / 64) evaluations per gradient, lane l
  * seeding coordinate l + 64 k in pass k): any metric, O(D^2 / 64) density terms per leapfrog and chain; with a scalar or
  * diagonal metric the same loop runs for one chain per wavefront in one launch per call (k_nuts_joint_rows up to
- * D = 192, k_hmc_joint_rows at any D; bitwise the lock-step path). */
+ * D = 192, k_hmc_joint_rows at any D; bitwise the lock-step path).
+ * A source with a reverse-mode program (#define AEHMC_JOINT_GRAD: aehmc_logp_grad_t, emitted by aehmc_amd/tracing.py)
+ * may have up to 10176 coordinates.  Above 2048 one chain's position and gradient rows fill a workgroup's LDS: NUTS and
+ * HMC with a scalar / diagonal metric run k_nuts_wide / k_hmc_wide compiled against the program (option "joint_wide"),
+ * new_state and the lock-step path (a shared dense metric) evaluate it a workgroup per chain (k_target_joint_wg). */
 int aehmc_set_custom_joint_target(aehmc_ctx *ctx, const char *source, int64_t D, const double *const *params,
                                   int32_t n_params, const char *include_dir);
 
@@ -253,6 +257,12 @@ int aehmc_set_metric(aehmc_ctx *ctx, const aehmc_metric *metric);
  *                   wavefronts per chain runs the program (k_nuts_joint_wg / k_hmc_joint_wg); 0 = never (a wavefront
  *                   per chain), 2 = always.  Discrete outputs identical, values to rounding (the sums are associated
  *                   differently).  Also the workgroup-per-chain kernels of a row-reduction target (GLM, N >= 8192)
+ *  "joint_wide"  1  joint user-defined density with its reverse-mode program (AEHMC_JOINT_GRAD), scalar / diagonal metric:
+ *                   NUTS and HMC on the workgroup-per-chain kernels (k_nuts_wide / k_hmc_wide compiled against the
+ *                   program, 512 threads, the chain's position and gradient rows in LDS) -- 1: above D = 2048 (there
+ *                   the only route besides the lock-step path); 2: also for 512 < D <= 2048 (cross-checks); 0 = never
+ *                   (above 2048 the lock-step path, the density evaluated a workgroup per chain: k_target_joint_wg).
+ *                   Discrete outputs identical, values to rounding (sums associated differently)
  *  "wg_waves"    0  wavefronts per SIMD those workgroup-per-chain kernels are compiled for: 4 (two workgroups per CU,
  *                   128 registers per lane), 3 (one, 168 registers); 0 = four unless the program then keeps more than
  *                   320 bytes per lane in scratch.  Same results either way */
