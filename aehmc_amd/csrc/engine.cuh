@@ -96,6 +96,9 @@ struct EngineArgs {
   int linear;
   // compacted list of live chains for the GEMMs (built by k_compact)
   int *row_idx, *n_rows;
+  // dense MVN target on the lock-step path: the matrix its products use in place of the target's precision (null:
+  // the precision itself; whitened mode, engine.hip: H = L^T P L under an identity metric)
+  const double *white_prec;
   // caller state / outputs
   double *q, *U, *g;
   aehmc_diagnostics out;
@@ -544,6 +547,41 @@ __device__ inline void nuts_book(const EngineArgs &a, long long c, int lane, Cha
                 }
               });
     ct.U_cur = target_finish(a, wave_sum(usum));
+  } else if (FUSE == 3) {
+    // identity metric, dense target (whitened mode, engine.hip): leap_stages<0,0,1> on the fly -- p' = p_half - b g',
+    // U' = 0.5 r.g' -- then the bookkeeping pass and the first U-turn level of an odd step, as FUSE = 1 does
+    const double step_size = (ct.dir ? 1.0 : -1.0) * (a.eps_c ? a.eps_c[c] : a.eps);
+    const double b = 0.5 * step_size;
+    const double *kp = a.ckp + ((size_t)tmax * a.C + c) * a.D;
+    const double *ks = a.cks + ((size_t)tmax * a.C + c) * a.D;
+    double usum = 0.0;
+    wave_pass(a.D, lane,
+              [&](long long i) {
+                return Ld6{a.cur_g[row + i], a.rbuf[row + i], a.cur_p[row + i], step == 0 ? 0.0 : a.psub[row + i],
+                           f_turn ? kp[i] : 0.0, f_turn ? ks[i] : 0.0};
+              },
+              [&](long long i, const Ld6 &x) {
+                usum += x.b * x.a;                      // leap_stages<0,0,1>
+                const double p = x.c - b * x.a;
+                a.cur_p[row + i] = p;
+                const double v = vel_diag(a, c, i, p);  // bookkeeping pass 1
+                kd += v * p;
+                const double s = (step == 0) ? p : x.d + p;
+                a.psub[row + i] = s;
+                if (even) {
+                  ckp[i] = p;
+                  cks[i] = s;
+                }
+                if (f_turn) {                           // first level of is_iterative_turning
+                  const double pl = x.e;
+                  const double vl = vel_diag(a, c, i, pl);
+                  const double sub = s - x.f + pl;
+                  const double rho = sub - (p + pl) / 2;
+                  f_dl += vl * rho;
+                  f_dr += v * rho;
+                }
+              });
+    ct.U_cur = target_finish(a, wave_sum(usum));
   } else if (FUSE3) {
     const double step_size = (ct.dir ? 1.0 : -1.0) * (a.eps_c ? a.eps_c[c] : a.eps);
     const double b = 0.5 * step_size;
@@ -933,6 +971,24 @@ __global__ __launch_bounds__(256) void k_step_linear(EngineArgs a) {
   } else if (has_U && lane == 0) {
     a.ctl[c].U_cur = U_new;
   }
+}
+
+// Whitened dense MVN (identity metric, dense target; engine.hip): the last stage of a leapfrog fused into the
+// bookkeeping pass (nuts_book FUSE = 3), then -- a chain that goes on -- the first stages of its NEXT leapfrog
+// (p_half, z', r = z' staged for the GEMM), as k_step_linear<15, true> does: one streaming launch per lock-step
+AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_step_white(EngineArgs a) {
+  AEHMC_CHAIN_OF_WAVE();
+  ChainCtl ct = a.ctl[c];
+  if (ct.done) return;
+  ChainRng rng = rng_load(a, c);
+  nuts_book<false, 3>(a, c, lane, ct, rng);
+  rng_store(a, c, lane, rng, 1, 3);
+  if (!ct.done) {
+    __threadfence_block();
+    double U_next = 0.0;
+    (void)leap_stages<true, true, false, false>(a, c, lane, ct.dir, U_next);  // (dense target: no U here)
+  }
+  if (lane == 0) a.ctl[c] = ct;
 }
 
 // ascending list of live chains + count (one 1024-thread block; deterministic order).  Runs after every lock-step
@@ -1462,6 +1518,47 @@ AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_half_dot(EngineArgs a, c
   for (long long i = lane; i < a.D; i += 64) s += x[row + i] * y[row + i];
   s = wave_sum(s);
   if (lane == 0) out[c] = 0.5 * s;
+}
+// whitened mode, end of a transition: q = L z + mu into `q` and r = q - mu into `r` (k_residual's arithmetic), `y` = L z
+AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_white_q(EngineArgs a, const double *y, double *q, double *r) {
+  AEHMC_CHAIN_OF_WAVE();
+  const size_t row = (size_t)c * a.D;
+  for (long long i = lane; i < a.D; i += 64) {
+    const double qi = y[row + i] + a.mu[i];
+    q[row + i] = qi;
+    r[row + i] = qi - a.mu[i];
+  }
+}
+// whitened mode: a chain whose returned point is its initial one (z == z0, every coordinate bit for bit: an HMC
+// rejection, a NUTS proposal never replaced) keeps the caller's (q, U, g); every other chain takes the fresh evaluation
+// (qn, Un, gn) at q = mu + L z
+AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_white_out(EngineArgs a, const double *z, const double *z0,
+                                                   const double *qn, const double *gn, const double *Un) {
+  AEHMC_CHAIN_OF_WAVE();
+  const size_t row = (size_t)c * a.D;
+  int moved = 0;
+  for (long long i = lane; i < a.D; i += 64)
+    moved |= __double_as_longlong(z[row + i]) != __double_as_longlong(z0[row + i]);
+  if (!__any(moved)) return;
+  for (long long i = lane; i < a.D; i += 64) {
+    a.q[row + i] = qn[row + i];
+    a.g[row + i] = gn[row + i];
+  }
+  if (lane == 0) a.U[c] = Un[c];
+}
+// whitened mode, once per binding: L (lower triangle of the Cholesky factor, zeros above) and its transpose
+AEHMC_TU_LOCAL __global__ void k_tril_pair(const double *src, double *L, double *Lt, long long n) {
+  const long long i = (long long)blockIdx.y * 32 + threadIdx.y, j = (long long)blockIdx.x * 32 + threadIdx.x;
+  if (i >= n || j >= n) return;
+  const double v = j <= i ? src[i * n + j] : 0.0;
+  L[i * n + j] = v;
+  Lt[j * n + i] = v;
+}
+// dst = (src + src^T) / 2, n x n (exactly symmetric: the two sums of a pair add the same two numbers)
+AEHMC_TU_LOCAL __global__ void k_symmetrize(const double *src, double *dst, long long n) {
+  const long long i = (long long)blockIdx.y * 32 + threadIdx.y, j = (long long)blockIdx.x * 32 + threadIdx.x;
+  if (i >= n || j >= n) return;
+  dst[i * n + j] = 0.5 * (src[i * n + j] + src[j * n + i]);
 }
 AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_vel_diag(EngineArgs a, const double *p, double *v) {
   AEHMC_CHAIN_OF_WAVE();

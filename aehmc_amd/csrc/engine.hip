@@ -60,6 +60,7 @@ struct aehmc_ctx {
   int opt_resident_nuts = 2;      // register-resident single-launch NUTS: 0 off, 1 on, 2 auto
   bool opt_fused_nuts = false;   // whole NUTS transition in one launch (diag metric, coordinate-wise target)
   bool opt_dense_linear = true;  // one metric GEMM per leapfrog (v carried by linearity)
+  bool opt_dense_whiten = true;  // dense MVN, shared dense metric, D > 512, lock-step: leapfrog in whitened coordinates
   bool opt_compact = true;       // finished chains drop out of the GEMMs
   int opt_block_roll = 0;        // block-resident NUTS: waiting chains that trigger a begin round (0: kernel default)
   int opt_joint_wg = 1;          // traced joint densities with long sweeps: a workgroup per chain (0 never, 1 when it pays, 2 always)
@@ -116,6 +117,12 @@ struct aehmc_ctx {
     std::map<std::string, hipFunction_t> fn;
   };
   std::map<std::string, RtcProgram> rtc;
+  // whitened dense MVN (white_prepare): imm = L L^T, z = L^-1 (q - mu), r = L^T p; the problem is then a Gaussian of
+  // precision H = L^T P L under the identity metric.  Formed from the bound arrays on first use, dropped on every
+  // aehmc_set_target / aehmc_set_metric
+  bool wh_ready = false;
+  double *wh_L = nullptr, *wh_Linv = nullptr, *wh_H = nullptr;  // [D, D] row-major: L, L^-1 = sqrt_mass^T, H
+  double *wh_zero = nullptr, *wh_one = nullptr;                 // mu of the whitened target [D] (zeros); the metric 1.0
 };
 
 #define HIPCHK(expr)                                                                     \
@@ -133,6 +140,14 @@ struct aehmc_ctx {
   } while (0)
 
 static inline dim3 chain_grid(int64_t C) { return dim3((unsigned)((C + 3) / 4)); }
+// drops the whitened operator (hipFree waits for the launches that still read it)
+static void white_release(aehmc_ctx *ctx) {
+  for (double **p : {&ctx->wh_L, &ctx->wh_Linv, &ctx->wh_H, &ctx->wh_zero, &ctx->wh_one}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  ctx->wh_ready = false;
+}
 constexpr int LINREG_SMAX = 32;
 // row slices per chain group: enough workgroups (~2048) to fill the GPU
 static inline int linreg_slices(int64_t C) {
@@ -201,6 +216,7 @@ extern "C" int aehmc_destroy(aehmc_ctx *ctx) {
   if (ctx->glm_XT) (void)hipFree(ctx->glm_XT);
   if (ctx->glm_z) (void)hipFree(ctx->glm_z);
   if (ctx->glm_lsum) (void)hipFree(ctx->glm_lsum);
+  white_release(ctx);
   for (auto &kv : ctx->rtc)
     if (kv.second.mod) (void)hipModuleUnload(kv.second.mod);
   for (int i = 0; i < NRING; i++)
@@ -233,6 +249,7 @@ extern "C" int aehmc_set_target(aehmc_ctx *ctx, const aehmc_target *t) {
     default:
       FAIL("unknown target kind");
   }
+  white_release(ctx);
   ctx->tgt = *t;
   ctx->has_tgt = true;
   if (ctx->log_sigma) {
@@ -552,6 +569,7 @@ extern "C" int aehmc_set_custom_glm_target(aehmc_ctx *ctx, const char *source, i
   aehmc_target t{};
   t.kind = AEHMC_T_GLM;
   t.D = D;
+  white_release(ctx);
   ctx->tgt = t;
   ctx->has_tgt = true;
   return 0;
@@ -624,6 +642,7 @@ extern "C" int aehmc_set_custom_joint_target(aehmc_ctx *ctx, const char *source,
   aehmc_target t{};
   t.kind = AEHMC_T_JOINT;
   t.D = D;
+  white_release(ctx);
   ctx->tgt = t;
   ctx->has_tgt = true;
   return 0;
@@ -638,6 +657,7 @@ extern "C" int aehmc_set_custom_target(aehmc_ctx *ctx, const char *source, int64
   aehmc_target t{};
   t.kind = AEHMC_T_CUSTOM;
   t.D = D;
+  white_release(ctx);
   ctx->tgt = t;
   ctx->has_tgt = true;
   return 0;
@@ -646,6 +666,26 @@ extern "C" int aehmc_set_custom_target(aehmc_ctx *ctx, const char *source, int64
 static int gemm(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, const double *A, int64_t lda,
                 const double *B, int64_t ldb, double *Cm, int64_t ldc, hipStream_t st,
                 const int *row_idx = nullptr, const int *n_rows = nullptr, int mode = 0);
+
+// Blocked (64-wide) right-looking Cholesky of Lw [D,D] in place (lower triangle; the upper one keeps the input);
+// `inv`, `invT`: [NB,NB] scratch each, `info`: the first failed pivot
+static int dense_cholesky(aehmc_ctx *ctx, double *Lw, int64_t D, double *inv, double *invT, int *info, hipStream_t st) {
+  const int NB = FACT_NB;
+  int rc = 0;
+  for (int64_t j0 = 0; j0 < D && !rc; j0 += NB) {
+    const int nb = (int)((D - j0 < NB) ? D - j0 : NB);
+    const int64_t M = D - j0 - nb;
+    hipLaunchKernelGGL(k_potrf_trtri, dim3(1), dim3(256), 0, st, Lw + j0 * D + j0, (long long)D, nb, 1, inv,
+                       invT, info, (int)j0);
+    if (M > 0) {
+      double *panel = Lw + (j0 + nb) * D + j0;
+      rc = gemm(ctx, M, nb, nb, panel, D, inv, NB, panel, D, st);                     // L21 = A21 L11^-T
+      if (!rc) rc = gemm(ctx, M, M, nb, panel, D, panel, D, Lw + (j0 + nb) * D + (j0 + nb), D, st, nullptr,
+                         nullptr, 1);                                                   // A22 -= L21 L21^T
+    }
+  }
+  return rc;
+}
 
 // metrics.py:56-58: L = cholesky(imm); mass_matrix_sqrt = solve_triangular(L, I, lower, trans)
 // = L^-T.  Blocked (64-wide) right-looking Cholesky and blocked triangular inverse; the
@@ -671,18 +711,7 @@ static int dense_sqrt_mass(aehmc_ctx *ctx, const double *imm, int64_t D, double 
     ctx->err = "dense metric: device copy failed";
     return done(-1);
   }
-  for (int64_t j0 = 0; j0 < D && !rc; j0 += NB) {  // Cholesky
-    const int nb = (int)((D - j0 < NB) ? D - j0 : NB);
-    const int64_t M = D - j0 - nb;
-    hipLaunchKernelGGL(k_potrf_trtri, dim3(1), dim3(256), 0, st, Lw + j0 * D + j0, (long long)D, nb, 1, inv,
-                       invT, info, (int)j0);
-    if (M > 0) {
-      double *panel = Lw + (j0 + nb) * D + j0;
-      rc = gemm(ctx, M, nb, nb, panel, D, inv, NB, panel, D, st);                     // L21 = A21 L11^-T
-      if (!rc) rc = gemm(ctx, M, M, nb, panel, D, panel, D, Lw + (j0 + nb) * D + (j0 + nb), D, st, nullptr,
-                         nullptr, 1);                                                   // A22 -= L21 L21^T
-    }
-  }
+  rc = dense_cholesky(ctx, Lw, D, inv, invT, info, st);
   const int64_t nblk = (D + NB - 1) / NB;
   for (int64_t kb = nblk - 1; kb >= 0 && !rc; kb--) {  // L^-1, block column by block column
     const int64_t j0 = kb * NB;
@@ -746,6 +775,7 @@ extern "C" int aehmc_set_metric(aehmc_ctx *ctx, const aehmc_metric *m) {
     }
     met.sqrt_mass = ctx->own_sqrt_mass;
   }
+  white_release(ctx);
   ctx->met = met;
   ctx->has_met = true;
   return 0;
@@ -922,6 +952,10 @@ extern "C" int aehmc_set_option(aehmc_ctx *ctx, const char *name, int64_t value)
   }
   if (!strcmp(name, "dense_linear")) {
     ctx->opt_dense_linear = value != 0;
+    return 0;
+  }
+  if (!strcmp(name, "dense_whiten")) {
+    ctx->opt_dense_whiten = value != 0;
     return 0;
   }
   if (!strcmp(name, "gemm_small_tiles")) {
@@ -1241,6 +1275,118 @@ static int launch_joint_rows(aehmc_ctx *ctx, const EngineArgs &a, const double *
     }                                                                                                   \
   } while (0)
 
+// ---- whitened dense MVN ("dense_whiten").  NUTS and HMC are equivariant under q = mu + L z, p = L^-T r
+// with imm = L L^T: in (z, r) the target is a Gaussian of precision H = L^T P L, the metric the identity, the kinetic
+// energy r.r / 2, and the momentum draw r = the raw normals.  A leapfrog then needs ONE chain-batched product (H z')
+// instead of two (P q', imm g').  Every transition maps in and out on its own.
+static bool white_wanted(const aehmc_ctx *ctx, const EngineArgs &a) {
+  return ctx->opt_dense_whiten && a.linear && a.tkind == AEHMC_T_DENSE_MVN && a.met_ndim == 2 && !ctx->met.per_chain &&
+         a.D > 512;
+}
+// L from a Cholesky of imm (the factor whose L^-T the bound sqrt_mass is: metrics.py:56-58), L^-1 = sqrt_mass^T, and
+// H = (L^T P) L by two GEMMs, symmetrised.  Once per (target, metric) binding, from the bound arrays, on the stream of
+// the first call that needs it.  (Not a factorisation of the caller's metric: aehmc_metric_sqrt is that.)
+static int white_prepare(aehmc_ctx *ctx, hipStream_t st) {
+  if (ctx->wh_ready) return 0;
+  white_release(ctx);
+  const int64_t D = ctx->tgt.D;
+  const size_t mb = (size_t)D * D * sizeof(double);
+  const int NB = FACT_NB;
+  double *Lw = nullptr, *Lt = nullptr, *M = nullptr, *small = nullptr;
+  int *info = nullptr;
+  const bool prof = ctx->prof;  // (the formation's GEMMs are not the profiled workload's)
+  auto done = [&](int r) {
+    (void)hipFree(Lw); (void)hipFree(Lt); (void)hipFree(M); (void)hipFree(small); (void)hipFree(info);
+    ctx->prof = prof;
+    if (r) white_release(ctx);
+    return r;
+  };
+  if (hipMalloc((void **)&ctx->wh_L, mb) != hipSuccess || hipMalloc((void **)&ctx->wh_Linv, mb) != hipSuccess ||
+      hipMalloc((void **)&ctx->wh_H, mb) != hipSuccess || hipMalloc((void **)&ctx->wh_zero, D * sizeof(double)) != hipSuccess ||
+      hipMalloc((void **)&ctx->wh_one, sizeof(double)) != hipSuccess || hipMalloc((void **)&Lw, mb) != hipSuccess ||
+      hipMalloc((void **)&Lt, mb) != hipSuccess || hipMalloc((void **)&M, mb) != hipSuccess ||
+      hipMalloc((void **)&small, (size_t)2 * NB * NB * sizeof(double)) != hipSuccess ||
+      hipMalloc((void **)&info, sizeof(int)) != hipSuccess) {
+    ctx->err = "whitened dense MVN: device allocation failed";
+    return done(-1);
+  }
+  static const double one = 1.0;
+  if (hipMemcpyAsync(Lw, ctx->met.imm, mb, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+      hipMemsetAsync(info, 0, sizeof(int), st) != hipSuccess ||
+      hipMemsetAsync(ctx->wh_zero, 0, D * sizeof(double), st) != hipSuccess ||
+      hipMemcpyAsync(ctx->wh_one, &one, sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) {
+    ctx->err = "whitened dense MVN: device copy failed";
+    return done(-1);
+  }
+  ctx->prof = false;
+  int rc = dense_cholesky(ctx, Lw, D, small, small + NB * NB, info, st);
+  const dim3 grid((unsigned)((D + 31) / 32), (unsigned)((D + 31) / 32));
+  if (!rc) {
+    hipLaunchKernelGGL(k_tril_pair, grid, dim3(32, 32), 0, st, (const double *)Lw, ctx->wh_L, Lt, (long long)D);
+    hipLaunchKernelGGL(k_transpose, grid, dim3(32, 8), 0, st, ctx->met.sqrt_mass, ctx->wh_Linv, (long long)D);
+    rc = gemm(ctx, D, D, D, Lt, D, ctx->tgt.prec, D, M, D, st);   // M = L^T P   (P symmetric: its rows are its columns)
+  }
+  if (!rc) rc = gemm(ctx, D, D, D, M, D, Lt, D, Lw, D, st);      // M L (the rows of L^T are the columns of L)
+  if (!rc) {
+    hipLaunchKernelGGL(k_symmetrize, grid, dim3(32, 32), 0, st, (const double *)Lw, ctx->wh_H, (long long)D);
+    int h_info = 0;
+    if (hipMemcpyAsync(&h_info, info, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
+      ctx->err = "whitened dense MVN: kernels failed";
+      rc = -1;
+    } else if (h_info) {
+      ctx->err = "dense inverse mass matrix is not positive definite (pivot " + std::to_string(h_info) + ")";
+      rc = -2;
+    }
+  }
+  if (!rc) ctx->wh_ready = true;
+  return done(rc);
+}
+// state and momentum of the whitened problem in workspace vectors that the dense-metric layout holds and the identity
+// metric leaves unused
+struct WhiteBufs {
+  double *z, *hz, *z0, *r, *qn, *gn, *Un, *Uw;
+};
+// z0 = L^-1 (q0 - mu), H z0 (the product the leapfrogs form), U0 the caller's (U is invariant); `b` = the whitened
+// problem's arguments: identity metric, mu = 0, precision H
+static int white_begin(aehmc_ctx *ctx, const EngineArgs &a, EngineArgs &b, WhiteBufs &w, hipStream_t st) {
+  if (int rc = white_prepare(ctx, st)) return rc;
+  const int64_t C = a.C, D = a.D;
+  w.z = a.cur_w; w.hz = a.end_w[0]; w.z0 = a.end_w[1]; w.r = a.cur_v; w.qn = a.end_v[0]; w.gn = a.end_v[1];
+  w.Un = a.ckv; w.Uw = a.ckv + C;
+  LAUNCH(k_residual, C, st, a, (const double *)a.q, a.rbuf);
+  if (gemm(ctx, C, D, D, a.rbuf, D, ctx->wh_Linv, D, w.z, D, st)) return -1;
+  if (gemm(ctx, C, D, D, w.z, D, ctx->wh_H, D, w.hz, D, st)) return -1;
+  HIPCHK(hipMemcpyAsync(w.z0, w.z, (size_t)C * D * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(w.Uw, a.U, (size_t)C * sizeof(double), hipMemcpyDeviceToDevice, st));
+  b = a;
+  b.met_ndim = 0;
+  b.imm = b.sqrt_mass = ctx->wh_one;
+  b.imm_cs = 0;
+  b.linear = 0;
+  b.mu = ctx->wh_zero;
+  b.white_prec = ctx->wh_H;
+  b.cur_v = b.cur_w = b.ckv = nullptr;
+  for (int e = 0; e < 2; e++) b.end_v[e] = b.end_w[e] = nullptr;
+  b.q = w.z; b.g = w.hz; b.U = w.Uw;
+  b.out.momentum = w.r;
+  return 0;
+}
+// p = L^-T r (today's momentum product), q = mu + L z, then (U, g) evaluated afresh at q as aehmc_new_state does; a
+// chain whose returned point is its initial one keeps the caller's (q0, U0, g0)
+static int white_end(aehmc_ctx *ctx, const EngineArgs &a, const WhiteBufs &w, hipStream_t st) {
+  const int64_t C = a.C, D = a.D;
+  if (a.out.momentum)
+    if (metric_mul(ctx, C, w.r, ctx->met.sqrt_mass, a.out.momentum, st)) return -1;
+  if (gemm(ctx, C, D, D, w.z, D, ctx->wh_L, D, w.qn, D, st)) return -1;
+  LAUNCH(k_white_q, C, st, a, (const double *)w.qn, w.qn, a.rbuf);
+  if (gemm(ctx, C, D, D, a.rbuf, D, ctx->tgt.prec, D, w.gn, D, st)) return -1;
+  LAUNCH(k_half_dot, C, st, a, (const double *)a.rbuf, (const double *)w.gn, w.Un);
+  LAUNCH(k_white_out, C, st, a, (const double *)w.z, (const double *)w.z0, (const double *)w.qn,
+         (const double *)w.gn, (const double *)w.Un);
+  return 0;
+}
+
 // one lock-step leapfrog of every live chain (integrators.py:54-73); `book` appends the
 // NUTS bookkeeping; `need_v` says whether v' = imm p' must be formed (dense metric);
 // `ri`/`nr`: compacted live-chain list for the GEMMs (may be null)
@@ -1253,7 +1399,7 @@ static int launch_leapfrog(aehmc_ctx *ctx, const EngineArgs &a, bool book, bool 
   // targets evaluated between the stages: dense MVN (GEMM), linear regression (row sums), user-defined row reduction,
   // user-defined joint density
   auto target_ext = [&]() -> int {
-    if (tdense) return gemm(ctx, C, D, D, a.rbuf, D, ctx->tgt.prec, D, a.cur_g, D, st, ri, nr);
+    if (tdense) return gemm(ctx, C, D, D, a.rbuf, D, a.white_prec ? a.white_prec : ctx->tgt.prec, D, a.cur_g, D, st, ri, nr);
     if (tglm) return launch_glm(ctx, a, a.cur_q, a.cur_g, nullptr, 1, st, ri, nr);
     if (tjoint) return launch_joint_rows(ctx, a, a.cur_q, a.cur_g, nullptr, 1, st, ri, nr);
     return launch_linreg(ctx, a, a.cur_q, a.cur_g, nullptr, 1, st);
@@ -1265,9 +1411,14 @@ static int launch_leapfrog(aehmc_ctx *ctx, const EngineArgs &a, bool book, bool 
     return 0;
   }
   if (!md && text) {
-    LAUNCH((k_step<true, true, false, false, false>), C, st, a);
+    // (whitened dense MVN, NUTS lock-step loop: the first stages of every leapfrog but the first ride in the previous
+    //  step's bookkeeping launch -- k_step_white)
+    if (!(book && ctx->pre_done)) LAUNCH((k_step<true, true, false, false, false>), C, st, a);
     if (target_ext()) return -1;
-    if (book) LAUNCH((k_step<false, false, true, false, true>), C, st, a);
+    if (book && ctx->fuse_pre) {
+      LAUNCH(k_step_white, C, st, a);
+      ctx->pre_done = true;
+    } else if (book) LAUNCH((k_step<false, false, true, false, true>), C, st, a);
     else LAUNCH((k_step<false, false, true, false, false>), C, st, a);
     return 0;
   }
@@ -1670,9 +1821,15 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
     return prof_end(ctx, st, p);
   }
   ctx->rows_hint = 0;
-  ctx->fuse_pre = a.linear != 0;
+  const bool white = white_wanted(ctx, a);
+  EngineArgs wa;  // whitened mode: the transition runs on the whitened problem (white_begin), mapped back at the end
+  WhiteBufs wb{};
+  if (white)
+    if (int rc = white_begin(ctx, a, wa, wb, st)) return rc;
+  const EngineArgs &e = white ? wa : a;
+  ctx->fuse_pre = a.linear != 0 || white;
   ctx->pre_done = false;
-  if (int rc = launch_begin(ctx, a, true, st)) return rc;
+  if (int rc = launch_begin(ctx, e, true, st)) return rc;
   long long maxsteps = 0;
   for (int j = 0; j < max_num_expansions; j++) maxsteps += (1LL << j) + 1;  // 2**j + 1 per expansion
   const bool compact = ctx->opt_compact && (a.met_ndim == 2 || a.tkind == AEHMC_T_DENSE_MVN || a.tkind == AEHMC_T_GLM || a.tkind == AEHMC_T_JOINT);
@@ -1694,7 +1851,7 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
     }
     const int slot = batch % NRING;
     for (int k = 0; k < STEP_BATCH && s < maxsteps; k++, s++) {
-      if (int rc = launch_leapfrog(ctx, a, true, true, st, ri, nr)) return rc;
+      if (int rc = launch_leapfrog(ctx, e, true, true, st, ri, nr)) return rc;
       if (compact) {
         const bool last = (k == STEP_BATCH - 1) || (s == maxsteps - 1);
         hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, st, (const ChainCtl *)a.ctl,
@@ -1712,6 +1869,7 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
   }
   ctx->rows_hint = 0;
   ctx->fuse_pre = ctx->pre_done = false;
+  if (white) return white_end(ctx, a, wb, st);
   return 0;
 }
 
@@ -2110,12 +2268,20 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
     if (T > 1 && out->n_leapfrog) LAUNCH(k_fill_i64, C, st, (long long *)out->n_leapfrog, (long long)C, (long long)(L * T));
     return 0;
   }
+  const bool white = white_wanted(ctx, a);
   for (int64_t t = 0; t < T; t++) {
-    if (int rc = launch_begin(ctx, a, false, st)) return rc;
+    EngineArgs wa;  // whitened mode: each transition mapped in and out on its own (white_begin / white_end)
+    WhiteBufs wb{};
+    if (white)
+      if (int rc = white_begin(ctx, a, wa, wb, st)) return rc;
+    const EngineArgs &e = white ? wa : a;
+    if (int rc = launch_begin(ctx, e, false, st)) return rc;
     for (int64_t l = 0; l < L; l++)
-      if (int rc = launch_leapfrog(ctx, a, false, l == L - 1, st)) return rc;
-    if (a.met_ndim == 2) LAUNCH(k_hmc_end<true>, C, st, a, (long long)L);
-    else LAUNCH(k_hmc_end<false>, C, st, a, (long long)L);
+      if (int rc = launch_leapfrog(ctx, e, false, l == L - 1, st)) return rc;
+    if (e.met_ndim == 2) LAUNCH(k_hmc_end<true>, C, st, e, (long long)L);
+    else LAUNCH(k_hmc_end<false>, C, st, e, (long long)L);
+    if (white)
+      if (int rc = white_end(ctx, a, wb, st)) return rc;
     if (samples)
       HIPCHK(hipMemcpyAsync(samples + (size_t)t * C * D, q, (size_t)C * D * sizeof(double),
                             hipMemcpyDeviceToDevice, st));

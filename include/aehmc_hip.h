@@ -212,6 +212,16 @@ int aehmc_set_metric(aehmc_ctx *ctx, const aehmc_metric *metric);
  *  "dense_linear" 1 dense metric: carry w = imm g with the state so that
  *                   v_half = v - (eps/2) w, v' = v_half - (eps/2) w' (one metric GEMM per
  *                   leapfrog); 0 forms imm p_half and imm p' directly as metrics.py:71 does
+ *  "dense_whiten" 1 dense-precision Gaussian target (AEHMC_T_DENSE_MVN) under a shared dense inverse mass matrix,
+ *                   "dense_linear" = 1, D > 512, lock-step path (NUTS and HMC): every transition maps the state to
+ *                   z = L^-1 (q - mu), r = L^T p with imm = L L^T, runs its leapfrogs there -- a Gaussian of
+ *                   precision H = L^T P L under the identity metric, ONE chain-batched product per leapfrog -- and
+ *                   maps back: q = mu + L z, p = L^-T r, U and dU/dq evaluated afresh at q (as aehmc_new_state does);
+ *                   a chain whose returned point is its initial one returns the caller's q, U, dU/dq unchanged.
+ *                   Same discrete outputs and RNG consumption, reals equal up to rounding.  L, L^-1 and H are formed
+ *                   from the BOUND arrays (prec, imm, sqrt_mass) once per binding and dropped by aehmc_set_target /
+ *                   aehmc_set_metric: a caller who edits them in place must bind them again.  0 = two products per
+ *                   leapfrog in the original coordinates
  *  "gemm_small_tiles" 1  fp64 GEMM of a mid-size problem (fewer than 256 tiles of 128 x 128, N <= 2048):
  *                   1 = 64 x 128, 64 x 64 or 32 x 64 tiles, the largest that gives every CU two
  *                   workgroups (bitwise the results of the 128 x 128 kernel); 2 / 3 / 4 force
