@@ -1110,18 +1110,21 @@ static int prof_drain(aehmc_ctx *ctx) {
   ctx->prof_used = 0;
   return 0;
 }
-static int prof_begin(aehmc_ctx *ctx, hipStream_t st, bool &on) {
-  on = ctx->prof && !ctx->prof_ev.empty();
-  if (!on) return 0;
-  if (ctx->prof_used + 2 > ctx->prof_ev.size())
-    if (int rc = prof_drain(ctx)) return rc;
-  HIPCHK(hipEventRecord(ctx->prof_ev[ctx->prof_used], st));
-  return 0;
-}
-static int prof_end(aehmc_ctx *ctx, hipStream_t st, bool on) {
-  if (!on) return 0;
-  HIPCHK(hipEventRecord(ctx->prof_ev[ctx->prof_used + 1], st));
-  ctx->prof_used += 2;
+// `launch` (a callable: int(bool profiled), 0 on success) between the two events of a pair.  When it fails its error
+// is returned at once: the end event is not recorded and the pair is not counted.
+template <class Launch>
+static int profiled(aehmc_ctx *ctx, hipStream_t st, Launch launch) {
+  const bool on = ctx->prof && !ctx->prof_ev.empty();
+  if (on) {
+    if (ctx->prof_used + 2 > ctx->prof_ev.size())
+      if (int rc = prof_drain(ctx)) return rc;
+    HIPCHK(hipEventRecord(ctx->prof_ev[ctx->prof_used], st));
+  }
+  if (int rc = launch(on)) return rc;
+  if (on) {
+    HIPCHK(hipEventRecord(ctx->prof_ev[ctx->prof_used + 1], st));
+    ctx->prof_used += 2;
+  }
   return 0;
 }
 // A stream-K hand-off that timed out leaves garbage partial sums: every entry point that waits
@@ -1146,19 +1149,19 @@ extern "C" int aehmc_synchronize(aehmc_ctx *ctx, void *stream) {
 static int gemm(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, const double *A, int64_t lda,
                 const double *B, int64_t ldb, double *Cm, int64_t ldc, hipStream_t st,
                 const int *row_idx, const int *n_rows, int mode) {
-  bool p = false;
-  if (int rc = prof_begin(ctx, st, p)) return rc;
-  if (int rc = check_device_errors(ctx)) return rc;
-  GemmStreamK sk{ctx->sk_partial, ctx->sk_flags, ctx->d_err, ++ctx->sk_epoch};
-  const bool use_sk = ctx->opt_streamk && ctx->sk_grid > 0;
-  // the kernels read the exact row count on the device; the host only picks the kernel and the
-  // grid, from an upper bound: live chains never increase within a transition, so the count seen
-  // at the last poll bounds every later launch (few rows left: smaller tiles, no persistent grid)
-  if (n_rows && ctx->rows_hint > 0 && ctx->rows_hint < M) M = ctx->rows_hint;
-  HIPCHK(tu::gemm_nt_f64(M, N, K, A, lda, B, ldb, Cm, ldc, st, row_idx, n_rows,
-                            p ? ctx->d_flops : nullptr, (use_sk && mode == 0) ? &sk : nullptr, ctx->sk_grid,
-                            mode, ctx->opt_streamk == 2 ? ctx->sk_grid_wide : 0, ctx->opt_gemm_small));
-  return prof_end(ctx, st, p);
+  return profiled(ctx, st, [&](bool p) -> int {
+    if (int rc = check_device_errors(ctx)) return rc;
+    GemmStreamK sk{ctx->sk_partial, ctx->sk_flags, ctx->d_err, ++ctx->sk_epoch};
+    const bool use_sk = ctx->opt_streamk && ctx->sk_grid > 0;
+    // the kernels read the exact row count on the device; the host only picks the kernel and the
+    // grid, from an upper bound: live chains never increase within a transition, so the count seen
+    // at the last poll bounds every later launch (few rows left: smaller tiles, no persistent grid)
+    if (n_rows && ctx->rows_hint > 0 && ctx->rows_hint < M) M = ctx->rows_hint;
+    HIPCHK(tu::gemm_nt_f64(M, N, K, A, lda, B, ldb, Cm, ldc, st, row_idx, n_rows,
+                           p ? ctx->d_flops : nullptr, (use_sk && mode == 0) ? &sk : nullptr, ctx->sk_grid,
+                           mode, ctx->opt_streamk == 2 ? ctx->sk_grid_wide : 0, ctx->opt_gemm_small));
+    return 0;
+  });
 }
 
 // X [C,D] times the metric matrix `mat` (imm or sqrt_mass): one GEMM over all chains when the
@@ -1617,6 +1620,20 @@ static int nuts_path(const aehmc_ctx *ctx, int64_t C, int64_t max_num_expansions
   return NUTS_PATH_LOCKSTEP;
 }
 
+// The NutsSampleArgs of a route.  The caller's multi-transition request is taken -- and *multi_done set -- where the
+// route's kernel runs all of it in its one launch (`allowed`, a callable asked only when there is a request); otherwise
+// ONE transition.
+template <class Allowed>
+static NutsSampleArgs take_multi(const NutsSampleArgs *multi, bool *multi_done, Allowed allowed) {
+  NutsSampleArgs m{};
+  m.T = 1;
+  if (multi && multi_done && allowed()) {
+    m = *multi;
+    *multi_done = true;
+  }
+  return m;
+}
+
 // One NUTS transition of every chain.  `multi` (optional): the caller wants multi->T transitions with
 // per-transition outputs; a kernel that runs them all in one launch does so and sets *multi_done,
 // otherwise ONE transition is run and the caller loops.
@@ -1634,191 +1651,134 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
   // The single-launch kernels (teams of <= 64 lanes up to D = 512, a workgroup per chain above, the
   // workgroup-cooperative regression kernel) are taken wherever they exist; the lock-step engine below serves
   // dense metrics, dense targets, and `resident_nuts` = 0.
-  if (nuts_path(ctx, C, max_num_expansions) == NUTS_PATH_LINREG) {
-    NutsSampleArgs m{};
-    m.T = 1;
-    if (multi && multi_done && !(multi->adapt && a.met_ndim == 2 && !(multi->ad.full && ctx->met.per_chain))) {
-      m = *multi;
-      *multi_done = true;
-    }
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    HIPCHK(tu::nuts_linreg(a, m, st));
-    return prof_end(ctx, st, p);
-  }
   const int path = nuts_path(ctx, C, max_num_expansions);
-  if (path == NUTS_PATH_TEAMS || path == NUTS_PATH_WIDE) {
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    if (path == NUTS_PATH_WIDE) {  // one workgroup per chain (nuts_wide.cuh): momentum drawn at one wavefront per chain first
+  if (path == NUTS_PATH_LINREG) {
+    const NutsSampleArgs m = take_multi(multi, multi_done, [&] {
+      return !(multi->adapt && a.met_ndim == 2 && !(multi->ad.full && ctx->met.per_chain));
+    });
+    return profiled(ctx, st, [&](bool) -> int { HIPCHK(tu::nuts_linreg(a, m, st)); return 0; });
+  }
+  if (path == NUTS_PATH_WIDE) {  // one workgroup per chain (nuts_wide.cuh): momentum drawn at one wavefront per chain first
+    return profiled(ctx, st, [&](bool) -> int {
       if (!wide_rows_padded(a.D))  // (rows of nuts_wide_ld(D) would run past the workspace's vectors)
         FAIL("internal: the workgroup-per-chain NUTS kernel needs D > 512, got D = " + std::to_string(a.D));
       a.ldw = nuts_wide_ld(a.D);
       hipLaunchKernelGGL(k_draw_momentum, chain_grid(C), dim3(256), 0, st, a.rng, a.nsites, (long long)C,
                          (long long)a.D, a.sqrt_mass, (long long)a.imm_cs, a.met_ndim, a.zbuf, a.ldw, 1);
       HIPCHK(hipGetLastError());
-      if (a.tkind == AEHMC_T_CUSTOM) {  // the same instantiation (launch_nuts_wide's table), compiled against the user's function
-        const long long D = a.D;
-        const int T = D <= 2048 ? 256 : 512, R = D <= 1024 ? 4 : (D <= 4096 ? 8 : (D <= 8192 ? 16 : 20));
-        const bool qgl = D > 4096;
-        const std::string name = "aehmc::k_nuts_wide<" + std::to_string(T) + ", " + std::to_string(R) + ", " +
-                                 (qgl ? "true" : "false") + ", " + std::to_string((int)AEHMC_T_CUSTOM) + ">";
-        const size_t dyn = qgl ? (size_t)2 * (D + 1) * sizeof(double) : 0;  // (q and dU/dq in LDS)
-        if (int rc = rtc_launch(ctx, "wide", {name}, name, dim3((unsigned)C), dim3(T), dyn, st, a)) return rc;
-      } else if (a.tkind == AEHMC_T_JOINT) {  // traced joint density: the rows of its program (q, dU/dq) in LDS at every D
+      if (a.tkind == AEHMC_T_CUSTOM) {  // the same instantiation (plan_nuts_wide), compiled against the user's function
+        const NutsWidePlan pl = plan_nuts_wide(a.D);
+        const std::string name = "aehmc::k_nuts_wide<" + std::to_string(pl.T) + ", " + std::to_string(pl.R) + ", " +
+                                 (pl.qgl ? "true" : "false") + ", " + std::to_string((int)AEHMC_T_CUSTOM) + ">";
+        return rtc_launch(ctx, "wide", {name}, name, dim3((unsigned)C), dim3(pl.T), pl.dyn, st, a);
+      }
+      if (a.tkind == AEHMC_T_JOINT) {  // traced joint density: the rows of its program (q, dU/dq) in LDS at every D
         const std::string name = "aehmc::k_nuts_wide<512, " + std::to_string(joint_wide_r(a.D)) + ", true, " +
                                  std::to_string((int)AEHMC_T_JOINT) + ">";
-        if (int rc = joint_rows_launch(ctx, "jwide", {name}, name, a.D + 1, dim3((unsigned)C), dim3(512), st, a)) return rc;
-      } else {
-        HIPCHK(tu::nuts_wide(a, st));
+        return joint_rows_launch(ctx, "jwide", {name}, name, a.D + 1, dim3((unsigned)C), dim3(512), st, a);
       }
-    } else {  // teams of <= 64 lanes: any number of transitions in one launch
-      NutsSampleArgs m{};
-      m.T = 1;
-      if (multi && multi_done) {
-        m = *multi;
-        *multi_done = true;
-      }
+      HIPCHK(tu::nuts_wide(a, st));
+      return 0;
+    });
+  }
+  if (path == NUTS_PATH_TEAMS) {  // teams of <= 64 lanes: any number of transitions in one launch
+    const NutsSampleArgs m = take_multi(multi, multi_done, [] { return true; });
+    return profiled(ctx, st, [&](bool) -> int {
       if (a.tkind == AEHMC_T_CUSTOM) {  // the same instantiation, compiled against the user's function
         const ResidentPlan pl = plan_nuts_resident(a, m, ctx->opt_resident_min_team);
         const std::string name = "aehmc::k_nuts_resident<" + std::to_string(pl.T) + ", " + std::to_string(pl.R) + ", " +
                                  (pl.multi ? "true" : "false") + ", 0, " + (pl.ckl ? "true" : "false") + ">";
-        if (int rc = rtc_launch(ctx, "nuts", {name}, name, dim3(pl.grid), dim3(256), pl.dyn, st, a, m)) return rc;
-      } else if (a.tkind == AEHMC_T_JOINT) {  // joint density with a reverse-mode program: one wavefront per chain, rows in LDS
+        return rtc_launch(ctx, "nuts", {name}, name, dim3(pl.grid), dim3(256), pl.dyn, st, a, m);
+      }
+      if (a.tkind == AEHMC_T_JOINT) {  // joint density with a reverse-mode program: one wavefront per chain, rows in LDS
         ResidentPlan pl = plan_nuts_resident(a, m, 0);
         pl.T = 64;
         pl.R = a.D <= 64 ? 1 : a.D <= 128 ? 2 : a.D <= 256 ? 4 : 8;
         const std::string name = "aehmc::k_nuts_resident<64, " + std::to_string(pl.R) + ", " + (pl.multi ? "true" : "false") + ", 0, false>";
-        if (int rc = rtc_launch(ctx, "jnuts", {name}, name, dim3((unsigned)((C + 3) / 4)), dim3(256),
-                                (size_t)4 * 2 * a.D * sizeof(double), st, a, m))
-          return rc;
-      } else {
-        HIPCHK(tu::nuts_resident(a, m, st, ctx->opt_resident_min_team));
+        return rtc_launch(ctx, "jnuts", {name}, name, dim3((unsigned)((C + 3) / 4)), dim3(256),
+                          (size_t)4 * 2 * a.D * sizeof(double), st, a, m);
       }
-    }
-    return prof_end(ctx, st, p);
+      HIPCHK(tu::nuts_resident(a, m, st, ctx->opt_resident_min_team));
+      return 0;
+    });
   }
   if (path == NUTS_PATH_FUSED_DENSE) {  // small dense problems: k_nuts_resident's DENSE instantiations
     const bool md = a.met_ndim == 2, td = a.tkind == AEHMC_T_DENSE_MVN, pc = md && ctx->met.per_chain;
     a.linear = 0;  // literal products (metrics.py:71)
-    NutsSampleArgs m{};
-    m.T = 1;
-    if (multi && multi_done && (!multi->adapt || (pc && multi->ad.full))) {  // (adaptation in the launch: per-chain dense)
-      m = *multi;
-      *multi_done = true;
-    }
+    // (adaptation in the launch: per-chain dense)
+    NutsSampleArgs m = take_multi(multi, multi_done, [&] { return (!multi->adapt || (pc && multi->ad.full)); });
     m.prec = ctx->tgt.prec;
     if (pc)
       if (int rc = fused_dense_workspace(ctx, (size_t)C * a.D * a.D * sizeof(double), &m.imm_ws)) return rc;
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    if (a.tkind == AEHMC_T_JOINT) {  // the same kernel, compiled against the user's density (DENSE bit 8: joint target)
-      const int dense = (md ? RES_DENSE_METRIC : 0) | (pc ? RES_DENSE_PER_CHAIN : 0) | RES_DENSE_JOINT;
-      const bool mlt = m.T > 1 || m.samples || m.acc_hist || m.div_hist || m.nleap_total || m.adapt;
-      const std::string name = "aehmc::k_nuts_resident<64, 1, " + std::string(mlt ? "true" : "false") + ", " +
-                               std::to_string(dense) + ", false>";
-      const size_t dyn = (size_t)(md && !pc ? 2 : 0) * a.D * a.D * sizeof(double);
-      const unsigned grid = (unsigned)((C + RES_DENSE_BLOCK / 64 - 1) / (RES_DENSE_BLOCK / 64));
-      if (int rc = rtc_launch(ctx, "jnuts", {name}, name, dim3(grid), dim3(RES_DENSE_BLOCK), dyn, st, a, m)) return rc;
-    } else {
+    return profiled(ctx, st, [&](bool) -> int {
+      if (a.tkind == AEHMC_T_JOINT) {  // the same kernel, compiled against the user's density (DENSE bit 8: joint target)
+        const int dense = (md ? RES_DENSE_METRIC : 0) | (pc ? RES_DENSE_PER_CHAIN : 0) | RES_DENSE_JOINT;
+        const bool mlt = m.T > 1 || m.samples || m.acc_hist || m.div_hist || m.nleap_total || m.adapt;
+        const std::string name = "aehmc::k_nuts_resident<64, 1, " + std::string(mlt ? "true" : "false") + ", " +
+                                 std::to_string(dense) + ", false>";
+        const size_t dyn = (size_t)(md && !pc ? 2 : 0) * a.D * a.D * sizeof(double);
+        const unsigned grid = (unsigned)((C + RES_DENSE_BLOCK / 64 - 1) / (RES_DENSE_BLOCK / 64));
+        return rtc_launch(ctx, "jnuts", {name}, name, dim3(grid), dim3(RES_DENSE_BLOCK), dyn, st, a, m);
+      }
       HIPCHK(tu::nuts_resident_dense(a, m, st, md, td, pc));
-    }
-    return prof_end(ctx, st, p);
+      return 0;
+    });
   }
   if (path == NUTS_PATH_BLOCK_DENSE) {  // mid-size dense problems: every transition of the call in one launch
-    NutsSampleArgs m{};
-    m.T = 1;
-    if (multi && multi_done && !multi->adapt) {
-      m = *multi;
-      *multi_done = true;
-    }
+    NutsSampleArgs m = take_multi(multi, multi_done, [&] { return !multi->adapt; });
     m.prec = ctx->tgt.prec;
     m.roll = ctx->opt_block_roll;
     double *bp = nullptr;
     if (int rc = block_pack_workspace(ctx, a.D, &bp)) return rc;
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    if (a.tkind == AEHMC_T_CUSTOM) {  // the transition-by-transition kernels, compiled against the user's function
-      BlkMats mats;
-      HIPCHK(blk_pack_matrices(a, nullptr, bp, mats, st));
-      EngineArgs b = a;
-      b.imm = mats.imm; b.sqrt_mass = mats.sqrt_mass;
-      const bool reg = ctx->opt_block_dense != 2 && block_reg_supported(a.D);
-      const std::string name = reg ? "aehmc::k_nuts_block_reg<" + std::string(a.D <= 128 ? "2" : "4") + ", false>"
-                                   : std::string("aehmc::k_nuts_block_dense<false>");
-      const size_t dyn = reg ? blk_reg_lds_bytes(a.D) : blk_lds_bytes(a.D);
-      if (int rc = rtc_launch(ctx, "block", {name}, name, dim3((unsigned)((C + BLK_CHAINS - 1) / BLK_CHAINS)),
-                              dim3(BLK_THREADS), dyn, st, b, m))
-        return rc;
-    } else if (ctx->opt_block_dense != 2 && block_roll_wanted(a.D, m.T, ctx->opt_block_roll)) HIPCHK(tu::nuts_block_roll(a, m, bp, st));
-    else if (ctx->opt_block_dense != 2 && block_reg_supported(a.D)) HIPCHK(tu::nuts_block_reg(a, m, bp, st));
-    else HIPCHK(tu::nuts_block_dense(a, m, bp, st));
-    return prof_end(ctx, st, p);
+    return profiled(ctx, st, [&](bool) -> int {
+      if (a.tkind == AEHMC_T_CUSTOM) {  // the transition-by-transition kernels, compiled against the user's function
+        BlkMats mats;
+        HIPCHK(blk_pack_matrices(a, nullptr, bp, mats, st));
+        EngineArgs b = a;
+        b.imm = mats.imm; b.sqrt_mass = mats.sqrt_mass;
+        const bool reg = ctx->opt_block_dense != 2 && block_reg_supported(a.D);
+        const std::string name = reg ? "aehmc::k_nuts_block_reg<" + std::string(a.D <= 128 ? "2" : "4") + ", false>"
+                                     : std::string("aehmc::k_nuts_block_dense<false>");
+        const size_t dyn = reg ? blk_reg_lds_bytes(a.D) : blk_lds_bytes(a.D);
+        return rtc_launch(ctx, "block", {name}, name, dim3((unsigned)((C + BLK_CHAINS - 1) / BLK_CHAINS)),
+                          dim3(BLK_THREADS), dyn, st, b, m);
+      }
+      if (ctx->opt_block_dense != 2 && block_roll_wanted(a.D, m.T, ctx->opt_block_roll)) HIPCHK(tu::nuts_block_roll(a, m, bp, st));
+      else if (ctx->opt_block_dense != 2 && block_reg_supported(a.D)) HIPCHK(tu::nuts_block_reg(a, m, bp, st));
+      else HIPCHK(tu::nuts_block_dense(a, m, bp, st));
+      return 0;
+    });
   }
   if (path == NUTS_PATH_GLM_ROWS) {  // row-reduction target, D <= 32, scalar / diagonal metric: every transition of the call in one launch
-    NutsSampleArgs m{};
-    m.T = 1;
-    if (multi && multi_done && !multi->adapt) {
-      m = *multi;
-      *multi_done = true;
-    }
+    const NutsSampleArgs m = take_multi(multi, multi_done, [&] { return !multi->adapt; });
     const bool wg = glm_wg_wanted(ctx, a.D, C);
     const std::string name = wg ? glm_wg_name("k_nuts_glm_wg", a.D) : glm_rows_name("k_nuts_glm_rows", a.D);
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    std::string prog = "glmk";
-    if (wg)
-      if (int rc = wg_program(ctx, "glmk", {name}, name, &prog)) return rc;
-    if (int rc = rtc_launch(ctx, prog, {name}, name, wg ? dim3((unsigned)C) : chain_grid(C), dim3(wg ? 512 : 256), 0, st, a, m,
-                            (const double *)ctx->glm_XT, ctx->glm_y, (long long)ctx->glm_N))
-      return rc;
-    return prof_end(ctx, st, p);
+    return profiled(ctx, st, [&](bool) -> int {
+      std::string prog = "glmk";
+      if (wg)
+        if (int rc = wg_program(ctx, "glmk", {name}, name, &prog)) return rc;
+      return rtc_launch(ctx, prog, {name}, name, wg ? dim3((unsigned)C) : chain_grid(C), dim3(wg ? 512 : 256), 0, st, a, m,
+                        (const double *)ctx->glm_XT, ctx->glm_y, (long long)ctx->glm_N);
+    });
   }
   if (path == NUTS_PATH_JOINT_WG) {  // traced joint density, long sweeps, few chains: a workgroup per chain, one launch per call
-    NutsSampleArgs m{};
-    m.T = 1;
-    if (multi && multi_done && !multi->adapt) {
-      m = *multi;
-      *multi_done = true;
-    }
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    std::string prog;
-    if (int rc = wg_program(ctx, "jwg", RTC_JWG, RTC_JWG[0], &prog)) return rc;
-    if (int rc = rtc_launch(ctx, prog, RTC_JWG, RTC_JWG[0], dim3((unsigned)C), dim3(512), (size_t)2 * a.D * sizeof(double), st, a, m))
-      return rc;
-    return prof_end(ctx, st, p);
+    const NutsSampleArgs m = take_multi(multi, multi_done, [&] { return !multi->adapt; });
+    return profiled(ctx, st, [&](bool) -> int {
+      std::string prog;
+      if (int rc = wg_program(ctx, "jwg", RTC_JWG, RTC_JWG[0], &prog)) return rc;
+      return rtc_launch(ctx, prog, RTC_JWG, RTC_JWG[0], dim3((unsigned)C), dim3(512), (size_t)2 * a.D * sizeof(double), st, a, m);
+    });
   }
   if (path == NUTS_PATH_JOINT_ROWS) {  // joint target, D > 64, scalar / diagonal metric: every transition of the call in one launch
-    NutsSampleArgs m{};
-    m.T = 1;
-    if (multi && multi_done && !multi->adapt) {
-      m = *multi;
-      *multi_done = true;
-    }
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    if (int rc = rtc_launch(ctx, "jbase", RTC_JBASE, RTC_JBASE[2], chain_grid(C), dim3(256), (size_t)8 * a.D * sizeof(double), st, a, m))
-      return rc;
-    return prof_end(ctx, st, p);
+    const NutsSampleArgs m = take_multi(multi, multi_done, [&] { return !multi->adapt; });
+    return profiled(ctx, st, [&](bool) -> int { return rtc_launch(ctx, "jbase", RTC_JBASE, RTC_JBASE[2], chain_grid(C), dim3(256), (size_t)8 * a.D * sizeof(double), st, a, m); });
   }
   if (path == NUTS_PATH_PC_DENSE) {  // per-chain dense metrics, 64 < D <= 512: every transition of the call in one launch
-    NutsSampleArgs m{};
-    m.T = 1;
-    if (multi && multi_done && !multi->adapt) {
-      m = *multi;
-      *multi_done = true;
-    }
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    HIPCHK(tu::nuts_pc_dense(a, m, st));
-    return prof_end(ctx, st, p);
+    const NutsSampleArgs m = take_multi(multi, multi_done, [&] { return !multi->adapt; });
+    return profiled(ctx, st, [&](bool) -> int { HIPCHK(tu::nuts_pc_dense(a, m, st)); return 0; });
   }
   if (ctx->opt_fused_nuts && a.met_ndim < 2 && target_is_elem_host(a.tkind)) {
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    LAUNCH(k_nuts_fused, C, st, a);
-    return prof_end(ctx, st, p);
+    return profiled(ctx, st, [&](bool) -> int { LAUNCH(k_nuts_fused, C, st, a); return 0; });
   }
   ctx->rows_hint = 0;
   const bool white = white_wanted(ctx, a);
@@ -1992,6 +1952,73 @@ extern "C" int aehmc_nuts_sample(aehmc_ctx *ctx, int64_t C, uint64_t *rng, doubl
   return 0;
 }
 
+// which kernel family an HMC call takes, as nuts_path for NUTS: the first condition that holds, read from the bound
+// target / metric and the options alone (of what fill_args puts into EngineArgs: a.tkind = ctx->tgt.kind, a.met_ndim =
+// ctx->met.ndim, a.linear = dense metric && "dense_linear").  hmc_run holds one block per route and no condition.
+enum { HMC_PATH_LOCKSTEP = 0, HMC_PATH_FUSED, HMC_PATH_CUSTOM_FUSED, HMC_PATH_JOINT_FUSED, HMC_PATH_LINREG, HMC_PATH_WIDE,
+       HMC_PATH_FUSED_DENSE, HMC_PATH_GLM_ROWS, HMC_PATH_JOINT_WG, HMC_PATH_JOINT_ROWS, HMC_PATH_PC_DENSE, HMC_PATH_BLOCK_DENSE };
+static int hmc_path(const aehmc_ctx *ctx, int64_t C) {
+  const int tkind = ctx->tgt.kind, nd = ctx->met.ndim;
+  const int64_t D = ctx->tgt.D;
+  // fused register-resident path (hmc_fused.cuh): diagonal/scalar metric, coordinate-wise target
+  if (ctx->opt_fused_hmc && hmc_fused_supported(ctx->tgt.kind, ctx->met.ndim, D)) return HMC_PATH_FUSED;
+  // user-defined coordinate-wise target: the same fused kernel, compiled against the user's function at run time
+  if (ctx->opt_fused_hmc && ctx->tgt.kind == AEHMC_T_CUSTOM && ctx->met.ndim < 2 && D <= 1024) return HMC_PATH_CUSTOM_FUSED;
+  // traced joint density with its reverse-mode program, 64 < D <= 1024: the same fused kernel ("joint_resident" option;
+  // D <= 64 stays on k_hmc_fused_dense)
+  if (ctx->opt_fused_hmc && ctx->opt_joint_resident && ctx->tgt.kind == AEHMC_T_JOINT && joint_has_grad(ctx) && ctx->met.ndim < 2 &&
+      D > FUSED_DENSE_MAX_D && D <= 1024 && !joint_wg_wanted(ctx, C) && !joint_wide_wanted(ctx))
+    return HMC_PATH_JOINT_FUSED;
+  // regression target (hmc_linreg.cuh)
+  if (ctx->opt_fused_hmc && hmc_linreg_supported(ctx->tgt.kind, ctx->met.ndim, D)) return HMC_PATH_LINREG;
+  // a workgroup per chain (k_hmc_wide); a user-defined coordinate-wise target: the same kernel compiled against the user's function
+  const bool custom_wide = ctx->tgt.kind == AEHMC_T_CUSTOM && ctx->met.ndim < 2 && D > 1024 && D <= 10240;
+  // (a traced joint density above 2048 coordinates: the AEHMC_T_JOINT instantiation, the program's rows in LDS)
+  const bool joint_wide = joint_wide_wanted(ctx);
+  if (ctx->opt_fused_hmc && (custom_wide || joint_wide || hmc_resident_supported(ctx->tgt.kind, ctx->met.ndim, D))) return HMC_PATH_WIDE;
+  // small dense problems (shared dense metric and / or dense-precision target, D <= 64): the transition in one
+  // launch with the products inside the wavefront (k_hmc_fused_dense), as for NUTS
+  const bool tjoint = tkind == AEHMC_T_JOINT;
+  const bool fused_dense = ctx->opt_fused_hmc && D <= FUSED_DENSE_MAX_D && !(tjoint && nd < 2 && joint_wg_wanted(ctx, C)) &&
+                           (tjoint || ((nd == 2 || tkind == AEHMC_T_DENSE_MVN) &&
+                                       (target_is_elem_host(tkind) || tkind == AEHMC_T_DENSE_MVN)));
+  if (fused_dense) return HMC_PATH_FUSED_DENSE;
+  // row-reduction target with D <= 32, scalar / diagonal metric (glm_rows.cuh)
+  if (ctx->opt_fused_hmc && tkind == AEHMC_T_GLM && nd < 2 && (glm_rows_wanted(D, C) || glm_wg_wanted(ctx, D, C))) return HMC_PATH_GLM_ROWS;
+  // traced joint density with long data sweeps, few chains: a workgroup per chain (k_hmc_joint_wg)
+  if (ctx->opt_fused_hmc && tjoint && nd < 2 && D <= JOINT_ROWS_MAX_D && joint_wg_wanted(ctx, C)) return HMC_PATH_JOINT_WG;
+  // joint target of more than 64 coordinates, scalar / diagonal metric (k_hmc_joint_rows)
+  if (ctx->opt_fused_hmc && tjoint && nd < 2 && D <= JOINT_ROWS_MAX_D) return HMC_PATH_JOINT_ROWS;
+  const bool linear = nd == 2 && ctx->opt_dense_linear;  // (fill_args: a.linear)
+  // one dense metric per chain, 64 < D <= 512, coordinate-wise target, linear dense mode (nuts_pc_dense.cuh)
+  if (ctx->opt_fused_hmc && ctx->opt_pc_dense && linear && nuts_pc_dense_supported(tkind, nd, ctx->met.per_chain, D)) return HMC_PATH_PC_DENSE;
+  // mid-size dense problems (shared dense metric, 64 < D <= 512, linear dense mode; nuts_block.cuh)
+  const bool custom_block = tkind == AEHMC_T_CUSTOM && nd == 2 && !ctx->met.per_chain && D >= BLK_MIN_D && D <= BLK_MAX_D;
+  if (ctx->opt_fused_hmc && ctx->opt_block_dense && linear && (custom_block || block_dense_supported(tkind, nd, ctx->met.per_chain, D)))
+    return HMC_PATH_BLOCK_DENSE;
+  return HMC_PATH_LOCKSTEP;
+}
+// what every whole-call kernel on HmcFusedArgs reads of the call; the route adds its target's parameters, its literal
+// `tkind`, the per-transition outputs and, where its kernel has the mode, `fc`
+static HmcFusedArgs hmc_fused_args(const aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, int64_t L,
+                                   double divergence_threshold, double *q, double *U, double *g, const aehmc_diagnostics *out) {
+  HmcFusedArgs f{};
+  f.C = C; f.D = ctx->tgt.D; f.L = L; f.eps = step_size; f.thr = divergence_threshold;
+  f.met_ndim = ctx->met.ndim; f.imm = ctx->met.imm; f.sqrt_mass = ctx->met.sqrt_mass;
+  f.imm_cs = ctx->met.per_chain ? (ctx->met.ndim == 0 ? 1 : f.D) : 0;
+  f.eps_c = ctx->eps_c;
+  f.rng = rng; f.q = q; f.U = U; f.g = g; f.out = *out;
+  return f;
+}
+// n_leapfrog = L T of every chain behind a kernel that ran the whole call.  `only_multi`: the route's kernel writes it
+// itself when T == 1 (which routes do is kernel behaviour)
+static int fill_n_leapfrog(aehmc_ctx *ctx, int64_t C, int64_t L, int64_t T, const aehmc_diagnostics *out, bool only_multi,
+                           hipStream_t st) {
+  if ((!only_multi || T > 1) && out->n_leapfrog)
+    LAUNCH(k_fill_i64, C, st, (long long *)out->n_leapfrog, (long long)C, (long long)(L * T));
+  return 0;
+}
+
 // T HMC transitions of every chain; optional per-transition outputs (samples [T,C,D],
 // acc_hist [T,C], div_hist [T,C])
 static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, int64_t L,
@@ -2003,97 +2030,45 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
   if (!out->acceptance_probability || !out->is_diverging) FAIL("diagnostics arrays missing");
   if (!ctx->has_tgt || !ctx->has_met) FAIL("set_target and set_metric must be called first");
   const int64_t D = ctx->tgt.D;
-  // fused register-resident path (hmc_fused.cuh): diagonal/scalar metric, coordinate-wise target
-  if (ctx->opt_fused_hmc && hmc_fused_supported(ctx->tgt.kind, ctx->met.ndim, D)) {
+  const int path = hmc_path(ctx, C);
+  // The first four routes run the whole call in one launch on HmcFusedArgs alone: no workspace, so no fill_args (they
+  // never report "workspace too small" or "dimensions differ").
+  if (path == HMC_PATH_FUSED || path == HMC_PATH_CUSTOM_FUSED || path == HMC_PATH_JOINT_FUSED || path == HMC_PATH_LINREG) {
     if (int rc = check_per_chain(ctx, C)) return rc;
-    HmcFusedArgs f{};
-    f.C = C; f.D = D; f.L = L; f.eps = step_size; f.thr = divergence_threshold;
-    f.met_ndim = ctx->met.ndim; f.imm = ctx->met.imm; f.sqrt_mass = ctx->met.sqrt_mass;
-    f.imm_cs = ctx->met.per_chain ? (ctx->met.ndim == 0 ? 1 : D) : 0;
-    f.eps_c = ctx->eps_c;
-    f.tkind = ctx->tgt.kind; f.mu = ctx->tgt.mu; f.sigma = ctx->tgt.sigma; f.log_sigma = ctx->log_sigma;
-    f.rng = rng; f.q = q; f.U = U; f.g = g; f.out = *out;
+    HmcFusedArgs f = hmc_fused_args(ctx, C, rng, step_size, L, divergence_threshold, q, U, g, out);
     f.T = T; f.samples = samples; f.acc_hist = acc_hist; f.div_hist = div_hist;
-    f.fc = ctx->opt_fp_contract;
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    HIPCHK(tu::hmc_fused(f, st));
-    return prof_end(ctx, st, p);
-  }
-  // user-defined coordinate-wise target: the same fused kernel, compiled against the user's function at run time
-  if (ctx->opt_fused_hmc && ctx->tgt.kind == AEHMC_T_CUSTOM && ctx->met.ndim < 2 && D <= 1024) {
-    if (int rc = check_per_chain(ctx, C)) return rc;
-    HmcFusedArgs f{};
-    f.C = C; f.D = D; f.L = L; f.eps = step_size; f.thr = divergence_threshold;
-    f.met_ndim = ctx->met.ndim; f.imm = ctx->met.imm; f.sqrt_mass = ctx->met.sqrt_mass;
-    f.imm_cs = ctx->met.per_chain ? (ctx->met.ndim == 0 ? 1 : D) : 0;
-    f.eps_c = ctx->eps_c;
-    f.tkind = AEHMC_T_CUSTOM; f.cparams = ctx->d_cparams;
-    f.rng = rng; f.q = q; f.U = U; f.g = g; f.out = *out;
-    f.T = T; f.samples = samples; f.acc_hist = acc_hist; f.div_hist = div_hist;
-    f.fc = ctx->opt_fp_contract;
-    const int R = hmc_fused_r(D);
-    const std::string name = "aehmc::k_hmc_fused<" + std::to_string(R) + ", 5, " + (f.fc ? "true" : "false") + ">";
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    if (int rc = rtc_launch(ctx, "hmc", {name}, name, dim3((unsigned)((C + 3) / 4)), dim3(256),
-                            (size_t)4 * R * 64 * sizeof(double), st, f))
-      return rc;
-    return prof_end(ctx, st, p);
-  }
-  // traced joint density with its reverse-mode program, 64 < D <= 1024 (round 6): the same fused kernel with the position
-  // and gradient rows of the generated program in LDS ("joint_resident" option; D <= 64 stays on k_hmc_fused_dense)
-  if (ctx->opt_fused_hmc && ctx->opt_joint_resident && ctx->tgt.kind == AEHMC_T_JOINT && joint_has_grad(ctx) && ctx->met.ndim < 2 &&
-      D > FUSED_DENSE_MAX_D && D <= 1024 && !joint_wg_wanted(ctx, C) && !joint_wide_wanted(ctx)) {
-    if (int rc = check_per_chain(ctx, C)) return rc;
-    HmcFusedArgs f{};
-    f.C = C; f.D = D; f.L = L; f.eps = step_size; f.thr = divergence_threshold;
-    f.met_ndim = ctx->met.ndim; f.imm = ctx->met.imm; f.sqrt_mass = ctx->met.sqrt_mass;
-    f.imm_cs = ctx->met.per_chain ? (ctx->met.ndim == 0 ? 1 : D) : 0;
-    f.eps_c = ctx->eps_c;
+    if (path == HMC_PATH_FUSED) {  // fused register-resident path (hmc_fused.cuh): diagonal/scalar metric, coordinate-wise target
+      f.tkind = ctx->tgt.kind; f.mu = ctx->tgt.mu; f.sigma = ctx->tgt.sigma; f.log_sigma = ctx->log_sigma;
+      f.fc = ctx->opt_fp_contract;
+      return profiled(ctx, st, [&](bool) -> int { HIPCHK(tu::hmc_fused(f, st)); return 0; });
+    }
+    if (path == HMC_PATH_LINREG) {  // regression target: the whole call in one launch, four chains per workgroup (hmc_linreg.cuh)
+      f.tkind = ctx->tgt.kind; f.X = ctx->tgt.X; f.y = ctx->tgt.y; f.N = ctx->tgt.N;
+      return profiled(ctx, st, [&](bool) -> int { HIPCHK(tu::hmc_linreg(f, st)); return 0; });
+    }
+    if (path == HMC_PATH_CUSTOM_FUSED) {  // user-defined coordinate-wise target: the same fused kernel, compiled against the user's function at run time
+      f.tkind = AEHMC_T_CUSTOM; f.cparams = ctx->d_cparams;
+      f.fc = ctx->opt_fp_contract;
+      const int R = hmc_fused_r(D);
+      const std::string name = "aehmc::k_hmc_fused<" + std::to_string(R) + ", 5, " + (f.fc ? "true" : "false") + ">";
+      return profiled(ctx, st, [&](bool) -> int {
+        return rtc_launch(ctx, "hmc", {name}, name, dim3((unsigned)((C + 3) / 4)), dim3(256), (size_t)4 * R * 64 * sizeof(double), st, f);
+      });
+    }
+    // traced joint density (round 6): the same fused kernel with the position and gradient rows of the generated program in LDS
     f.tkind = AEHMC_T_JOINT; f.cparams = ctx->d_cparams;
-    f.rng = rng; f.q = q; f.U = U; f.g = g; f.out = *out;
-    f.T = T; f.samples = samples; f.acc_hist = acc_hist; f.div_hist = div_hist;
     const int R = hmc_fused_r(D);
     const std::string name = "aehmc::k_hmc_fused<" + std::to_string(R) + ", " + std::to_string((int)AEHMC_T_JOINT) + ", false>";
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    if (int rc = rtc_launch(ctx, "jhmcf", {name}, name, dim3((unsigned)((C + 3) / 4)), dim3(256),
-                            (size_t)4 * 2 * R * 64 * sizeof(double), st, f))
-      return rc;
-    return prof_end(ctx, st, p);
-  }
-  // regression target: the whole call in one launch, four chains per workgroup (hmc_linreg.cuh)
-  if (ctx->opt_fused_hmc && hmc_linreg_supported(ctx->tgt.kind, ctx->met.ndim, D)) {
-    if (int rc = check_per_chain(ctx, C)) return rc;
-    HmcFusedArgs f{};
-    f.C = C; f.D = D; f.L = L; f.eps = step_size; f.thr = divergence_threshold;
-    f.met_ndim = ctx->met.ndim; f.imm = ctx->met.imm; f.sqrt_mass = ctx->met.sqrt_mass;
-    f.imm_cs = ctx->met.per_chain ? (ctx->met.ndim == 0 ? 1 : D) : 0;
-    f.eps_c = ctx->eps_c;
-    f.tkind = ctx->tgt.kind; f.X = ctx->tgt.X; f.y = ctx->tgt.y; f.N = ctx->tgt.N;
-    f.rng = rng; f.q = q; f.U = U; f.g = g; f.out = *out;
-    f.T = T; f.samples = samples; f.acc_hist = acc_hist; f.div_hist = div_hist;
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    HIPCHK(tu::hmc_linreg(f, st));
-    return prof_end(ctx, st, p);
+    return profiled(ctx, st, [&](bool) -> int {
+      return rtc_launch(ctx, "jhmcf", {name}, name, dim3((unsigned)((C + 3) / 4)), dim3(256), (size_t)4 * 2 * R * 64 * sizeof(double), st, f);
+    });
   }
   EngineArgs a;
   if (int rc = fill_args(ctx, C, 1, a)) return rc;
-  // (a user-defined coordinate-wise target: the same kernel compiled against the user's function at run time, round 5)
-  const bool custom_wide = ctx->tgt.kind == AEHMC_T_CUSTOM && ctx->met.ndim < 2 && D > 1024 && D <= 10240;
-  // (a traced joint density above 2048 coordinates: the AEHMC_T_JOINT instantiation, the program's rows in LDS)
-  const bool joint_wide = joint_wide_wanted(ctx);
-  if (ctx->opt_fused_hmc && (custom_wide || joint_wide || hmc_resident_supported(ctx->tgt.kind, ctx->met.ndim, D))) {
-    HmcFusedArgs f{};
-    f.C = C; f.D = D; f.L = L; f.eps = step_size; f.thr = divergence_threshold;
-    f.met_ndim = ctx->met.ndim; f.imm = ctx->met.imm; f.sqrt_mass = ctx->met.sqrt_mass;
-    f.imm_cs = ctx->met.per_chain ? (ctx->met.ndim == 0 ? 1 : D) : 0;
-    f.eps_c = ctx->eps_c;
+  if (path == HMC_PATH_WIDE) {  // a workgroup per chain (k_hmc_wide), coordinate-wise target or traced joint density
+    HmcFusedArgs f = hmc_fused_args(ctx, C, rng, step_size, L, divergence_threshold, q, U, g, out);
     f.tkind = ctx->tgt.kind; f.mu = ctx->tgt.mu; f.sigma = ctx->tgt.sigma; f.log_sigma = ctx->log_sigma;
     f.cparams = ctx->d_cparams;
-    f.rng = rng; f.q = q; f.U = U; f.g = g; f.out = *out;
     f.fc = ctx->opt_fp_contract;
     // A launch pair per CHUNK of transitions: the momenta of the chunk are drawn first, at one wavefront per
     // chain (k_draw_momentum), into [nt][C][D]; the workgroup-per-chain kernel then runs the nt transitions
@@ -2111,46 +2086,39 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
         (char *)a.zbuf + vec > (char *)ctx->ws + ctx->ws_bytes || (char *)a.cur_q < (char *)ctx->ws)
       FAIL("internal: the workspace span for the momentum rows is not the layout hmc_run expects");
     double *zall = a.cur_q;
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    for (int64_t t0 = 0; t0 < T; t0 += cap) {
-      const int nt = (int)(T - t0 < cap ? T - t0 : cap);
-      hipLaunchKernelGGL(k_draw_momentum, chain_grid(C), dim3(256), 0, st, rng, 2, (long long)C, (long long)D,
-                         f.sqrt_mass, f.imm_cs, f.met_ndim, zall, (long long)D, nt);
-      HIPCHK(hipGetLastError());
-      f.samples = samples ? samples + (size_t)t0 * C * D : nullptr;
-      f.acc_hist = acc_hist ? acc_hist + (size_t)t0 * C : nullptr;
-      f.div_hist = div_hist ? div_hist + (size_t)t0 * C : nullptr;
-      f.out.momentum = t0 + nt == T ? out->momentum : nullptr;  // only the last transition's is observable
-      if (custom_wide) {  // launch_hmc_resident's table
-        const int TT = D <= 2048 ? 256 : (D <= 4096 ? 512 : 1024), R = D <= 8192 ? 8 : 10;
-        const std::string name = "aehmc::k_hmc_wide<" + std::to_string(TT) + ", " + std::to_string(R) + ", " +
-                                 std::to_string((int)AEHMC_T_CUSTOM) + ", " + (f.fc ? "true" : "false") + ">";
-        if (int rc = rtc_launch(ctx, "hmc", {name}, name, dim3((unsigned)C), dim3(TT), 0, st, f, (const double *)zall, nt))
-          return rc;
-      } else if (joint_wide) {  // k_nuts_wide's table: 512 threads (the program's workgroup), q and dU/dq in LDS only
-        const std::string name = "aehmc::k_hmc_wide<512, " + std::to_string(joint_wide_r(D)) + ", " +
-                                 std::to_string((int)AEHMC_T_JOINT) + ", false>";
-        if (int rc = joint_rows_launch(ctx, "jwide", {name}, name, D + 1, dim3((unsigned)C), dim3(512), st, f, (const double *)zall, nt))
-          return rc;
-      } else {
-        HIPCHK(tu::hmc_resident(f, zall, nt, st));
+    return profiled(ctx, st, [&](bool) -> int {
+      for (int64_t t0 = 0; t0 < T; t0 += cap) {
+        const int nt = (int)(T - t0 < cap ? T - t0 : cap);
+        hipLaunchKernelGGL(k_draw_momentum, chain_grid(C), dim3(256), 0, st, rng, 2, (long long)C, (long long)D,
+                           f.sqrt_mass, f.imm_cs, f.met_ndim, zall, (long long)D, nt);
+        HIPCHK(hipGetLastError());
+        f.samples = samples ? samples + (size_t)t0 * C * D : nullptr;
+        f.acc_hist = acc_hist ? acc_hist + (size_t)t0 * C : nullptr;
+        f.div_hist = div_hist ? div_hist + (size_t)t0 * C : nullptr;
+        f.out.momentum = t0 + nt == T ? out->momentum : nullptr;  // only the last transition's is observable
+        if (f.tkind == AEHMC_T_CUSTOM) {  // the same instantiation (plan_hmc_wide), compiled against the user's function (round 5)
+          const HmcWidePlan pl = plan_hmc_wide(D, AEHMC_T_CUSTOM);
+          const std::string name = "aehmc::k_hmc_wide<" + std::to_string(pl.T) + ", " + std::to_string(pl.R) + ", " +
+                                   std::to_string((int)AEHMC_T_CUSTOM) + ", " + (f.fc ? "true" : "false") + ">";
+          if (int rc = rtc_launch(ctx, "hmc", {name}, name, dim3((unsigned)C), dim3(pl.T), pl.dyn, st, f, (const double *)zall, nt))
+            return rc;
+        } else if (f.tkind == AEHMC_T_JOINT) {  // k_nuts_wide's rule: 512 threads (the program's workgroup), q and dU/dq in LDS only
+          const std::string name = "aehmc::k_hmc_wide<512, " + std::to_string(joint_wide_r(D)) + ", " +
+                                   std::to_string((int)AEHMC_T_JOINT) + ", false>";
+          if (int rc = joint_rows_launch(ctx, "jwide", {name}, name, D + 1, dim3((unsigned)C), dim3(512), st, f, (const double *)zall, nt))
+            return rc;
+        } else {
+          HIPCHK(tu::hmc_resident(f, zall, nt, st));
+        }
       }
-    }
-    if (T > 1 && out->n_leapfrog)
-      LAUNCH(k_fill_i64, C, st, (long long *)out->n_leapfrog, (long long)C, (long long)(L * T));
-    return prof_end(ctx, st, p);
+      return fill_n_leapfrog(ctx, C, L, T, out, true, st);
+    });
   }
   a.eps = step_size; a.thr = divergence_threshold;
   a.rng = rng; a.nsites = 2;
   a.q = q; a.U = U; a.g = g; a.out = *out;
-  // small dense problems (shared dense metric and / or dense-precision target, D <= 64): the transition in one
-  // launch with the products inside the wavefront (k_hmc_fused_dense), as for NUTS
-  const bool tjoint = a.tkind == AEHMC_T_JOINT;
-  const bool fused_dense = ctx->opt_fused_hmc && D <= FUSED_DENSE_MAX_D && !(tjoint && a.met_ndim < 2 && joint_wg_wanted(ctx, C)) &&
-                           (tjoint || ((a.met_ndim == 2 || a.tkind == AEHMC_T_DENSE_MVN) &&
-                                       (target_is_elem_host(a.tkind) || a.tkind == AEHMC_T_DENSE_MVN)));
-  if (fused_dense) {  // all T transitions in one launch
+  if (path == HMC_PATH_FUSED_DENSE) {  // small dense problems: all T transitions in one launch (k_hmc_fused_dense), as for NUTS
+    const bool tjoint = a.tkind == AEHMC_T_JOINT;
     const bool md = a.met_ndim == 2, td = a.tkind == AEHMC_T_DENSE_MVN, pc = md && ctx->met.per_chain;
     EngineArgs b = a;
     b.linear = 0;  // literal products (metrics.py:71)
@@ -2159,8 +2127,6 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
     if (pc)
       if (int rc = fused_dense_workspace(ctx, (size_t)C * D * D * sizeof(double), &imm_ws)) return rc;
     const dim3 grid((unsigned)((C + FUSED_DENSE_BLOCK / 64 - 1) / (FUSED_DENSE_BLOCK / 64))), block(FUSED_DENSE_BLOCK);
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
 #define AEHMC_FD_LAUNCH(MDV, TDV, PCV)                                                                         \
   do {                                                                                                         \
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_fused_dense<MDV, TDV, PCV>),               \
@@ -2168,105 +2134,87 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
     hipLaunchKernelGGL((k_hmc_fused_dense<MDV, TDV, PCV>), grid, block, dyn, st, b, ctx->tgt.prec, imm_ws,      \
                        (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);                        \
   } while (0)
-    if (tjoint) {  // the same kernel, compiled against the user's density
-      const std::string name = "aehmc::k_hmc_fused_dense<" + std::string(md ? "true" : "false") + ", false, " +
-                               (pc ? "true" : "false") + ">";
-      const double *noprec = nullptr;
-      if (int rc = rtc_launch(ctx, "jhmc", {name}, name, grid, block, dyn, st, b, noprec, imm_ws, (long long)L, (long long)T,
-                              samples, acc_hist, (int *)div_hist))
-        return rc;
-    } else if (md && td && pc) AEHMC_FD_LAUNCH(true, true, true);
-    else if (md && td) AEHMC_FD_LAUNCH(true, true, false);
-    else if (md && pc) AEHMC_FD_LAUNCH(true, false, true);
-    else if (md) AEHMC_FD_LAUNCH(true, false, false);
-    else AEHMC_FD_LAUNCH(false, true, false);
+    const auto launch = [&](bool) -> int {
+      if (tjoint) {  // the same kernel, compiled against the user's density
+        const std::string name = "aehmc::k_hmc_fused_dense<" + std::string(md ? "true" : "false") + ", false, " +
+                                 (pc ? "true" : "false") + ">";
+        const double *noprec = nullptr;
+        if (int rc = rtc_launch(ctx, "jhmc", {name}, name, grid, block, dyn, st, b, noprec, imm_ws, (long long)L, (long long)T,
+                                samples, acc_hist, (int *)div_hist))
+          return rc;
+      } else if (md && td && pc) AEHMC_FD_LAUNCH(true, true, true);
+      else if (md && td) AEHMC_FD_LAUNCH(true, true, false);
+      else if (md && pc) AEHMC_FD_LAUNCH(true, false, true);
+      else if (md) AEHMC_FD_LAUNCH(true, false, false);
+      else AEHMC_FD_LAUNCH(false, true, false);
+      HIPCHK(hipGetLastError());
+      return 0;
+    };
 #undef AEHMC_FD_LAUNCH
-    HIPCHK(hipGetLastError());
-    if (int rc = prof_end(ctx, st, p)) return rc;
-    if (T > 1 && out->n_leapfrog) LAUNCH(k_fill_i64, C, st, (long long *)out->n_leapfrog, (long long)C, (long long)(L * T));
-    return 0;
+    if (int rc = profiled(ctx, st, launch)) return rc;
+    return fill_n_leapfrog(ctx, C, L, T, out, true, st);
   }
-  // row-reduction target with D <= 32, scalar / diagonal metric: all T transitions in one launch (glm_rows.cuh)
-  if (ctx->opt_fused_hmc && a.tkind == AEHMC_T_GLM && a.met_ndim < 2 && (glm_rows_wanted(D, C) || glm_wg_wanted(ctx, D, C))) {
+  if (path == HMC_PATH_GLM_ROWS) {  // row-reduction target with D <= 32, scalar / diagonal metric: all T transitions in one launch (glm_rows.cuh)
     const bool wg = glm_wg_wanted(ctx, D, C);
     const std::string name = wg ? glm_wg_name("k_hmc_glm_wg", D) : glm_rows_name("k_hmc_glm_rows", D);
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    std::string prog = "glmk";
-    if (wg)
-      if (int rc = wg_program(ctx, "glmk", {name}, name, &prog)) return rc;
-    if (int rc = rtc_launch(ctx, prog, {name}, name, wg ? dim3((unsigned)C) : chain_grid(C), dim3(wg ? 512 : 256), 0, st, a, (long long)L,
-                            (long long)T, samples, acc_hist,
-                            (int *)div_hist, (const double *)ctx->glm_XT, ctx->glm_y, (long long)ctx->glm_N))
-      return rc;
-    if (int rc = prof_end(ctx, st, p)) return rc;
-    if (out->n_leapfrog) LAUNCH(k_fill_i64, C, st, (long long *)out->n_leapfrog, (long long)C, (long long)(L * T));
-    return 0;
+    const auto launch = [&](bool) -> int {
+      std::string prog = "glmk";
+      if (wg)
+        if (int rc = wg_program(ctx, "glmk", {name}, name, &prog)) return rc;
+      return rtc_launch(ctx, prog, {name}, name, wg ? dim3((unsigned)C) : chain_grid(C), dim3(wg ? 512 : 256), 0, st, a,
+                        (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, (const double *)ctx->glm_XT,
+                        ctx->glm_y, (long long)ctx->glm_N);
+    };
+    if (int rc = profiled(ctx, st, launch)) return rc;
+    return fill_n_leapfrog(ctx, C, L, T, out, false, st);
   }
-  // traced joint density with long data sweeps, few chains: a workgroup per chain (k_hmc_joint_wg)
-  if (ctx->opt_fused_hmc && tjoint && a.met_ndim < 2 && D <= JOINT_ROWS_MAX_D && joint_wg_wanted(ctx, C)) {
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    std::string prog;
-    if (int rc = wg_program(ctx, "jwg", RTC_JWG, RTC_JWG[1], &prog)) return rc;
-    if (int rc = rtc_launch(ctx, prog, RTC_JWG, RTC_JWG[1], dim3((unsigned)C), dim3(512), (size_t)2 * D * sizeof(double), st, a,
-                            (long long)L, (long long)T, samples, acc_hist, (int *)div_hist))
-      return rc;
-    if (int rc = prof_end(ctx, st, p)) return rc;
-    if (out->n_leapfrog) LAUNCH(k_fill_i64, C, st, (long long *)out->n_leapfrog, (long long)C, (long long)(L * T));
-    return 0;
+  if (path == HMC_PATH_JOINT_WG) {  // traced joint density with long data sweeps, few chains: a workgroup per chain (k_hmc_joint_wg)
+    const auto launch = [&](bool) -> int {
+      std::string prog;
+      if (int rc = wg_program(ctx, "jwg", RTC_JWG, RTC_JWG[1], &prog)) return rc;
+      return rtc_launch(ctx, prog, RTC_JWG, RTC_JWG[1], dim3((unsigned)C), dim3(512), (size_t)2 * D * sizeof(double), st, a,
+                        (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);
+    };
+    if (int rc = profiled(ctx, st, launch)) return rc;
+    return fill_n_leapfrog(ctx, C, L, T, out, false, st);
   }
-  // joint target of more than 64 coordinates, scalar / diagonal metric: all T transitions in one launch, the lock-step
-  // loop of a chain in one wavefront (k_hmc_joint_rows)
-  if (ctx->opt_fused_hmc && tjoint && a.met_ndim < 2 && D <= JOINT_ROWS_MAX_D) {
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    if (int rc = rtc_launch(ctx, "jbase", RTC_JBASE, RTC_JBASE[3], chain_grid(C), dim3(256), (size_t)8 * D * sizeof(double), st, a,
-                            (long long)L, (long long)T, samples, acc_hist, (int *)div_hist))
-      return rc;
-    if (int rc = prof_end(ctx, st, p)) return rc;
-    if (out->n_leapfrog) LAUNCH(k_fill_i64, C, st, (long long *)out->n_leapfrog, (long long)C, (long long)(L * T));
-    return 0;
+  if (path == HMC_PATH_JOINT_ROWS) {  // all T transitions in one launch, the lock-step loop of a chain in one wavefront (k_hmc_joint_rows)
+    const auto launch = [&](bool) -> int {
+      return rtc_launch(ctx, "jbase", RTC_JBASE, RTC_JBASE[3], chain_grid(C), dim3(256), (size_t)8 * D * sizeof(double), st, a,
+                        (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);
+    };
+    if (int rc = profiled(ctx, st, launch)) return rc;
+    return fill_n_leapfrog(ctx, C, L, T, out, false, st);
   }
-  // one dense metric per chain, 64 < D <= 512, coordinate-wise target, linear dense mode: all T transitions in one
-  // launch, the wavefront that owns a chain streaming its matrix (nuts_pc_dense.cuh)
-  if (ctx->opt_fused_hmc && ctx->opt_pc_dense && a.linear &&
-      nuts_pc_dense_supported(a.tkind, a.met_ndim, ctx->met.per_chain, D)) {
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    HIPCHK(tu::hmc_pc_dense(a, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, st));
-    if (int rc = prof_end(ctx, st, p)) return rc;
-    if (out->n_leapfrog) LAUNCH(k_fill_i64, C, st, (long long *)out->n_leapfrog, (long long)C, (long long)(L * T));
-    return 0;
+  if (path == HMC_PATH_PC_DENSE) {  // all T transitions in one launch, the wavefront that owns a chain streaming its matrix (nuts_pc_dense.cuh)
+    const auto launch = [&](bool) -> int { HIPCHK(tu::hmc_pc_dense(a, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, st)); return 0; };
+    if (int rc = profiled(ctx, st, launch)) return rc;
+    return fill_n_leapfrog(ctx, C, L, T, out, false, st);
   }
-  // mid-size dense problems (shared dense metric, 64 < D <= 512, linear dense mode): all T transitions in one launch,
-  // a workgroup per 16 chains, products on MFMA inside the workgroup (nuts_block.cuh)
-  const bool custom_block = a.tkind == AEHMC_T_CUSTOM && a.met_ndim == 2 && !ctx->met.per_chain && D >= BLK_MIN_D && D <= BLK_MAX_D;
-  if (ctx->opt_fused_hmc && ctx->opt_block_dense && a.linear &&
-      (custom_block || block_dense_supported(a.tkind, a.met_ndim, ctx->met.per_chain, D))) {
+  if (path == HMC_PATH_BLOCK_DENSE) {  // all T transitions in one launch, a workgroup per 16 chains, products on MFMA (nuts_block.cuh)
     double *bp = nullptr;
     if (int rc = block_pack_workspace(ctx, D, &bp)) return rc;
-    bool p = false;
-    if (int rc = prof_begin(ctx, st, p)) return rc;
-    if (custom_block) {  // user-defined coordinate-wise target: the same kernels, compiled against the user's function (round 5)
-      BlkMats mats;
-      HIPCHK(blk_pack_matrices(a, nullptr, bp, mats, st));
-      EngineArgs b = a;
-      b.imm = mats.imm; b.sqrt_mass = mats.sqrt_mass;
-      const bool reg = ctx->opt_block_dense != 2 && block_reg_supported(D);
-      const std::string name = reg ? "aehmc::k_hmc_block_reg<" + std::string(D <= 128 ? "2" : "4") + ", false>"
-                                   : std::string("aehmc::k_hmc_block_dense<false>");
-      const size_t dyn = reg ? blk_reg_lds_bytes(D) : blk_lds_bytes(D);
-      if (int rc = rtc_launch(ctx, "block", {name}, name, dim3((unsigned)((C + BLK_CHAINS - 1) / BLK_CHAINS)), dim3(BLK_THREADS),
-                              dyn, st, b, (const double *)nullptr, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist))
-        return rc;
-    } else if (ctx->opt_block_dense != 2 && block_reg_supported(D))
-      HIPCHK(tu::hmc_block_reg(a, ctx->tgt.prec, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, bp, st));
-    else
-      HIPCHK(tu::hmc_block_dense(a, ctx->tgt.prec, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, bp, st));
-    if (int rc = prof_end(ctx, st, p)) return rc;
-    if (T > 1 && out->n_leapfrog) LAUNCH(k_fill_i64, C, st, (long long *)out->n_leapfrog, (long long)C, (long long)(L * T));
-    return 0;
+    const auto launch = [&](bool) -> int {
+      if (a.tkind == AEHMC_T_CUSTOM) {  // user-defined coordinate-wise target: the same kernels, compiled against the user's function (round 5)
+        BlkMats mats;
+        HIPCHK(blk_pack_matrices(a, nullptr, bp, mats, st));
+        EngineArgs b = a;
+        b.imm = mats.imm; b.sqrt_mass = mats.sqrt_mass;
+        const bool reg = ctx->opt_block_dense != 2 && block_reg_supported(D);
+        const std::string name = reg ? "aehmc::k_hmc_block_reg<" + std::string(D <= 128 ? "2" : "4") + ", false>"
+                                     : std::string("aehmc::k_hmc_block_dense<false>");
+        const size_t dyn = reg ? blk_reg_lds_bytes(D) : blk_lds_bytes(D);
+        return rtc_launch(ctx, "block", {name}, name, dim3((unsigned)((C + BLK_CHAINS - 1) / BLK_CHAINS)), dim3(BLK_THREADS),
+                          dyn, st, b, (const double *)nullptr, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);
+      }
+      if (ctx->opt_block_dense != 2 && block_reg_supported(D))
+        HIPCHK(tu::hmc_block_reg(a, ctx->tgt.prec, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, bp, st));
+      else
+        HIPCHK(tu::hmc_block_dense(a, ctx->tgt.prec, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, bp, st));
+      return 0;
+    };
+    if (int rc = profiled(ctx, st, launch)) return rc;
+    return fill_n_leapfrog(ctx, C, L, T, out, true, st);
   }
   const bool white = white_wanted(ctx, a);
   for (int64_t t = 0; t < T; t++) {
@@ -2292,8 +2240,7 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
       HIPCHK(hipMemcpyAsync(div_hist + (size_t)t * C, out->is_diverging, C * sizeof(int32_t),
                             hipMemcpyDeviceToDevice, st));
   }
-  if (T > 1 && out->n_leapfrog) LAUNCH(k_fill_i64, C, st, (long long *)out->n_leapfrog, (long long)C, (long long)(L * T));
-  return 0;
+  return fill_n_leapfrog(ctx, C, L, T, out, true, st);
 }
 
 extern "C" int aehmc_hmc_step(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,

@@ -645,10 +645,25 @@ inline bool hmc_resident_supported(int tkind, int met_ndim, long long D) {
   return target_is_elem_host(tkind) && met_ndim < 2 && D > 1024 && D <= (tkind == AEHMC_T_DIAG_GAUSSIAN ? 10176 : 10240);
 }
 #ifndef __HIPCC_RTC__
+// Which k_hmc_wide instantiation a D-dimensional chain takes: threads per workgroup, elements per thread, and the
+// dynamic LDS of its target -- q [D] at the transition's start, or sigma [D] and mu [D] (diagonal Gaussian); the
+// run-time compiled copy of a user-defined target keeps nothing there.  Read by launch_hmc_resident below and by the
+// engine where it names that copy.
+struct HmcWidePlan {
+  int T, R;
+  size_t dyn;
+};
+inline HmcWidePlan plan_hmc_wide(long long D, int tkind) {
+  HmcWidePlan p{};
+  p.T = D <= 2048 ? 256 : D <= 4096 ? 512 : 1024;
+  p.R = D <= 8192 ? 8 : 10;
+  p.dyn = tkind == AEHMC_T_CUSTOM ? 0 : (size_t)D * sizeof(double) * (tkind == AEHMC_T_DIAG_GAUSSIAN ? 2 : 1);
+  return p;
+}
 template <int T, int R>
-inline hipError_t launch_hmc_wide_r(const HmcFusedArgs &a, const double *zbuf, int nt, hipStream_t st) {
-  const bool dg = a.tkind == AEHMC_T_DIAG_GAUSSIAN;
-  const size_t dyn = (size_t)a.D * sizeof(double) * (dg ? 2 : 1);
+inline hipError_t launch_hmc_wide_r(const HmcFusedArgs &a, const HmcWidePlan &p, const double *zbuf, int nt, hipStream_t st) {
+  if (p.T != T || p.R != R) return hipErrorInvalidValue;
+  const size_t dyn = p.dyn;
 #define AEHMC_WIDE_LAUNCH_FC(TK, FCV)                                                                      \
   do {                                                                                                     \
     hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_wide<T, R, TK, FCV>),        \
@@ -678,10 +693,12 @@ inline hipError_t launch_hmc_wide_r(const HmcFusedArgs &a, const double *zbuf, i
 // `nt` consecutive transitions; `samples`, `acc_hist`, `div_hist` point at the FIRST of them ([nt][C][..] slices);
 // zbuf [nt][C][D] holds their momenta.
 inline hipError_t launch_hmc_resident(const HmcFusedArgs &a, const double *zbuf, int nt, hipStream_t st) {
-  if (a.D <= 2048) return launch_hmc_wide_r<256, 8>(a, zbuf, nt, st);
-  if (a.D <= 4096) return launch_hmc_wide_r<512, 8>(a, zbuf, nt, st);
-  if (a.D <= 8192) return launch_hmc_wide_r<1024, 8>(a, zbuf, nt, st);
-  return launch_hmc_wide_r<1024, 10>(a, zbuf, nt, st);
+  const HmcWidePlan p = plan_hmc_wide(a.D, a.tkind);
+  switch (p.T) {  // (the compiled instantiations; launch_hmc_wide_r refuses a plan that is not its own)
+    case 256: return launch_hmc_wide_r<256, 8>(a, p, zbuf, nt, st);
+    case 512: return launch_hmc_wide_r<512, 8>(a, p, zbuf, nt, st);
+    default: return p.R == 8 ? launch_hmc_wide_r<1024, 8>(a, p, zbuf, nt, st) : launch_hmc_wide_r<1024, 10>(a, p, zbuf, nt, st);
+  }
 }
 
 template <int R, bool FC>

@@ -635,10 +635,27 @@ inline bool nuts_wide_supported(int tkind, int met_ndim, long long D) {
          met_ndim < 2 && D > 512 && D <= 10176;
 }
 
+// Which instantiation a D-dimensional chain takes: threads per workgroup, elements per thread, whether q and (diagonal
+// target) dU/dq or (otherwise, R > 8) imm live in LDS -- two arrays of D + 1 doubles, `dyn` bytes.  Read by
+// launch_nuts_wide below and by the engine where it names the run-time compiled copy of a user-defined target.
+struct NutsWidePlan {
+  int T, R;
+  bool qgl;
+  size_t dyn;
+};
+inline NutsWidePlan plan_nuts_wide(long long D) {
+  NutsWidePlan p{};
+  p.T = D <= 2048 ? 256 : 512;
+  p.R = D <= 1024 ? 4 : D <= 4096 ? 8 : D <= 8192 ? 16 : 20;
+  p.qgl = D > 4096;
+  p.dyn = p.qgl ? (size_t)2 * (D + 1) * sizeof(double) : 0;
+  return p;
+}
+
 template <int T, int R, bool QGL>
-inline hipError_t launch_nuts_wide_tr(const EngineArgs &a, hipStream_t st) {
-  // q and (diagonal target) dU/dq or (otherwise, R > 8) imm: two arrays of D + 1 doubles
-  const size_t dyn = QGL ? (size_t)2 * (a.D + 1) * sizeof(double) : 0;
+inline hipError_t launch_nuts_wide_tr(const EngineArgs &a, const NutsWidePlan &p, hipStream_t st) {
+  if (p.T != T || p.R != R || p.qgl != QGL) return hipErrorInvalidValue;
+  const size_t dyn = p.dyn;
   const dim3 grid((unsigned)a.C), block(T);
 #define AEHMC_WIDE_LAUNCH(TKV)                                                                          \
   do {                                                                                                  \
@@ -663,12 +680,13 @@ inline long long nuts_wide_ld(long long D) { return (D + 511) / 512 * 512; }
 inline bool wide_rows_padded(long long D) { return D > 512; }
 // the momentum of site #1 must already be in a.zbuf (k_draw_momentum, rows of a.ldw, zero padded)
 inline hipError_t launch_nuts_wide(const EngineArgs &a, hipStream_t st) {
-  const long long D = a.D;
-  if (D <= 1024) return launch_nuts_wide_tr<256, 4, false>(a, st);
-  if (D <= 2048) return launch_nuts_wide_tr<256, 8, false>(a, st);
-  if (D <= 4096) return launch_nuts_wide_tr<512, 8, false>(a, st);
-  if (D <= 8192) return launch_nuts_wide_tr<512, 16, true>(a, st);
-  return launch_nuts_wide_tr<512, 20, true>(a, st);
+  const NutsWidePlan p = plan_nuts_wide(a.D);
+  switch (p.R) {  // (the compiled instantiations; launch_nuts_wide_tr refuses a plan that is not its own)
+    case 4: return launch_nuts_wide_tr<256, 4, false>(a, p, st);
+    case 8: return p.T == 256 ? launch_nuts_wide_tr<256, 8, false>(a, p, st) : launch_nuts_wide_tr<512, 8, false>(a, p, st);
+    case 16: return launch_nuts_wide_tr<512, 16, true>(a, p, st);
+    default: return launch_nuts_wide_tr<512, 20, true>(a, p, st);
+  }
 }
 #endif  // __HIPCC_RTC__
 
