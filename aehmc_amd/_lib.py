@@ -77,6 +77,7 @@ SYMBOLS = {
     "aehmc_rng_normals": (_I, [_P, _I64, _P, _I64, _P, _P]),
     "aehmc_rng_bernoulli": (_I, [_P, _I64, _P, _I64, _P, _P, _P]),
     "aehmc_gemm_nt": (_I, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
+    "aehmc_gemm_nt_tri": (_I, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _P, _P, _P]),
     "aehmc_profile_enable": (_I, [_P, _I]),
     "aehmc_profile_read": (_I, [_P, ct.POINTER(_D), ct.POINTER(_I64), ct.POINTER(_D)]),
     "aehmc_synchronize": (_I, [_P, _P]),

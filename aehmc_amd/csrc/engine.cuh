@@ -1519,6 +1519,26 @@ AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_half_dot(EngineArgs a, c
   s = wave_sum(s);
   if (lane == 0) out[c] = 0.5 * s;
 }
+// whitened mode, start of a transition: r = q - mu (k_residual's arithmetic) and the carry test.  With `have` the
+// vectors (qn, gn, Un) are the state the previous transition returned, and the workspace still holds the (z, H z) it
+// came from: a chain whose incoming (q, g, U) equals them bit for bit keeps that pair.  ctl.done = 1 marks such a
+// chain, so that k_compact lists the others -- the rows whose z and H z the two input products have to form.
+AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_white_match(EngineArgs a, int have, const double *qn, const double *gn,
+                                                     const double *Un, double *r) {
+  AEHMC_CHAIN_OF_WAVE();
+  const size_t row = (size_t)c * a.D;
+  int diff = have ? 0 : 1;
+  for (long long i = lane; i < a.D; i += 64) {
+    const double qi = a.q[row + i];
+    r[row + i] = qi - a.mu[i];
+    if (have)
+      diff |= (int)(__double_as_longlong(qi) != __double_as_longlong(qn[row + i])) |
+              (int)(__double_as_longlong(a.g[row + i]) != __double_as_longlong(gn[row + i]));
+  }
+  if (have) diff |= __double_as_longlong(a.U[c]) != __double_as_longlong(Un[c]);
+  const int any_diff = __any(diff);
+  if (lane == 0) a.ctl[c].done = any_diff ? 0 : 1;
+}
 // whitened mode, end of a transition: q = L z + mu into `q` and r = q - mu into `r` (k_residual's arithmetic), `y` = L z
 AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_white_q(EngineArgs a, const double *y, double *q, double *r) {
   AEHMC_CHAIN_OF_WAVE();
@@ -1531,15 +1551,23 @@ AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_white_q(EngineArgs a, co
 }
 // whitened mode: a chain whose returned point is its initial one (z == z0, every coordinate bit for bit: an HMC
 // rejection, a NUTS proposal never replaced) keeps the caller's (q, U, g); every other chain takes the fresh evaluation
-// (qn, Un, gn) at q = mu + L z
+// (qn, Un, gn) at q = mu + L z.  Either way (qn, gn, Un) end up holding what the caller gets back, next to the (z, H z)
+// it belongs to: the record the next transition's k_white_match tests against
 AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_white_out(EngineArgs a, const double *z, const double *z0,
-                                                   const double *qn, const double *gn, const double *Un) {
+                                                   double *qn, double *gn, double *Un) {
   AEHMC_CHAIN_OF_WAVE();
   const size_t row = (size_t)c * a.D;
   int moved = 0;
   for (long long i = lane; i < a.D; i += 64)
     moved |= __double_as_longlong(z[row + i]) != __double_as_longlong(z0[row + i]);
-  if (!__any(moved)) return;
+  if (!__any(moved)) {
+    for (long long i = lane; i < a.D; i += 64) {
+      qn[row + i] = a.q[row + i];
+      gn[row + i] = a.g[row + i];
+    }
+    if (lane == 0) Un[c] = a.U[c];
+    return;
+  }
   for (long long i = lane; i < a.D; i += 64) {
     a.q[row + i] = qn[row + i];
     a.g[row + i] = gn[row + i];
@@ -1553,6 +1581,18 @@ AEHMC_TU_LOCAL __global__ void k_tril_pair(const double *src, double *L, double 
   const double v = j <= i ? src[i * n + j] : 0.0;
   L[i * n + j] = v;
   Lt[j * n + i] = v;
+}
+// whitened mode, once per binding: *flag = 1 unless every element of `m` [n, n] below the diagonal is all-zero bits
+// (only then may the products by `m` and by its transpose take the triangular hint of gemm_f64.cuh)
+AEHMC_TU_LOCAL __global__ void k_check_upper(const double *m, long long n, int *flag) {
+  const long long i = (long long)blockIdx.y * 32 + threadIdx.y, j = (long long)blockIdx.x * 32 + threadIdx.x;
+  if (i >= n || j >= i) return;
+  if (__double_as_longlong(m[i * n + j]) != 0) *flag = 1;
+}
+// *flag = 1 unless a and b [n] hold the same bits
+AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_bits_differ(const double *a, const double *b, long long n, int *flag) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n && __double_as_longlong(a[i]) != __double_as_longlong(b[i])) *flag = 1;
 }
 // dst = (src + src^T) / 2, n x n (exactly symmetric: the two sums of a pair add the same two numbers)
 AEHMC_TU_LOCAL __global__ void k_symmetrize(const double *src, double *dst, long long n) {

@@ -123,6 +123,25 @@ struct aehmc_ctx {
   bool wh_ready = false;
   double *wh_L = nullptr, *wh_Linv = nullptr, *wh_H = nullptr;  // [D, D] row-major: L, L^-1 = sqrt_mass^T, H
   double *wh_zero = nullptr, *wh_one = nullptr;                 // mu of the whitened target [D] (zeros); the metric 1.0
+  double *wh_mu = nullptr;                                      // the target's mu as it was when the operator was formed
+  bool wh_tri = false;  // sqrt_mass is upper triangular to the bit (white_prepare): its products take the triangular hint
+  // whitened carry ("dense_whiten_carry"): after white_end the workspace vectors z, hz, qn, gn (and Un) hold,
+  // per chain, the returned (q, g, U) and the whitened pair (z, H z) it came from.  white_begin keeps the pair of every
+  // chain whose incoming state is that record, bit for bit.  Dropped (carry_drop) by whatever may write those vectors
+  // or change what they mean.
+  bool opt_dense_whiten_carry = true;
+  struct {
+    bool valid = false;
+    int64_t C = 0, D = 0;
+    const double *z = nullptr, *hz = nullptr, *qn = nullptr, *gn = nullptr;
+    // aehmc_set_target / aehmc_set_metric with a valid record: the operator it was made with is kept aside (`old_*`)
+    // instead of freed, and the record is `pending`.  When the next whitened call has formed the new binding's operator,
+    // the record counts again if L, L^-1, H and mu are the old ones bit for bit -- results follow the CONTENT of the
+    // bound arrays, not which arrays hold it (a caller who passes a fresh copy of the same matrix every call gets what
+    // one binding gives) -- and is dropped otherwise.
+    bool pending = false;
+    double *old_L = nullptr, *old_Linv = nullptr, *old_H = nullptr, *old_mu = nullptr;
+  } carry;
 };
 
 #define HIPCHK(expr)                                                                     \
@@ -140,13 +159,39 @@ struct aehmc_ctx {
   } while (0)
 
 static inline dim3 chain_grid(int64_t C) { return dim3((unsigned)((C + 3) / 4)); }
-// drops the whitened operator (hipFree waits for the launches that still read it)
-static void white_release(aehmc_ctx *ctx) {
-  for (double **p : {&ctx->wh_L, &ctx->wh_Linv, &ctx->wh_H, &ctx->wh_zero, &ctx->wh_one}) {
+static void carry_free_old(aehmc_ctx *ctx) {
+  for (double **p : {&ctx->carry.old_L, &ctx->carry.old_Linv, &ctx->carry.old_H, &ctx->carry.old_mu}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
-  ctx->wh_ready = false;
+}
+static inline void carry_drop(aehmc_ctx *ctx) {
+  ctx->carry.valid = ctx->carry.pending = false;
+  if (ctx->carry.old_L) carry_free_old(ctx);
+}
+// drops the whitened operator (hipFree waits for the launches that still read it)
+// `rebind` (aehmc_set_target, aehmc_set_metric on a dense-MVN binding): a valid carry record becomes pending, see
+// aehmc_ctx::carry
+static void white_release(aehmc_ctx *ctx, bool rebind = false) {
+  const bool set_aside = rebind && ctx->carry.valid && ctx->wh_ready && ctx->wh_mu;
+  const bool keep = set_aside || (rebind && ctx->carry.pending && !ctx->wh_ready);
+  if (set_aside) {
+    carry_free_old(ctx);
+    ctx->carry.old_L = ctx->wh_L; ctx->carry.old_Linv = ctx->wh_Linv; ctx->carry.old_H = ctx->wh_H;
+    ctx->carry.old_mu = ctx->wh_mu;
+    ctx->wh_L = ctx->wh_Linv = ctx->wh_H = ctx->wh_mu = nullptr;
+  }
+  for (double **p : {&ctx->wh_L, &ctx->wh_Linv, &ctx->wh_H, &ctx->wh_zero, &ctx->wh_one, &ctx->wh_mu}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  ctx->wh_ready = ctx->wh_tri = false;
+  if (keep) {
+    ctx->carry.valid = false;
+    ctx->carry.pending = true;
+  } else {
+    carry_drop(ctx);
+  }
 }
 constexpr int LINREG_SMAX = 32;
 // row slices per chain group: enough workgroups (~2048) to fill the GPU
@@ -249,7 +294,7 @@ extern "C" int aehmc_set_target(aehmc_ctx *ctx, const aehmc_target *t) {
     default:
       FAIL("unknown target kind");
   }
-  white_release(ctx);
+  white_release(ctx, t->kind == AEHMC_T_DENSE_MVN);
   ctx->tgt = *t;
   ctx->has_tgt = true;
   if (ctx->log_sigma) {
@@ -665,7 +710,8 @@ extern "C" int aehmc_set_custom_target(aehmc_ctx *ctx, const char *source, int64
 
 static int gemm(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, const double *A, int64_t lda,
                 const double *B, int64_t ldb, double *Cm, int64_t ldc, hipStream_t st,
-                const int *row_idx = nullptr, const int *n_rows = nullptr, int mode = 0);
+                const int *row_idx = nullptr, const int *n_rows = nullptr, int mode = 0, int tri = 0,
+                bool carry_in = false);
 
 // Blocked (64-wide) right-looking Cholesky of Lw [D,D] in place (lower triangle; the upper one keeps the input);
 // `inv`, `invT`: [NB,NB] scratch each, `info`: the first failed pivot
@@ -775,7 +821,7 @@ extern "C" int aehmc_set_metric(aehmc_ctx *ctx, const aehmc_metric *m) {
     }
     met.sqrt_mass = ctx->own_sqrt_mass;
   }
-  white_release(ctx);
+  white_release(ctx, met.ndim == 2 && !met.per_chain);
   ctx->met = met;
   ctx->has_met = true;
   return 0;
@@ -951,11 +997,18 @@ extern "C" int aehmc_set_option(aehmc_ctx *ctx, const char *name, int64_t value)
     return 0;
   }
   if (!strcmp(name, "dense_linear")) {
+    if (ctx->opt_dense_linear != (value != 0)) carry_drop(ctx);
     ctx->opt_dense_linear = value != 0;
     return 0;
   }
   if (!strcmp(name, "dense_whiten")) {
+    if (ctx->opt_dense_whiten != (value != 0)) carry_drop(ctx);
     ctx->opt_dense_whiten = value != 0;
+    return 0;
+  }
+  if (!strcmp(name, "dense_whiten_carry")) {
+    if (ctx->opt_dense_whiten_carry != (value != 0)) carry_drop(ctx);
+    ctx->opt_dense_whiten_carry = value != 0;
     return 0;
   }
   if (!strcmp(name, "gemm_small_tiles")) {
@@ -1054,6 +1107,7 @@ extern "C" int aehmc_set_workspace(aehmc_ctx *ctx, void *ws, int64_t bytes) {
   if (((uintptr_t)ws) % 256 != 0) FAIL("workspace must be 256-byte aligned");
   ctx->ws = ws;
   ctx->ws_bytes = bytes;
+  carry_drop(ctx);
   return 0;
 }
 
@@ -1067,7 +1121,10 @@ static int check_per_chain(aehmc_ctx *ctx, int64_t C) {
          std::to_string(C) + " chains");
   return 0;
 }
-static int fill_args(aehmc_ctx *ctx, int64_t C, int64_t E, EngineArgs &a, bool uses_params = true) {
+// Every caller may write the workspace's vectors, so the whitened carry record is dropped here; nuts_run and hmc_run
+// (`keep_carry`) decide for themselves once they know their route.
+static int fill_args(aehmc_ctx *ctx, int64_t C, int64_t E, EngineArgs &a, bool uses_params = true, bool keep_carry = false) {
+  if (!keep_carry) carry_drop(ctx);
   if (!ctx->has_tgt || !ctx->has_met) FAIL("set_target and set_metric must be called first");
   if (ctx->tgt.D != ctx->met.D) FAIL("target and metric dimensions differ");
   if (C <= 0) FAIL("C must be positive");
@@ -1135,6 +1192,7 @@ static int check_device_errors(aehmc_ctx *ctx) {
     // per-call state is reset because the call that saw the failure returns from the middle of it
     ctx->h_err[0] = 0;
     ctx->rows_hint = 0;
+    carry_drop(ctx);
     ctx->fuse_pre = ctx->pre_done = false;
     FAIL("stream-K GEMM: a workgroup hand-off timed out (results invalid)");
   }
@@ -1148,26 +1206,31 @@ extern "C" int aehmc_synchronize(aehmc_ctx *ctx, void *stream) {
 }
 static int gemm(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, const double *A, int64_t lda,
                 const double *B, int64_t ldb, double *Cm, int64_t ldc, hipStream_t st,
-                const int *row_idx, const int *n_rows, int mode) {
-  return profiled(ctx, st, [&](bool p) -> int {
+                const int *row_idx, const int *n_rows, int mode, int tri, bool carry_in) {
+  // tri: triangular hint for B (gemm_f64.cuh).  carry_in: one of white_begin's two input products on the rows that
+  // could not be carried -- often none, so it is kept out of the timed launch pairs (its flops are still counted), and
+  // its rows are not bounded by rows_hint, which belongs to the lock-step loop
+  auto launch = [&](bool p) -> int {
     if (int rc = check_device_errors(ctx)) return rc;
     GemmStreamK sk{ctx->sk_partial, ctx->sk_flags, ctx->d_err, ++ctx->sk_epoch};
     const bool use_sk = ctx->opt_streamk && ctx->sk_grid > 0;
     // the kernels read the exact row count on the device; the host only picks the kernel and the
     // grid, from an upper bound: live chains never increase within a transition, so the count seen
     // at the last poll bounds every later launch (few rows left: smaller tiles, no persistent grid)
-    if (n_rows && ctx->rows_hint > 0 && ctx->rows_hint < M) M = ctx->rows_hint;
+    if (!carry_in && n_rows && ctx->rows_hint > 0 && ctx->rows_hint < M) M = ctx->rows_hint;
     HIPCHK(tu::gemm_nt_f64(M, N, K, A, lda, B, ldb, Cm, ldc, st, row_idx, n_rows,
                            p ? ctx->d_flops : nullptr, (use_sk && mode == 0) ? &sk : nullptr, ctx->sk_grid,
-                           mode, ctx->opt_streamk == 2 ? ctx->sk_grid_wide : 0, ctx->opt_gemm_small));
+                           mode, ctx->opt_streamk == 2 ? ctx->sk_grid_wide : 0, ctx->opt_gemm_small, tri));
     return 0;
-  });
+  };
+  if (carry_in) return launch(ctx->prof && !ctx->prof_ev.empty());
+  return profiled(ctx, st, launch);
 }
 
 // X [C,D] times the metric matrix `mat` (imm or sqrt_mass): one GEMM over all chains when the
 // matrix is shared, per-chain mat-vecs when every chain has its own (is_mass_matrix_full)
 static int metric_mul(aehmc_ctx *ctx, int64_t C, const double *X, const double *mat, double *out,
-                      hipStream_t st, const int *row_idx = nullptr, const int *n_rows = nullptr) {
+                      hipStream_t st, const int *row_idx = nullptr, const int *n_rows = nullptr, int tri = 0) {
   const int64_t D = ctx->met.D;
   if (ctx->met.per_chain) {
     if (D <= AEHMC_PC_LDS_MAX_D)
@@ -1179,7 +1242,7 @@ static int metric_mul(aehmc_ctx *ctx, int64_t C, const double *X, const double *
     HIPCHK(hipGetLastError());
     return 0;
   }
-  return gemm(ctx, C, D, D, X, D, mat, D, out, D, st, row_idx, n_rows);
+  return gemm(ctx, C, D, D, X, D, mat, D, out, D, st, row_idx, n_rows, 0, tri);
 }
 
 extern "C" int aehmc_profile_enable(aehmc_ctx *ctx, int enable) {
@@ -1220,6 +1283,15 @@ extern "C" int aehmc_gemm_nt(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, co
   if (!ctx) return -2;
   HIPCHK(hipSetDevice(ctx->device));
   return gemm(ctx, M, N, K, A, lda, B, ldb, Cm, ldc, (hipStream_t)stream);
+}
+extern "C" int aehmc_gemm_nt_tri(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, const double *A, int64_t lda,
+                                 const double *B, int64_t ldb, double *Cm, int64_t ldc, int32_t tri,
+                                 const int32_t *row_idx, const int32_t *n_rows, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (tri < 0 || tri > 2) FAIL("gemm_nt_tri: tri is 0 (none), 1 (B lower triangular) or 2 (B upper triangular)");
+  if ((row_idx == nullptr) != (n_rows == nullptr)) FAIL("gemm_nt_tri: row_idx and n_rows go together");
+  return gemm(ctx, M, N, K, A, lda, B, ldb, Cm, ldc, (hipStream_t)stream, row_idx, n_rows, 0, tri);
 }
 
 // user-defined row-reduction target at the positions q [C,D]: Z = Q X^T (GEMM) -> dloss/dz in place + the loss sums
@@ -1291,8 +1363,9 @@ static bool white_wanted(const aehmc_ctx *ctx, const EngineArgs &a) {
 // the first call that needs it.  (Not a factorisation of the caller's metric: aehmc_metric_sqrt is that.)
 static int white_prepare(aehmc_ctx *ctx, hipStream_t st) {
   if (ctx->wh_ready) return 0;
-  white_release(ctx);
+  white_release(ctx, true);  // (a pending carry record waits for the operator formed here)
   const int64_t D = ctx->tgt.D;
+  if (ctx->carry.pending && ctx->carry.D != D) carry_drop(ctx);  // (the old operator is of another size)
   const size_t mb = (size_t)D * D * sizeof(double);
   const int NB = FACT_NB;
   double *Lw = nullptr, *Lt = nullptr, *M = nullptr, *small = nullptr;
@@ -1306,17 +1379,19 @@ static int white_prepare(aehmc_ctx *ctx, hipStream_t st) {
   };
   if (hipMalloc((void **)&ctx->wh_L, mb) != hipSuccess || hipMalloc((void **)&ctx->wh_Linv, mb) != hipSuccess ||
       hipMalloc((void **)&ctx->wh_H, mb) != hipSuccess || hipMalloc((void **)&ctx->wh_zero, D * sizeof(double)) != hipSuccess ||
+      hipMalloc((void **)&ctx->wh_mu, D * sizeof(double)) != hipSuccess ||
       hipMalloc((void **)&ctx->wh_one, sizeof(double)) != hipSuccess || hipMalloc((void **)&Lw, mb) != hipSuccess ||
       hipMalloc((void **)&Lt, mb) != hipSuccess || hipMalloc((void **)&M, mb) != hipSuccess ||
       hipMalloc((void **)&small, (size_t)2 * NB * NB * sizeof(double)) != hipSuccess ||
-      hipMalloc((void **)&info, sizeof(int)) != hipSuccess) {
+      hipMalloc((void **)&info, 3 * sizeof(int)) != hipSuccess) {  // [0] failed pivot, [1] sqrt_mass is not triangular, [2] the operator differs from the pending record's
     ctx->err = "whitened dense MVN: device allocation failed";
     return done(-1);
   }
   static const double one = 1.0;
   if (hipMemcpyAsync(Lw, ctx->met.imm, mb, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-      hipMemsetAsync(info, 0, sizeof(int), st) != hipSuccess ||
+      hipMemsetAsync(info, 0, 3 * sizeof(int), st) != hipSuccess ||
       hipMemsetAsync(ctx->wh_zero, 0, D * sizeof(double), st) != hipSuccess ||
+      hipMemcpyAsync(ctx->wh_mu, ctx->tgt.mu, D * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess ||
       hipMemcpyAsync(ctx->wh_one, &one, sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) {
     ctx->err = "whitened dense MVN: device copy failed";
     return done(-1);
@@ -1327,19 +1402,35 @@ static int white_prepare(aehmc_ctx *ctx, hipStream_t st) {
   if (!rc) {
     hipLaunchKernelGGL(k_tril_pair, grid, dim3(32, 32), 0, st, (const double *)Lw, ctx->wh_L, Lt, (long long)D);
     hipLaunchKernelGGL(k_transpose, grid, dim3(32, 8), 0, st, ctx->met.sqrt_mass, ctx->wh_Linv, (long long)D);
+    // sqrt_mass may be the caller's: its products, and those of its transpose L^-1, take the triangular hint only
+    // when its lower triangle is all-zero bits (L's upper one is: k_tril_pair writes it)
+    hipLaunchKernelGGL(k_check_upper, grid, dim3(32, 32), 0, st, ctx->met.sqrt_mass, (long long)D, info + 1);
     rc = gemm(ctx, D, D, D, Lt, D, ctx->tgt.prec, D, M, D, st);   // M = L^T P   (P symmetric: its rows are its columns)
   }
   if (!rc) rc = gemm(ctx, D, D, D, M, D, Lt, D, Lw, D, st);      // M L (the rows of L^T are the columns of L)
   if (!rc) {
     hipLaunchKernelGGL(k_symmetrize, grid, dim3(32, 32), 0, st, (const double *)Lw, ctx->wh_H, (long long)D);
-    int h_info = 0;
-    if (hipMemcpyAsync(&h_info, info, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+    if (ctx->carry.pending) {
+      const unsigned nb = (unsigned)(((size_t)D * D + 255) / 256);
+      hipLaunchKernelGGL(k_bits_differ, dim3(nb), dim3(256), 0, st, (const double *)ctx->wh_L, (const double *)ctx->carry.old_L, (long long)(D * D), info + 2);
+      hipLaunchKernelGGL(k_bits_differ, dim3(nb), dim3(256), 0, st, (const double *)ctx->wh_Linv, (const double *)ctx->carry.old_Linv, (long long)(D * D), info + 2);
+      hipLaunchKernelGGL(k_bits_differ, dim3(nb), dim3(256), 0, st, (const double *)ctx->wh_H, (const double *)ctx->carry.old_H, (long long)(D * D), info + 2);
+      hipLaunchKernelGGL(k_bits_differ, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, (const double *)ctx->wh_mu, (const double *)ctx->carry.old_mu, (long long)D, info + 2);
+    }
+    int h_info[3] = {0, 0, 0};
+    if (hipMemcpyAsync(h_info, info, 3 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
       ctx->err = "whitened dense MVN: kernels failed";
       rc = -1;
-    } else if (h_info) {
-      ctx->err = "dense inverse mass matrix is not positive definite (pivot " + std::to_string(h_info) + ")";
+    } else if (h_info[0]) {
+      ctx->err = "dense inverse mass matrix is not positive definite (pivot " + std::to_string(h_info[0]) + ")";
       rc = -2;
+    }
+    ctx->wh_tri = !rc && h_info[1] == 0;
+    if (ctx->carry.pending) {  // the record counts again only under the operator it was made with
+      const bool same = !rc && h_info[2] == 0;
+      carry_drop(ctx);
+      ctx->carry.valid = same;
     }
   }
   if (!rc) ctx->wh_ready = true;
@@ -1352,14 +1443,34 @@ struct WhiteBufs {
 };
 // z0 = L^-1 (q0 - mu), H z0 (the product the leapfrogs form), U0 the caller's (U is invariant); `b` = the whitened
 // problem's arguments: identity metric, mu = 0, precision H
+// With "dense_whiten_carry" the two products run on the chains whose incoming state is not the carry record's
+// (k_white_match, k_compact: all of them when there is no record, none in a chained run); the others keep the z and
+// H z the previous transition ended on.  Decided on the device, per chain, by content.
 static int white_begin(aehmc_ctx *ctx, const EngineArgs &a, EngineArgs &b, WhiteBufs &w, hipStream_t st) {
-  if (int rc = white_prepare(ctx, st)) return rc;
+  if (int rc = white_prepare(ctx, st)) {  // (settles a pending record: valid again, or dropped)
+    carry_drop(ctx);
+    return rc;
+  }
+  const bool had = ctx->carry.valid;
+  carry_drop(ctx);  // consumed: white_end records the next one, a call that fails midway none
   const int64_t C = a.C, D = a.D;
   w.z = a.cur_w; w.hz = a.end_w[0]; w.z0 = a.end_w[1]; w.r = a.cur_v; w.qn = a.end_v[0]; w.gn = a.end_v[1];
   w.Un = a.ckv; w.Uw = a.ckv + C;
-  LAUNCH(k_residual, C, st, a, (const double *)a.q, a.rbuf);
-  if (gemm(ctx, C, D, D, a.rbuf, D, ctx->wh_Linv, D, w.z, D, st)) return -1;
-  if (gemm(ctx, C, D, D, w.z, D, ctx->wh_H, D, w.hz, D, st)) return -1;
+  const int tri_in = ctx->wh_tri ? 1 : 0;
+  if (ctx->opt_dense_whiten_carry) {
+    const bool have = had && ctx->carry.C == C && ctx->carry.D == D && ctx->carry.z == w.z &&
+                      ctx->carry.hz == w.hz && ctx->carry.qn == w.qn && ctx->carry.gn == w.gn;
+    LAUNCH(k_white_match, C, st, a, have ? 1 : 0, (const double *)w.qn, (const double *)w.gn, (const double *)w.Un, a.rbuf);
+    hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, st, (const ChainCtl *)a.ctl, (long long)C, a.row_idx, a.n_rows,
+                       (int *)nullptr);
+    HIPCHK(hipGetLastError());
+    if (gemm(ctx, C, D, D, a.rbuf, D, ctx->wh_Linv, D, w.z, D, st, a.row_idx, a.n_rows, 0, tri_in, true)) return -1;
+    if (gemm(ctx, C, D, D, w.z, D, ctx->wh_H, D, w.hz, D, st, a.row_idx, a.n_rows, 0, 0, true)) return -1;
+  } else {
+    LAUNCH(k_residual, C, st, a, (const double *)a.q, a.rbuf);
+    if (gemm(ctx, C, D, D, a.rbuf, D, ctx->wh_Linv, D, w.z, D, st, nullptr, nullptr, 0, tri_in)) return -1;
+    if (gemm(ctx, C, D, D, w.z, D, ctx->wh_H, D, w.hz, D, st)) return -1;
+  }
   HIPCHK(hipMemcpyAsync(w.z0, w.z, (size_t)C * D * sizeof(double), hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(w.Uw, a.U, (size_t)C * sizeof(double), hipMemcpyDeviceToDevice, st));
   b = a;
@@ -1380,13 +1491,17 @@ static int white_begin(aehmc_ctx *ctx, const EngineArgs &a, EngineArgs &b, White
 static int white_end(aehmc_ctx *ctx, const EngineArgs &a, const WhiteBufs &w, hipStream_t st) {
   const int64_t C = a.C, D = a.D;
   if (a.out.momentum)
-    if (metric_mul(ctx, C, w.r, ctx->met.sqrt_mass, a.out.momentum, st)) return -1;
-  if (gemm(ctx, C, D, D, w.z, D, ctx->wh_L, D, w.qn, D, st)) return -1;
+    if (metric_mul(ctx, C, w.r, ctx->met.sqrt_mass, a.out.momentum, st, nullptr, nullptr, ctx->wh_tri ? 2 : 0)) return -1;
+  if (gemm(ctx, C, D, D, w.z, D, ctx->wh_L, D, w.qn, D, st, nullptr, nullptr, 0, 1)) return -1;
   LAUNCH(k_white_q, C, st, a, (const double *)w.qn, w.qn, a.rbuf);
   if (gemm(ctx, C, D, D, a.rbuf, D, ctx->tgt.prec, D, w.gn, D, st)) return -1;
   LAUNCH(k_half_dot, C, st, a, (const double *)a.rbuf, (const double *)w.gn, w.Un);
-  LAUNCH(k_white_out, C, st, a, (const double *)w.z, (const double *)w.z0, (const double *)w.qn,
-         (const double *)w.gn, (const double *)w.Un);
+  LAUNCH(k_white_out, C, st, a, (const double *)w.z, (const double *)w.z0, w.qn, w.gn, w.Un);
+  if (ctx->opt_dense_whiten_carry) {
+    ctx->carry.valid = true;
+    ctx->carry.C = C; ctx->carry.D = D;
+    ctx->carry.z = w.z; ctx->carry.hz = w.hz; ctx->carry.qn = w.qn; ctx->carry.gn = w.gn;
+  }
   return 0;
 }
 
@@ -1644,7 +1759,7 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
   if (max_num_expansions < 1 || max_num_expansions > 20) FAIL("max_num_expansions must be in [1, 20]");
   if (!out->acceptance_probability || !out->is_diverging) FAIL("diagnostics arrays missing");
   EngineArgs a;
-  if (int rc = fill_args(ctx, C, max_num_expansions, a)) return rc;
+  if (int rc = fill_args(ctx, C, max_num_expansions, a, true, true)) return rc;
   a.eps = step_size; a.thr = divergence_threshold;
   a.rng = rng; a.nsites = 4;
   a.q = q; a.U = U; a.g = g; a.out = *out;
@@ -1652,6 +1767,8 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
   // workgroup-cooperative regression kernel) are taken wherever they exist; the lock-step engine below serves
   // dense metrics, dense targets, and `resident_nuts` = 0.
   const int path = nuts_path(ctx, C, max_num_expansions);
+  const bool white = path == NUTS_PATH_LOCKSTEP && white_wanted(ctx, a);
+  if (!white) carry_drop(ctx);  // (every other route may write the workspace vectors the record lives in)
   if (path == NUTS_PATH_LINREG) {
     const NutsSampleArgs m = take_multi(multi, multi_done, [&] {
       return !(multi->adapt && a.met_ndim == 2 && !(multi->ad.full && ctx->met.per_chain));
@@ -1781,7 +1898,6 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
     return profiled(ctx, st, [&](bool) -> int { LAUNCH(k_nuts_fused, C, st, a); return 0; });
   }
   ctx->rows_hint = 0;
-  const bool white = white_wanted(ctx, a);
   EngineArgs wa;  // whitened mode: the transition runs on the whitened problem (white_begin), mapped back at the end
   WhiteBufs wb{};
   if (white)
@@ -2064,7 +2180,9 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
     });
   }
   EngineArgs a;
-  if (int rc = fill_args(ctx, C, 1, a)) return rc;
+  if (int rc = fill_args(ctx, C, 1, a, true, true)) return rc;
+  const bool white = path == HMC_PATH_LOCKSTEP && white_wanted(ctx, a);
+  if (!white) carry_drop(ctx);  // (every other route may write the workspace vectors the record lives in)
   if (path == HMC_PATH_WIDE) {  // a workgroup per chain (k_hmc_wide), coordinate-wise target or traced joint density
     HmcFusedArgs f = hmc_fused_args(ctx, C, rng, step_size, L, divergence_threshold, q, U, g, out);
     f.tkind = ctx->tgt.kind; f.mu = ctx->tgt.mu; f.sigma = ctx->tgt.sigma; f.log_sigma = ctx->log_sigma;
@@ -2216,7 +2334,6 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
     if (int rc = profiled(ctx, st, launch)) return rc;
     return fill_n_leapfrog(ctx, C, L, T, out, true, st);
   }
-  const bool white = white_wanted(ctx, a);
   for (int64_t t = 0; t < T; t++) {
     EngineArgs wa;  // whitened mode: each transition mapped in and out on its own (white_begin / white_end)
     WhiteBufs wb{};

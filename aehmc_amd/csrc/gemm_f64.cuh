@@ -240,7 +240,15 @@ __device__ __forceinline__ void gemm_tile_coords(int t, int Tm, int Tn, int &tm,
 // operand bytes and LDS fragment reads per MFMA.
 // PIPE: the software-pipelined K loop at one workgroup per CU (NJ = 8 always; NJ = 4 for launches
 // with too few wide tiles to fill the CUs)
-template <bool VEC, int NJ, bool PIPE = (NJ == 8)>
+// TRI: triangular-operand hint, its own instantiations (TRI = 0 is the code it was before the hint existed).
+//   1: B[n,k] == 0 for k > n (lower triangular),  2: B[n,k] == 0 for k < n (upper triangular).
+// Column tile tn then runs only the K-tiles [k_lo(tn), k_hi(tn)) that are not wholly inside the zero triangle.  A
+// skipped K-tile would have added a * (+-0) to accumulators that start at +0, which leaves every bit of them alone as
+// long as `a` is finite: for finite A the output is BITWISE the untriangular one (a NaN or an infinity in A would have
+// spread over its whole output row and now reaches only part of it).  Every element still sums its K-tiles in
+// ascending order.  Tiles have unequal weight, so the schedule is the (tile, k) range scheme over ALL tiles, cut by
+// the cumulative K-tile counts; the flop counter adds what is executed, 2 M x (columns x K of the K-tiles run).
+template <bool VEC, int NJ, bool PIPE = (NJ == 8), int TRI = 0>
 __global__ __launch_bounds__(256, (PIPE ? 1 : 2)) void gemm_nt_f64_streamk_kernel(
     int64_t M, int64_t N, int64_t K, const double *__restrict__ A, int64_t lda,
     const double *__restrict__ B, int64_t ldb, double *__restrict__ Cm, int64_t ldc,
@@ -251,7 +259,7 @@ __global__ __launch_bounds__(256, (PIPE ? 1 : 2)) void gemm_nt_f64_streamk_kerne
   __shared__ __attribute__((aligned(16))) double ldsB[2][BN][GEMM_LDS];
   __shared__ int s_rows[GEMM_BM];
   if (n_rows) M = *n_rows;
-  if (flop_counter && blockIdx.x == 0 && threadIdx.x == 0)
+  if (TRI == 0 && flop_counter && blockIdx.x == 0 && threadIdx.x == 0)
     atomicAdd(flop_counter, (unsigned long long)(2 * M * N * K));
   const int G = gridDim.x;                                     // multiple of 8
   const int bb = (blockIdx.x % 8) * (G / 8) + blockIdx.x / 8;  // an XCD owns a contiguous tile range
@@ -496,6 +504,91 @@ __global__ __launch_bounds__(256, (PIPE ? 1 : 2)) void gemm_nt_f64_streamk_kerne
     }
   };
 
+  if constexpr (TRI != 0) {
+    constexpr int PW = (NJ == 8 ? AEHMC_GEMM_PW_WIDE : GEMM_PANEL_W);
+    // K-tiles of column tile tn outside B's zero triangle (never none: a tile without work would keep stale output)
+    auto k_lo = [&](int tn) -> int {
+      if (TRI != 2) return 0;
+      const long long lo = (long long)tn * BN / GEMM_BK;
+      return lo < nk ? (int)lo : nk - 1;
+    };
+    auto k_hi = [&](int tn) -> int {
+      if (TRI != 1) return nk;
+      const long long hi = ((long long)(tn + 1) * BN + GEMM_BK - 1) / GEMM_BK;
+      return hi < nk ? (int)hi : nk;
+    };
+    auto col_of = [&](int t) -> int {
+      int tm, tn;
+      gemm_tile_coords<PW>(t, Tm, Tn, tm, tn);
+      return tn;
+    };
+    long long wsum = 0, fl = 0;
+    for (int tn = 0; tn < Tn; tn++) {
+      const int w = k_hi(tn) - k_lo(tn);
+      const long long n0 = (long long)tn * BN, cols = (N - n0 < BN) ? N - n0 : BN;
+      long long kend = (long long)k_hi(tn) * GEMM_BK;
+      if (kend > K) kend = K;
+      wsum += w;
+      fl += cols * (kend - (long long)k_lo(tn) * GEMM_BK);
+    }
+    if (flop_counter && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(flop_counter, (unsigned long long)(2 * M * fl));
+    const long long total = wsum * Tm;
+    const long long W = (total + G - 1) / G;
+    if (W < nk) {  // few rows: a range could lie inside one tile; whole tiles, each over its own K range
+      for (long long base = 0; base < T; base += G) {
+        const long long left = (T - base < G) ? T - base : G;
+        const long long chunk = (left + 7) / 8, slot = blockIdx.x / 8, x = blockIdx.x % 8;
+        if (slot < chunk && x * chunk + slot < left) {
+          const int t = (int)(base + x * chunk + slot), tn = col_of(t);
+          pass(t, k_lo(tn), k_hi(tn), 0);
+        }
+      }
+      return;
+    }
+    // (tile, k) position of work item `it` in tile order: panel by panel, the tiles of a row block of a panel together
+    auto locate = [&](long long it, int &t, int &off) {
+      int tn0 = 0;
+      long long tbase = 0;
+      for (;;) {
+        const int pw = (Tn - tn0 < PW) ? Tn - tn0 : PW;
+        long long ps = 0;
+        for (int j = 0; j < pw; j++) ps += k_hi(tn0 + j) - k_lo(tn0 + j);
+        if (it < ps * Tm || tn0 + pw >= Tn) {
+          const long long tm = it / ps;
+          long long rem = it - tm * ps;
+          int j = 0;
+          while (j + 1 < pw && rem >= k_hi(tn0 + j) - k_lo(tn0 + j)) {
+            rem -= k_hi(tn0 + j) - k_lo(tn0 + j);
+            j++;
+          }
+          t = (int)(tbase + tm * pw + j);
+          off = (int)rem;
+          return;
+        }
+        it -= ps * Tm;
+        tbase += (long long)Tm * pw;
+        tn0 += pw;
+      }
+    };
+    // W >= nk >= every tile's weight: a range that does not start on a tile boundary ends in a later tile, so a
+    // workgroup has at most one tail (its first tile) and one head (its last), as in the hybrid schedule below
+    const long long it0 = (long long)bb * W, it1 = (it0 + W < total) ? it0 + W : total;
+    if (it0 >= it1) return;
+    int tf, ks, tl, ke;
+    locate(it0, tf, ks);
+    locate(it1 - 1, tl, ke);
+    ke += 1;
+    const int cf = col_of(tf), cl = col_of(tl);
+    const bool has_tail = ks > 0;
+    const bool has_head = ke < k_hi(cl) - k_lo(cl);
+    if (has_head) pass(tl, k_lo(cl), k_lo(cl) + ke, 1);
+    for (int t = has_tail ? tf + 1 : tf; t <= (has_head ? tl - 1 : tl); t++) {
+      const int tn = col_of(t);
+      pass(t, k_lo(tn), k_hi(tn), 0);
+    }
+    if (has_tail) pass(tf, k_lo(cf) + ks, k_hi(cf), 2);
+    return;
+  }
   const long long total = T * nk;
   const long long W = (total + G - 1) / G;
   // Whole tiles, strided over the grid (the one-tile-per-workgroup order, which keeps the
@@ -769,7 +862,9 @@ inline hipError_t launch_gemm_nt_f64(int64_t M, int64_t N, int64_t K, const doub
                                      const int *row_idx = nullptr, const int *n_rows = nullptr,
                                      unsigned long long *flop_counter = nullptr,
                                      const GemmStreamK *sk = nullptr, int sk_grid = 0, int mode = 0,
-                                     int sk_grid_wide = 0, int small_tiles = 1) {
+                                     int sk_grid_wide = 0, int small_tiles = 1, int tri = 0) {
+  // tri: triangular-operand hint (see gemm_nt_f64_streamk_kernel's TRI).  Only the 128 x 256 stream-K kernel honours
+  // it; every other kernel computes the full product, which for finite A is the same bits.
   if (M <= 0 || N <= 0) return hipSuccess;
   const int Tm = (int)((M + GEMM_BM - 1) / GEMM_BM), Tn = (int)((N + GEMM_BN - 1) / GEMM_BN);
   const int total = Tm * Tn;
@@ -822,6 +917,13 @@ inline hipError_t launch_gemm_nt_f64(int64_t M, int64_t N, int64_t K, const doub
     return hipGetLastError();
   }
   if (vec && sk && sk_grid_wide > 0 && K % GEMM_BK == 0 && Tm * (int)((N + 255) / 256) >= sk_grid_wide) {  // 128 x 256 tiles
+    if (tri == 1)
+      hipLaunchKernelGGL((gemm_nt_f64_streamk_kernel<true, 8, true, 1>), dim3(sk_grid_wide), dim3(256), 0, stream, M, N, K,
+                         A, lda, B, ldb, Cm, ldc, row_idx, n_rows, flop_counter, *sk);
+    else if (tri == 2)
+      hipLaunchKernelGGL((gemm_nt_f64_streamk_kernel<true, 8, true, 2>), dim3(sk_grid_wide), dim3(256), 0, stream, M, N, K,
+                         A, lda, B, ldb, Cm, ldc, row_idx, n_rows, flop_counter, *sk);
+    else
     hipLaunchKernelGGL((gemm_nt_f64_streamk_kernel<true, 8>), dim3(sk_grid_wide), dim3(256), 0, stream, M, N, K,
                        A, lda, B, ldb, Cm, ldc, row_idx, n_rows, flop_counter, *sk);
     return hipGetLastError();

@@ -351,9 +351,13 @@ class Engine:
             raise EngineError("aehmc_workspace_bytes: target/metric not set")
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
+            self._ws_bound = None
             self._ws = torch.empty(int(need), dtype=torch.uint8, device=self.device)
-        self._check(self.lib.aehmc_set_workspace(self.ctx, self._ws.data_ptr(), self._ws.numel()),
-                    "aehmc_set_workspace")
+        # bound once per buffer: aehmc_set_workspace tells the engine that whatever it kept in the workspace is gone
+        if getattr(self, "_ws_bound", None) != (self._ws.data_ptr(), self._ws.numel()):
+            self._check(self.lib.aehmc_set_workspace(self.ctx, self._ws.data_ptr(), self._ws.numel()),
+                        "aehmc_set_workspace")
+            self._ws_bound = (self._ws.data_ptr(), self._ws.numel())
 
     def rtc_stats(self):
         """(programs compiled by hipRTC, programs loaded from the on-disk cache) of this engine's ctx."""
@@ -548,6 +552,20 @@ class Engine:
         self._check(self.lib.aehmc_gemm_nt(self.ctx, M, N, K, A.data_ptr(), A.stride(0), B.data_ptr(),
                                            B.stride(0), out.data_ptr(), out.stride(0), self.stream),
                     "aehmc_gemm_nt")
+        return out
+
+    def gemm_nt_tri(self, A, B, tri, row_idx=None, n_rows=None, out=None):
+        """A B^T with the triangular hint `tri` on B (0 none, 1 lower, 2 upper; aehmc_gemm_nt_tri); `row_idx` [M] int32
+        and `n_rows` [1] int32 (device tensors, both or neither) select the rows that are computed and written."""
+        M, K = A.shape
+        N = B.shape[0]
+        if out is None:
+            out = torch.empty(M, N, dtype=torch.float64, device=self.device)
+        self._check(self.lib.aehmc_gemm_nt_tri(self.ctx, M, N, K, A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0),
+                                               out.data_ptr(), out.stride(0), int(tri),
+                                               row_idx.data_ptr() if row_idx is not None else None,
+                                               n_rows.data_ptr() if n_rows is not None else None, self.stream),
+                    "aehmc_gemm_nt_tri")
         return out
 
     # ------------------------------------------------------------------ warm-up

@@ -222,6 +222,16 @@ int aehmc_set_metric(aehmc_ctx *ctx, const aehmc_metric *metric);
  *                   from the BOUND arrays (prec, imm, sqrt_mass) once per binding and dropped by aehmc_set_target /
  *                   aehmc_set_metric: a caller who edits them in place must bind them again.  0 = two products per
  *                   leapfrog in the original coordinates
+ *  "dense_whiten_carry" 1  whitened mode: the engine keeps, in the workspace, the state a transition returned next to
+ *                   the whitened pair (z, H z) it came from.  A chain that enters the next whitened call with exactly
+ *                   that q, U and dU/dq (compared bit for bit on the device, per chain) continues from the pair
+ *                   instead of forming z = L^-1 (q - mu) and H z again; every other chain is mapped in as before.
+ *                   After aehmc_set_target / aehmc_set_metric the record survives only if the operator formed
+ *                   from the new arrays (L, L^-1, H, mu) is the old one bit for bit: results follow the content of the
+ *                   bound arrays, not which arrays hold it (the old operator is held until the next whitened call
+ *                   has compared it).  The record is dropped by anything that replaces the workspace or may write it (any other call that uses the workspace, another chain count or tree
+ *                   depth).  Same discrete outputs, reals equal up to rounding (z is not rounded through q).
+ *                   0 = every transition maps in from q
  *  "gemm_small_tiles" 1  fp64 GEMM of a mid-size problem (fewer than 256 tiles of 128 x 128, N <= 2048):
  *                   1 = 64 x 128, 64 x 64 or 32 x 64 tiles, the largest that gives every CU two
  *                   workgroups (bitwise the results of the 128 x 128 kernel); 2 / 3 / 4 force
@@ -411,6 +421,16 @@ int aehmc_rng_bernoulli(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_t n, con
 /* fp64 MFMA GEMM used by the dense-metric path: Cmat[M,N] = A[M,K] * B[N,K]^T (row-major) */
 int aehmc_gemm_nt(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, const double *A, int64_t lda,
                   const double *B, int64_t ldb, double *Cmat, int64_t ldc, void *stream);
+/* The same product with a hint on B: tri = 0 none, 1 = B[n,k] == 0 for k > n (lower triangular), 2 = B[n,k] == 0 for
+ * k < n (upper triangular).  A hint, not a mode: the 128 x 256 stream-K kernel (>= 256 tiles, K % 16 == 0) skips the
+ * K-tiles that lie wholly in the zero triangle, every other kernel computes the full product.  For FINITE A the result
+ * is bitwise that of aehmc_gemm_nt (skipped terms are a * 0 added to accumulators that start at +0); a NaN or infinity
+ * in A reaches only the elements whose K range holds it.  B's other triangle must be exact zeros.  row_idx / n_rows
+ * (both or neither; device pointers): compacted rows -- tile row r reads A row row_idx[r] and writes C row row_idx[r],
+ * *n_rows <= M rows exist.  The profiled flop count adds the K-tiles a launch executes. */
+int aehmc_gemm_nt_tri(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, const double *A, int64_t lda,
+                      const double *B, int64_t ldb, double *Cmat, int64_t ldc, int32_t tri, const int32_t *row_idx,
+                      const int32_t *n_rows, void *stream);
 
 /* timing hooks for bench.py: HIP events (on the launch stream) around every launch of the
  * dominant kernel (fp64 GEMM, or the fused HMC kernel) since profile_enable(1), and the
