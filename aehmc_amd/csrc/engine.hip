@@ -978,6 +978,52 @@ extern "C" int aehmc_covariance_final(aehmc_ctx *ctx, int64_t C, int64_t D, int3
   return 0;
 }
 
+// Posterior summaries (summary.cuh): caller-owned buffers only -- no workspace, no EngineArgs, nothing the whitened
+// carry record depends on.
+static int summary_shape(aehmc_ctx *ctx, const char *what, int64_t N, int64_t C, int64_t D, int32_t S) {
+  if (N <= 0 || C <= 0 || D <= 0 || (S != 1 && S != 2)) FAIL(std::string(what) + ": bad arguments");
+  if (N / S < 2) FAIL(std::string(what) + ": a segment needs at least two draws");
+  if (C * D > (int64_t)1 << 38) FAIL(std::string(what) + ": C * D is too large");
+  return 0;
+}
+extern "C" int aehmc_summary_update(aehmc_ctx *ctx, int64_t T, int64_t C, int64_t D, int64_t t0, int64_t num_draws,
+                                    int32_t n_segments, const double *samples, double *mean, double *m2, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = summary_shape(ctx, "summary_update", num_draws, C, D, n_segments)) return rc;
+  if (T <= 0 || t0 < 0 || t0 + T > num_draws || !samples || !mean || !m2) FAIL("summary_update: bad arguments");
+  HIPCHK(tu::summary_update(samples, T, C * D, t0, num_draws, n_segments, mean, m2, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int aehmc_summary_autocov(aehmc_ctx *ctx, int64_t num_draws, int64_t C, int64_t D, int32_t n_segments,
+                                     int64_t K, int64_t G, const double *samples, const double *mean, double *work,
+                                     double *acov, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = summary_shape(ctx, "summary_autocov", num_draws, C, D, n_segments)) return rc;
+  const int64_t n = num_draws / n_segments;
+  if (!samples || !mean || !work || !acov || G < 1 || G > n_segments * C || G > 65535)
+    FAIL("summary_autocov: bad arguments");
+  if (K < 2 || K > n) FAIL("summary_autocov: the number of lags K must be in [2, segment length]");
+  if (n + K > AEHMC_SUMMARY_MAX_ROWS)
+    FAIL("summary_autocov: segment length + lags is " + std::to_string(n + K) + ", supported up to " +
+         std::to_string(AEHMC_SUMMARY_MAX_ROWS) + " (use fewer lags)");
+  HIPCHK(tu::summary_acov(samples, mean, work, acov, num_draws, C, D, n_segments, K, (int)G, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int aehmc_summary_final(aehmc_ctx *ctx, int64_t num_draws, int64_t C, int64_t D, int32_t n_segments,
+                                   int64_t K, const double *mean, const double *m2, const double *acov, double *out,
+                                   int32_t *lag_truncated, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = summary_shape(ctx, "summary_final", num_draws, C, D, n_segments)) return rc;
+  if (!mean || !m2 || !out) FAIL("summary_final: bad arguments");
+  if (acov && (!lag_truncated || K < 2)) FAIL("summary_final: acov needs lag_truncated and K >= 2");
+  HIPCHK(tu::summary_final(mean, m2, acov, out, lag_truncated, num_draws / n_segments, (int64_t)n_segments * C, D, K,
+                           (hipStream_t)stream));
+  return 0;
+}
+
 extern "C" int aehmc_set_option(aehmc_ctx *ctx, const char *name, int64_t value) {
   if (!ctx || !name) return -2;
   if (!strcmp(name, "fused_hmc")) {

@@ -41,5 +41,12 @@ hipError_t hmc_pc_dense(const EngineArgs &a, long long L, long long nt, double *
 // hmc_fused.cuh
 hipError_t hmc_fused(const HmcFusedArgs &a, hipStream_t st);
 hipError_t hmc_resident(const HmcFusedArgs &a, const double *zbuf, int nt, hipStream_t st);
+// summary.cuh
+hipError_t summary_update(const double *x, long long T, long long E, long long t0, long long N, int S, double *mean,
+                          double *m2, hipStream_t st);
+hipError_t summary_acov(const double *x, const double *mean, double *partial, double *acov, long long N, long long C,
+                        long long D, int S, long long K, int G, hipStream_t st);
+hipError_t summary_final(const double *mean, const double *m2, const double *acov, double *out, int *lag_truncated,
+                         long long n, long long m, long long D, long long K, hipStream_t st);
 }  // namespace tu
 }  // namespace aehmc

@@ -432,12 +432,24 @@ class Engine:
                         int(L), float(thr), q.data_ptr(), U.data_ptr(), g.data_ptr(), ct.byref(c), self.stream)
         return out
 
-    def hmc_sample(self, rng, eps, L, thr, n, q, U, g, keep_samples=True):
+    def _samples_buffer(self, n, C, D, keep_samples, into):
+        """The [n, C, D] array a sample() call writes its draws to: fresh, or the head of the caller's buffer ``into``
+        (summary.run folds chunk after chunk from one buffer)."""
+        if not keep_samples:
+            return None
+        if into is None:
+            return torch.empty(n, C, D, dtype=torch.float64, device=self.device)
+        if into.dtype != torch.float64 or into.device != self.device or not into.is_contiguous() or into.numel() < n * C * D:
+            raise ValueError(f"samples buffer must be a contiguous float64 tensor on {self.device} with at least "
+                             f"{n * C * D} elements")
+        return into.reshape(-1)[:n * C * D].reshape(n, C, D)
+
+    def hmc_sample(self, rng, eps, L, thr, n, q, U, g, keep_samples=True, into=None):
         C, D = q.shape
         self.ensure_workspace(C, 1)
         out, c = self._diag(C, D, False)
         dev = self.device
-        samples = torch.empty(n, C, D, dtype=torch.float64, device=dev) if keep_samples else None
+        samples = self._samples_buffer(n, C, D, keep_samples, into)
         acc = torch.empty(n, C, dtype=torch.float64, device=dev)
         div = torch.empty(n, C, dtype=torch.int32, device=dev)
         self._step_call(
@@ -457,12 +469,12 @@ class Engine:
                         self.stream)
         return out
 
-    def nuts_sample(self, rng, eps, max_exp, thr, n, q, U, g, keep_samples=True):
+    def nuts_sample(self, rng, eps, max_exp, thr, n, q, U, g, keep_samples=True, into=None):
         C, D = q.shape
         self.ensure_workspace(C, max_exp)
         out, c = self._diag(C, D, True)
         dev = self.device
-        samples = torch.empty(n, C, D, dtype=torch.float64, device=dev) if keep_samples else None
+        samples = self._samples_buffer(n, C, D, keep_samples, into)
         acc = torch.empty(n, C, dtype=torch.float64, device=dev)
         div = torch.empty(n, C, dtype=torch.int32, device=dev)
         total = torch.zeros(C, dtype=torch.int64, device=dev)
@@ -612,6 +624,40 @@ class Engine:
                                                     m2.data_ptr(), n.data_ptr(), out.data_ptr(), self.stream),
                     "aehmc_covariance_final")
         return out
+
+    # ------------------------------------------------------------------ posterior summaries
+    def summary_update(self, chunk, t0, num_draws, n_segments, mean, m2):
+        """Fold draws t0 ... t0 + T - 1 (chunk [T, C, D]) into the running moments mean, m2 [n_segments, C, D]."""
+        T, C, D = chunk.shape
+        self._check(self.lib.aehmc_summary_update(self.ctx, T, C, D, int(t0), int(num_draws), int(n_segments),
+                                                  chunk.data_ptr(), mean.data_ptr(), m2.data_ptr(), self.stream),
+                    "aehmc_summary_update")
+
+    def summary_autocov(self, samples, n_segments, K, mean):
+        """Chain-averaged autocovariance [K, D] of the stored draws [N, C, D] about the split chains' means."""
+        N, C, D = samples.shape
+        m = n_segments * C
+        # groups of split chains: about 1024 workgroups in all, partial sums within 256 MB
+        blocks = -(-D // 8)
+        G = max(1, min(m, -(-1024 // blocks), (256 << 20) // (8 * K * D), 65535))
+        work = torch.empty(G, K, D, dtype=torch.float64, device=self.device)
+        acov = torch.empty(K, D, dtype=torch.float64, device=self.device)
+        self._check(self.lib.aehmc_summary_autocov(self.ctx, N, C, D, int(n_segments), int(K), G, samples.data_ptr(),
+                                                   mean.data_ptr(), work.data_ptr(), acov.data_ptr(), self.stream),
+                    "aehmc_summary_autocov")
+        return acov
+
+    def summary_final(self, num_draws, n_segments, mean, m2, acov=None):
+        """out [7, D] (mean, sd, rhat, ess, mcse, ess_chains, mcse_chains) and lag_truncated [D] (None without acov)."""
+        _, C, D = mean.shape
+        out = torch.empty(7, D, dtype=torch.float64, device=self.device)
+        trunc = torch.empty(D, dtype=torch.int32, device=self.device) if acov is not None else None
+        self._check(self.lib.aehmc_summary_final(self.ctx, int(num_draws), C, D, int(n_segments),
+                                                 acov.shape[0] if acov is not None else 0, mean.data_ptr(), m2.data_ptr(),
+                                                 acov.data_ptr() if acov is not None else None, out.data_ptr(),
+                                                 trunc.data_ptr() if trunc is not None else None, self.stream),
+                    "aehmc_summary_final")
+        return out, trunc
 
     def profile_enable(self, on=True):
         self._check(self.lib.aehmc_profile_enable(self.ctx, int(on)), "aehmc_profile_enable")

@@ -42,11 +42,12 @@ def new_kernel(srng: RandomStream, logprob_fn, max_num_expansions: int = 10,
         return info, {srng: holder["rng"]}
 
     def sample(state: IntegratorState, step_size, inverse_mass_matrix, num_samples: int,
-               keep_samples: bool = True):
+               keep_samples: bool = True, into=None):
         """``num_samples`` consecutive transitions per chain in one engine call (the
         reference's user-level ``aesara.scan(kernel, n_steps=N)``, tests/test_hmc.py:296-324).
         Returns ``(samples [N, ...], Diagnostics of the last transition with the leapfrog
-        TOTAL in n_leapfrog, acceptance history, divergence history)``."""
+        TOTAL in n_leapfrog, acceptance history, divergence history)``.  ``into``: a device buffer the
+        draws are written to instead of a fresh one (``samples`` is then a view of it)."""
         eng = get_engine()
         layout = Layout(tuple(state.position.shape), srng.batched, srng.num_chains)
         if "rng" not in holder or holder["rng"].device != eng.device:  # (uploaded at construction when a GPU is there)
@@ -55,7 +56,7 @@ def new_kernel(srng: RandomStream, logprob_fn, max_num_expansions: int = 10,
         eng.set_target(logprob_fn, layout.D, scalar=layout.scalar)
         eng.set_metric(inverse_mass_matrix, layout.D)
         out = eng.nuts_sample(holder["rng"], eng.set_step_sizes(step_size), int(max_num_expansions),
-                              float(divergence_threshold), int(num_samples), q, U, g, keep_samples)
+                              float(divergence_threshold), int(num_samples), q, U, g, keep_samples, into)
         info = diagnostics(layout, q, U, g, out, True)
         samples, acc_hist, div_hist = histories(layout, out, int(num_samples), keep_samples)
         return samples, info, acc_hist, div_hist

@@ -1,0 +1,207 @@
+"""Posterior summaries on the device: per-coordinate mean, sd, split R-hat, effective sample size and Monte-Carlo
+standard error of what ``kernel.sample`` draws (``aehmc_summary_update`` / ``_autocov`` / ``_final``, csrc/summary.cuh).
+
+The reference leaves this to arviz on the host (tests/test_hmc.py:158-167: ``arviz.ess``, then ``std / sqrt(ess)``).
+Here the draws stay where they are, and a run whose draws cannot be stored at all (4096 chains x 10^4 coordinates are
+328 MB per draw) is summarised while it is sampled: ``run``.
+
+Two families of estimators per coordinate, with n draws per (split) chain and m (split) chains:
+
+- across chains -- ``rhat``, ``ess_chains``, ``mcse_chains``: W is the mean of the chains' variances, B/n the variance
+  of the chains' means, var+ = W (n - 1) / n + B/n; rhat = sqrt(var+ / W), mcse_chains = sqrt((B/n) / m) (the spread of
+  independent chain means: exact whatever the autocorrelation, and sharp with many chains), ess_chains = var+ /
+  mcse_chains^2.  They need running moments only, so they stream.
+- along chains -- ``ess``, ``mcse``, ``lag_truncated``: Stan's estimator from the chain-averaged autocovariance with
+  Geyer's initial positive, initial monotone sequence.  It needs every draw, so only ``summarize`` gives it.
+
+fp64, deterministic: two calls on the same draws, and any chunking of them, give the same bits.  No CPU fallback."""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional
+
+import torch
+
+from .engine import get_engine
+
+# aehmc_hip.h: AEHMC_SUMMARY_MAX_ROWS -- the autocovariance kernel keeps a coordinate's centred series (one segment)
+# and as many zeros as there are lags in LDS
+MAX_ACOV_ROWS = 8192
+# summary.run(chunk=None): the draw buffer of a chunk stays under this many bytes (at least one draw)
+CHUNK_BYTES = 1 << 30
+
+
+class Summary(NamedTuple):
+    """Per-coordinate device tensors shaped like one chain's position, plus the run's size.  ``ess``, ``mcse`` and
+    ``lag_truncated`` (bool: the autocorrelation pairs were still positive at the last lag, so ``ess`` is an
+    over-estimate -- raise ``max_lag`` or run longer) are None in streaming mode."""
+    mean: torch.Tensor
+    sd: torch.Tensor
+    rhat: torch.Tensor
+    ess: Optional[torch.Tensor]
+    mcse: Optional[torch.Tensor]
+    ess_chains: torch.Tensor
+    mcse_chains: torch.Tensor
+    lag_truncated: Optional[torch.Tensor]
+    num_draws: int
+    num_chains: int
+
+
+def _check_run(num_draws, num_chains, shape, split):
+    num_draws, num_chains, shape = int(num_draws), int(num_chains), tuple(int(s) for s in shape)
+    if len(shape) > 1:
+        raise ValueError(f"a chain's position must be a scalar or a vector, got shape {shape}")
+    if num_chains < 1 or (len(shape) == 1 and shape[0] < 1):
+        raise ValueError("num_chains and the position's length must be positive")
+    if split and num_draws < 4:
+        raise ValueError(f"split chains need at least 4 draws, got {num_draws}")
+    if not split and num_draws < 2:
+        raise ValueError(f"a summary needs at least 2 draws, got {num_draws}")
+    return num_draws, num_chains, shape
+
+
+def _check_draws(x, what):
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{what} must be a torch tensor (what kernel.sample returns), got {type(x).__name__}")
+    if x.dtype != torch.float64:
+        raise ValueError(f"{what} must be float64, got {x.dtype}")
+    if not x.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+
+
+class Accumulator:
+    """Streaming moments of a run of ``num_draws`` draws of ``num_chains`` chains whose position has shape ``shape``
+    (``()`` or ``(D,)``): ``update(chunk)`` folds the next draws, in order, ``result()`` gives the ``Summary`` once all
+    have arrived (``ess`` / ``mcse`` / ``lag_truncated`` None).  Where the chunks are cut does not change a bit."""
+
+    def __init__(self, num_draws: int, num_chains: int, shape, split: bool = True):
+        self.num_draws, self.num_chains, self.shape = _check_run(num_draws, num_chains, shape, split)
+        self.split = bool(split)
+        self.D = self.shape[0] if self.shape else 1
+        self._eng = get_engine()
+        S = 2 if self.split else 1
+        self.mean = torch.zeros(S, self.num_chains, self.D, dtype=torch.float64, device=self._eng.device)
+        self.m2 = torch.zeros_like(self.mean)
+        self.seen = 0
+
+    def _rows(self, chunk, what="chunk"):
+        _check_draws(chunk, what)
+        T = chunk.shape[0] if chunk.ndim else 0
+        tails = [(self.num_chains,) + self.shape] + ([self.shape] if self.num_chains == 1 else [])  # (one chain: no axis)
+        if T < 1 or tuple(chunk.shape[1:]) not in tails:
+            raise ValueError(f"{what} must be [T, {self.num_chains}" + "".join(f", {s}" for s in self.shape) +
+                             f"], got {tuple(chunk.shape)}")
+        if chunk.device != self._eng.device:
+            raise ValueError(f"{what} must be on {self._eng.device}, it is on {chunk.device}")
+        return chunk.reshape(T, self.num_chains, self.D)
+
+    def update(self, chunk):
+        return self._fold(self._rows(chunk))
+
+    def _fold(self, x):  # x: [T, C, D]
+        if self.seen + x.shape[0] > self.num_draws:
+            raise ValueError(f"{self.seen} draws folded, {x.shape[0]} more exceed the run's {self.num_draws}")
+        self._eng.summary_update(x, self.seen, self.num_draws, self.mean.shape[0], self.mean, self.m2)
+        self.seen += x.shape[0]
+        return self
+
+    def result(self, _acov=None) -> Summary:
+        if self.seen != self.num_draws:
+            raise ValueError(f"{self.seen} of {self.num_draws} draws folded")
+        out, trunc = self._eng.summary_final(self.num_draws, self.mean.shape[0], self.mean, self.m2, _acov)
+        f = [out[i].reshape(self.shape) for i in range(7)]
+        have = _acov is not None
+        return Summary(mean=f[0], sd=f[1], rhat=f[2], ess=f[3] if have else None, mcse=f[4] if have else None,
+                       ess_chains=f[5], mcse_chains=f[6],
+                       lag_truncated=trunc.bool().reshape(self.shape) if have else None,
+                       num_draws=self.num_draws, num_chains=self.num_chains)
+
+
+def summarize(samples, *, batched: bool = True, split: bool = True, max_lag: Optional[int] = None) -> Summary:
+    """Summary of stored draws ``samples`` [N, ...] as ``kernel.sample`` returns them: [N, C] or [N, C, D] with
+    ``batched`` (a leading chain axis, the default), [N] or [N, D] for one chain.  ``split``: every chain counts as
+    two, its first and its last N // 2 draws (arviz's and Stan's split R-hat / ESS).  ``max_lag``: the autocorrelation
+    sum uses lags 0 ... max_lag (default: every lag of a segment); segment length + lags may not exceed
+    ``MAX_ACOV_ROWS``."""
+    _check_draws(samples, "samples")
+    lo = 2 if batched else 1
+    if samples.ndim not in (lo, lo + 1):
+        raise ValueError(f"samples must be [N, C] or [N, C, D] (batched) or [N] / [N, D], got {tuple(samples.shape)}")
+    N = samples.shape[0]
+    C = samples.shape[1] if batched else 1
+    shape = tuple(samples.shape[lo:])
+    N, C, shape = _check_run(N, C, shape, split)
+    n = N // 2 if split else N
+    if max_lag is not None and int(max_lag) < 1:
+        raise ValueError("max_lag must be at least 1")
+    K = n if max_lag is None else min(int(max_lag) + 1, n)
+    if n + K > MAX_ACOV_ROWS:
+        fits = (f"max_lag <= {MAX_ACOV_ROWS - n - 1} fits at this length" if n <= MAX_ACOV_ROWS - 2 else
+                f"no max_lag fits segments above {MAX_ACOV_ROWS - 2} draws")
+        raise ValueError(f"the autocovariance kernel holds segment length + lags <= {MAX_ACOV_ROWS}: {N} draws give "
+                         f"segments of {n} draws with {K} lags ({fits}); summary.Accumulator gives the cross-chain "
+                         "estimators at any length")
+    acc = Accumulator(N, C, shape, split)
+    x = acc._rows(samples, "samples")
+    acc._fold(x)
+    acov = acc._eng.summary_autocov(x, 2 if split else 1, K, acc.mean)
+    return acc.result(acov)
+
+
+def rhat(samples, **kw):
+    return summarize(samples, **kw).rhat
+
+
+def ess(samples, **kw):
+    return summarize(samples, **kw).ess
+
+
+def mcse(samples, **kw):
+    return summarize(samples, **kw).mcse
+
+
+def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_integration_steps=None,
+        chunk: Optional[int] = None):
+    """Sample ``num_samples`` transitions per chain and summarise them without keeping them: ``kernel.sample`` is
+    driven in chunks of ``chunk`` draws into one reused buffer and every chunk is folded into an ``Accumulator``.
+    Returns ``(Summary, Diagnostics of the last transition, acceptance history, divergence history)`` -- what
+    ``kernel.sample`` returns with the summary in place of the draws (``n_leapfrog`` is the total of the run; the
+    Summary's ``ess`` / ``mcse`` / ``lag_truncated`` are None, its cross-chain estimators are what many chains are
+    judged by).  The chain states, the generator states and the histories are those of one ``kernel.sample`` call.
+
+    An HMC kernel needs ``num_integration_steps`` (as in ``window_adaptation.run``).  ``chunk=None``: the largest
+    chunk whose buffer stays under ``CHUNK_BYTES`` (1 GiB), at least one draw."""
+    is_hmc = getattr(kernel, "_hmc", None) is not None
+    if is_hmc and num_integration_steps is None:
+        raise ValueError("summary.run with an HMC kernel needs num_integration_steps")
+    if not hasattr(kernel, "sample"):
+        raise ValueError("summary.run needs a kernel of hmc.new_kernel / nuts.new_kernel (with .sample)")
+    extra = () if num_integration_steps is None else (int(num_integration_steps),)
+    pos = state.position
+    pshape = tuple(pos.shape) if hasattr(pos, "shape") else ()
+    batched = bool(getattr(kernel, "batched", len(pshape) == 2))
+    C = int(getattr(kernel, "num_chains", None) or (pshape[0] if batched else 1))
+    if batched and (len(pshape) < 1 or pshape[0] != C):
+        raise ValueError(f"position must have leading dimension {C}, got shape {pshape}")
+    shape = pshape[1:] if batched else pshape
+    N = int(num_samples)
+    if chunk is not None and int(chunk) < 1:
+        raise ValueError("chunk must be at least 1")
+    acc = Accumulator(N, C, shape)
+    per_draw = C * acc.D * 8
+    chunk = min(N, int(chunk) if chunk is not None else max(1, CHUNK_BYTES // per_draw))
+    dev = acc._eng.device
+    buf = torch.empty(chunk * C * acc.D, dtype=torch.float64, device=dev)
+    acc_hist = div_hist = info = total = None
+    done = 0
+    while done < N:
+        T = min(chunk, N - done)
+        samples, info, a, d = kernel.sample(state, step_size, inverse_mass_matrix, *extra, T, into=buf)
+        acc.update(samples.reshape((T, C) + shape))
+        if acc_hist is None:
+            acc_hist = torch.empty((N,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
+            div_hist = torch.empty((N,) + tuple(d.shape[1:]), dtype=d.dtype, device=d.device)
+        acc_hist[done:done + T], div_hist[done:done + T] = a, d
+        total = info.n_leapfrog if total is None else total + info.n_leapfrog
+        state = info.state._replace(momentum=None)
+        done += T
+    return acc.result(), info._replace(n_leapfrog=total), acc_hist, div_hist

@@ -359,6 +359,44 @@ int aehmc_welford_update(aehmc_ctx *ctx, int64_t C, int64_t D, int32_t full, con
 int aehmc_covariance_final(aehmc_ctx *ctx, int64_t C, int64_t D, int32_t full, int32_t shrink, const double *m2,
                            const int64_t *sample_size, double *out, void *stream);
 
+/* ---- posterior summaries of the draws (aehmc_amd/summary.py) ----
+ * What the reference's end-to-end checks compute on the host from every draw (tests/test_hmc.py:158-167: arviz.ess,
+ * then std / sqrt(ess)), on the device: per-chain moments, split R-hat, effective sample size and Monte-Carlo standard
+ * error per coordinate.  fp64, deterministic (no floating-point atomics, fixed summation orders: two calls on the same
+ * input are bit-equal).  All buffers are the caller's; none of these calls touches the workspace, the target or the
+ * metric.  `n_segments` is 1 (whole chains) or 2 (split chains): with h = num_draws / 2, draws [0, h) are segment 0 and
+ * draws [num_draws - h, num_draws) segment 1 (an odd run's middle draw belongs to neither); the segment length n is
+ * num_draws or h, the number of split chains m = n_segments * C.
+ *
+ * update: folds the chunk samples [T, C, D] -- draws t0 ... t0 + T - 1 of a run of num_draws -- into the running
+ * moments mean, m2 [n_segments, C, D] (Welford, ascending t; both start as ZEROS).  Chunks must arrive in order;
+ * where they are cut does not change a bit of the result.
+ *
+ * autocov: acov [K, D], for lags 0 ... K - 1 the biased autocovariance (divided by n) of every split chain about its
+ * own mean (`mean` as left by update after the whole run), averaged over the m split chains.  Needs all draws,
+ * samples [num_draws, C, D].  work [G, K, D] holds the partial sums of G groups of split chains (1 <= G <= m; group g
+ * takes the chains g, g + G, ... in order): more groups, more workgroups.  One coordinate's centred series and K zeros
+ * sit in a workgroup's LDS: n + K <= AEHMC_SUMMARY_MAX_ROWS, 2 <= K <= n.
+ *
+ * final: out [7, D] = mean, sd, rhat, ess, mcse, ess_chains, mcse_chains.  W = mean of the chains' variances (ddof 1),
+ * B/n = variance of the chains' means (ddof 1; 0 when m = 1), var+ = W (n - 1) / n + B/n; mean = pooled mean,
+ * sd = sqrt(var+), rhat = sqrt(var+ / W), mcse_chains = sqrt((B/n) / m) (NaN when m = 1), ess_chains = var+ / mcse_chains^2.
+ * With acov: rho_k = 1 - (W - acov_k) / var+, rho_0 = 1; pair sums P_j = rho_2j + rho_2j+1 are taken while positive
+ * (P_0 always) and clipped to the one before (Geyer's initial positive, initial monotone sequence);
+ * tau = -1 + 2 sum P_j + (the even term of the first non-positive pair, if positive), at least 1 / log10(m n);
+ * ess = m n / tau, mcse = sd / sqrt(ess); lag_truncated [D] = 1 where the pairs were still positive when the K lags ran
+ * out.  Without acov (NULL; lag_truncated may be NULL too) rows 3 and 4 of out are left alone.  A coordinate that never
+ * moved (var+ = 0) gives rhat = ess = ess_chains = NaN and mcse = 0. */
+#define AEHMC_SUMMARY_MAX_ROWS 8192
+int aehmc_summary_update(aehmc_ctx *ctx, int64_t T, int64_t C, int64_t D, int64_t t0, int64_t num_draws,
+                         int32_t n_segments, const double *samples, double *mean, double *m2, void *stream);
+int aehmc_summary_autocov(aehmc_ctx *ctx, int64_t num_draws, int64_t C, int64_t D, int32_t n_segments, int64_t K,
+                          int64_t G, const double *samples, const double *mean, double *work, double *acov,
+                          void *stream);
+int aehmc_summary_final(aehmc_ctx *ctx, int64_t num_draws, int64_t C, int64_t D, int32_t n_segments, int64_t K,
+                        const double *mean, const double *m2, const double *acov, double *out,
+                        int32_t *lag_truncated, void *stream);
+
 /* window_adaptation.run (window_adaptation.py:17-116) for a NUTS kernel: num_steps x (one transition
  * with the current per-chain parameters, then aehmc_adapt_update), enqueued in one call.  `stage` /
  * `is_window_end` [num_steps] are HOST arrays from build_schedule.  Before the call the caller binds
