@@ -1023,6 +1023,24 @@ extern "C" int aehmc_summary_final(aehmc_ctx *ctx, int64_t num_draws, int64_t C,
                            (hipStream_t)stream));
   return 0;
 }
+extern "C" int aehmc_summary_lag_update(aehmc_ctx *ctx, int64_t T, int64_t C, int64_t D, int64_t t0, int64_t num_draws,
+                                        int32_t n_segments, int64_t K, const double *samples, double *shift,
+                                        double *sums, double *ring, double *head, double *work, double *acov,
+                                        void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = summary_shape(ctx, "summary_lag_update", num_draws, C, D, n_segments)) return rc;
+  if (T <= 0 || t0 < 0 || t0 + T > num_draws || !samples || !shift || !sums || !ring || !head || !work || !acov)
+    FAIL("summary_lag_update: bad arguments");
+  if (K < 2 || K > num_draws / n_segments)
+    FAIL("summary_lag_update: the number of lags K must be in [2, segment length]");
+  const int cg = tu::summary_lag_group(K);
+  if ((C + cg - 1) / cg > 65535) FAIL("summary_lag_update: more than 65535 groups of chains");
+  HIPCHK(tu::summary_lag_update(samples, T, C, D, t0, num_draws, n_segments, K, cg, shift, sums, ring, head, work, acov,
+                                (hipStream_t)stream));
+  return 0;
+}
+extern "C" int64_t aehmc_summary_lag_group(int64_t K) { return K < 2 ? 0 : tu::summary_lag_group(K); }
 
 extern "C" int aehmc_set_option(aehmc_ctx *ctx, const char *name, int64_t value) {
   if (!ctx || !name) return -2;

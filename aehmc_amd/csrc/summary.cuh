@@ -238,6 +238,211 @@ __global__ __launch_bounds__(SUMMARY_THREADS) void k_summary_final(SummaryFinalA
   }
 }
 
+// ---- streaming autocovariance: lagged products over a ring of the last K - 1 draws (aehmc_summary_lag_update) ----
+// A split chain's draws are shifted by its first draw a (y_t = x_t - a: products of shifted draws survive an offset
+// that raw products would not).  State between calls, all of it the caller's: shift [C][D] (a), sums [C][D]
+// (Y = sum of y_t, ascending t), ring [K - 1][C][D] (y of segment position p in slot p mod (K - 1)), head [K - 1][C][D]
+// (y of the first K - 1 positions) and prod [G][K][D]: R(k) = sum_t y_t y_{t-k}, summed over the chains of group g.
+constexpr int SUMMARY_LAG_DB = 16;                                // coordinates per workgroup
+constexpr int SUMMARY_LAG_LPB = SUMMARY_THREADS / SUMMARY_LAG_DB;  // lag lanes per coordinate
+constexpr int SUMMARY_LAG_TB = 4;                                 // draws a lane multiplies per pass over its rows
+constexpr int SUMMARY_LAG_CG_MAX = 4;                             // chains per group, a power of two
+constexpr int SUMMARY_LAG_SHORT_CG = 4, SUMMARY_LAG_LONG_CG = 2;  // ... of the two variants below
+constexpr int SUMMARY_LAG_SHORT = 3, SUMMARY_LAG_SHORT_TILE = 32;  // K <= 48: 3 lags per lane, tiles of 32 draws
+constexpr int SUMMARY_LAG_LONG = 9, SUMMARY_LAG_LONG_TILE = 16;    // above: 9 lags per lane, tiles of 16 draws
+constexpr long long SUMMARY_LAG_SHORT_K = (long long)SUMMARY_LAG_LPB * SUMMARY_LAG_SHORT;
+
+struct SummaryLagArgs {
+  const double *x;  // the chunk [.][C][D]
+  double *shift, *sums, *ring, *head, *prod;
+  long long C, D, K;
+  long long ta, T;          // rows [ta, ta + T) of the chunk belong to the segment ...
+  long long p0;             // ... as its positions p0, p0 + 1, ...
+  long long base0, base1;   // p0 mod (K - 1), (p0 + T) mod (K - 1)
+  int CG;                   // chains per group
+};
+
+// doubles of LDS per row of CG chains x 16 coordinates: a lag lane is LB (odd) rows from the next, and 16 doubles of
+// padding put the two lag lanes of a 32-lane group of ds_read_b64 on different halves of the 64 banks
+__host__ __device__ inline int summary_lag_row(int CG) {
+  const int W = CG * SUMMARY_LAG_DB;
+  return W % 32 == 0 ? W + 16 : W;
+}
+template <int LB, int TT> inline size_t summary_lag_lds(int CG, long long K) {
+  const int KP = SUMMARY_LAG_LPB * LB;
+  return ((size_t)(TT + KP - 1 + (K > KP ? TT : 0)) * summary_lag_row(CG) + CG * SUMMARY_LAG_DB) * sizeof(double);
+}
+
+// The fold.  Workgroup (x: block of 16 coordinates, y: group g of CG consecutive chains).  Per tile of TT draws it
+// stages in LDS, shifted on load, the rows the lags of this pass reach back to (from the ring where they precede the
+// chunk, zeros before the segment) and the tile itself.  Lane (lag lane kl, coordinate j) owns LB consecutive lags and
+// takes SUMMARY_LAG_TB consecutive draws at a time: TB + (TB + LB - 1) LDS reads serve TB * LB FMAs, per chain.  For
+// every draw the products of the group's chains are summed first, in chain order from zero, and that sum is added to the
+// lane's accumulator: the additions into an accumulator are one per draw in ascending t whatever the chunking and the
+// tiling, which is what keeps a chunk boundary invisible.  A pass covers 16 * LB lags; more lags, more passes.
+template <int LB, int TT>
+__global__ __launch_bounds__(SUMMARY_THREADS) void k_summary_lag_fold(SummaryLagArgs a) {
+  extern __shared__ double s_lag[];
+  constexpr int DB = SUMMARY_LAG_DB, TB = SUMMARY_LAG_TB, KP = SUMMARY_LAG_LPB * LB, PR = TT + KP - 1;
+  static_assert(TT % TB == 0 && LB % 2 == 1, "tile and lag blocking");
+  const int CG = a.CG, W = CG * DB, wsh = __ffs(W) - 1, RS = summary_lag_row(CG);
+  const int tid = threadIdx.x, j = tid & (DB - 1), kl = tid / DB;
+  const long long D = a.D, E = a.C * D, K = a.K, Km1 = K - 1, T = a.T;
+  const long long d0 = (long long)blockIdx.x * DB, c0 = (long long)blockIdx.y * CG;
+  const int ncg = (int)((a.C - c0) < CG ? (a.C - c0) : CG);
+  const bool fresh = a.p0 == 0, multi = K > KP;
+  double *s_past = s_lag, *s_sep = s_lag + PR * RS, *s_a = s_lag + (PR + (multi ? TT : 0)) * RS;
+  const double *xs = a.x + a.ta * E;
+
+  // the (chain, coordinate) this thread stages: the same for every row it touches (256 is a multiple of W)
+  const int e = tid & (W - 1), ecc = e / DB;
+  const bool eok = ecc < ncg && d0 + (e & (DB - 1)) < D;
+  const long long eoff = eok ? (c0 + ecc) * D + d0 + (e & (DB - 1)) : 0;
+  double ysum = 0.0;
+  if (tid < W) {
+    s_a[tid] = eok ? (fresh ? xs[eoff] : a.shift[eoff]) : 0.0;
+    if (eok && !fresh) ysum = a.sums[eoff];
+  }
+  __syncthreads();
+  const double ea = s_a[e];
+  const bool dlive = d0 + j < D;
+
+  for (long long kp = 0; kp < K; kp += KP) {
+    const long long kb = kp + (long long)kl * LB;
+    const bool active = kb < K;
+    double acc[LB];
+#pragma unroll
+    for (int i = 0; i < LB; ++i)
+      acc[i] = (!fresh && dlive && kb + i < K) ? a.prod[((long long)blockIdx.y * K + kb + i) * D + d0 + j] : 0.0;
+    const double *s_cur = kp == 0 ? s_past + (KP - 1) * RS : s_sep;
+    for (long long tl = 0; tl < T; tl += TT) {
+      const int nt = (int)((T - tl) < TT ? (T - tl) : TT);
+      __syncthreads();
+      for (int r = tid >> wsh; r < PR; r += SUMMARY_THREADS >> wsh) {
+        const long long rel = tl - kp - (KP - 1) + r;  // chunk row of the segment's part; negative: before the chunk
+        double v = 0.0;
+        if (eok && a.p0 + rel >= 0 && rel < T) {
+          if (rel >= 0) {
+            v = xs[rel * E + eoff] - ea;
+          } else if (-rel <= Km1) {
+            long long sl = a.base0 + rel;
+            if (sl < 0) sl += Km1;
+            v = a.ring[sl * E + eoff];
+          }
+        }
+        s_past[r * RS + e] = v;
+      }
+      if (kp > 0)
+        for (int r = tid >> wsh; r < TT; r += SUMMARY_THREADS >> wsh)
+          s_sep[r * RS + e] = (eok && tl + r < T) ? xs[(tl + r) * E + eoff] - ea : 0.0;
+      __syncthreads();
+      if (kp == 0 && tid < W)
+        for (int t = 0; t < nt; ++t) ysum += s_cur[t * RS + tid];
+      if (!active) continue;
+      for (int tt0 = 0; tt0 < nt; tt0 += TB) {
+        double s[TB][LB];
+#pragma unroll
+        for (int tb = 0; tb < TB; ++tb)
+#pragma unroll
+          for (int i = 0; i < LB; ++i) s[tb][i] = 0.0;
+        const double *pw = s_past + (tt0 + KP - kl * LB - LB) * RS + j;
+        const double *pc = s_cur + tt0 * RS + j;
+        for (int cc = 0; cc < ncg; ++cc) {
+          double w[TB + LB - 1], y[TB];
+#pragma unroll
+          for (int q = 0; q < TB + LB - 1; ++q) w[q] = pw[q * RS + cc * DB];
+#pragma unroll
+          for (int tb = 0; tb < TB; ++tb) y[tb] = pc[tb * RS + cc * DB];
+#pragma unroll
+          for (int tb = 0; tb < TB; ++tb)
+#pragma unroll
+            for (int i = 0; i < LB; ++i) s[tb][i] = fma(y[tb], w[tb + LB - 1 - i], s[tb][i]);
+        }
+#pragma unroll
+        for (int tb = 0; tb < TB; ++tb)
+          if (tt0 + tb < nt) {
+#pragma unroll
+            for (int i = 0; i < LB; ++i) acc[i] += s[tb][i];
+          }
+      }
+    }
+    if (active && dlive) {
+#pragma unroll
+      for (int i = 0; i < LB; ++i)
+        if (kb + i < K) a.prod[((long long)blockIdx.y * K + kb + i) * D + d0 + j] = acc[i];
+    }
+  }
+
+  // carry: the last min(T, K - 1) shifted draws into their ring slots, the segment's first K - 1 into the head.  Every
+  // read of the ring lies before the last barrier above, and no other workgroup touches these chains and coordinates.
+  if (!eok) return;
+  const long long nring = T < Km1 ? T : Km1;
+  for (long long q = 1 + (tid >> wsh); q <= nring; q += SUMMARY_THREADS >> wsh) {
+    long long sl = a.base1 - q;
+    if (sl < 0) sl += Km1;
+    a.ring[sl * E + eoff] = xs[(T - q) * E + eoff] - ea;
+  }
+  const long long hend = (a.p0 + T) < Km1 ? (a.p0 + T) : Km1;
+  for (long long p = a.p0 + (tid >> wsh); p < hend; p += SUMMARY_THREADS >> wsh)
+    a.head[p * E + eoff] = xs[(p - a.p0) * E + eoff] - ea;
+  if (tid < W) {
+    a.sums[eoff] = ysum;
+    if (fresh) a.shift[eoff] = ea;
+  }
+}
+
+struct SummaryLagEndArgs {
+  const double *sums, *ring, *head;
+  double *prod, *acov;
+  long long C, D, K, G, n, basen;  // n: segment length, basen = n mod (K - 1)
+  int CG, first, last;             // first / last segment of the run
+  double m;                        // number of split chains
+};
+
+// The segment finaliser, at a segment's last draw.  With ybar = Y / n and first_k / last_k the sums of the chain's first
+// and last k shifted draws (running sums over the head and the ring): n acov(k) = R(k) - ybar (2 Y - first_k - last_k)
+// + (n - k) ybar^2.  Thread (group g, coordinate d) adds the corrections of its chains, in chain order, to prod[g].
+__global__ __launch_bounds__(SUMMARY_THREADS) void k_summary_lag_center(SummaryLagEndArgs a) {
+  const long long i = (long long)blockIdx.x * SUMMARY_THREADS + threadIdx.x;
+  if (i >= a.G * a.D) return;
+  const long long g = i / a.D, d = i % a.D, D = a.D, E = a.C * D, Km1 = a.K - 1, c0 = g * a.CG;
+  const int ncg = (int)((a.C - c0) < a.CG ? (a.C - c0) : a.CG);
+  const double dn = (double)a.n;
+  double Y[SUMMARY_LAG_CG_MAX], yb[SUMMARY_LAG_CG_MAX], F[SUMMARY_LAG_CG_MAX], L[SUMMARY_LAG_CG_MAX];
+#pragma unroll
+  for (int c = 0; c < SUMMARY_LAG_CG_MAX; ++c) {
+    Y[c] = c < ncg ? a.sums[(c0 + c) * D + d] : 0.0;
+    yb[c] = Y[c] / dn;
+    F[c] = L[c] = 0.0;
+  }
+  for (long long k = 0; k < a.K; ++k) {
+    long long sl = a.basen - k;
+    if (sl < 0) sl += Km1;
+    double corr = 0.0;
+#pragma unroll
+    for (int c = 0; c < SUMMARY_LAG_CG_MAX; ++c) {
+      if (c >= ncg) continue;
+      if (k > 0) {
+        F[c] += a.head[(k - 1) * E + (c0 + c) * D + d];
+        L[c] += a.ring[sl * E + (c0 + c) * D + d];
+      }
+      corr += (dn - (double)k) * yb[c] * yb[c] - yb[c] * (2.0 * Y[c] - F[c] - L[c]);
+    }
+    a.prod[(g * a.K + k) * D + d] += corr;
+  }
+}
+
+// acov[k][d] (+)= (sum over the groups, ascending) / n; after the run's last segment, / (number of split chains)
+__global__ __launch_bounds__(SUMMARY_THREADS) void k_summary_lag_reduce(SummaryLagEndArgs a) {
+  const long long i = (long long)blockIdx.x * SUMMARY_THREADS + threadIdx.x, KD = a.K * a.D;
+  if (i >= KD) return;
+  double sum = 0.0;
+  for (long long g = 0; g < a.G; ++g) sum += a.prod[g * KD + i];
+  double v = sum / (double)a.n;
+  if (!a.first) v = a.acov[i] + v;
+  a.acov[i] = a.last ? v / a.m : v;
+}
+
 // ---- launches (tu_summary.hip) ----
 inline hipError_t launch_summary_update(const double *x, long long T, long long E, long long t0, long long N, int S,
                                         double *mean, double *m2, hipStream_t st) {
@@ -291,6 +496,66 @@ inline hipError_t launch_summary_final(const double *mean, const double *m2, con
   a.DX = DX;
   hipLaunchKernelGGL(k_summary_final, dim3((unsigned)((D + DX - 1) / DX)), dim3(SUMMARY_THREADS), 0, st, a);
   return hipGetLastError();
+}
+
+template <int LB, int TT>
+inline hipError_t launch_summary_lag_fold(const SummaryLagArgs &a, long long G, hipStream_t st) {
+  static bool lds_opt_in_dev[64] = {};  // once per device and instantiation: the most this kernel asks for
+  int dev = 0;
+  if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+  bool unset = false, &lds_opt_in = (dev >= 0 && dev < 64) ? lds_opt_in_dev[dev] : unset;
+  if (!lds_opt_in) {
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_summary_lag_fold<LB, TT>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)summary_lag_lds<LB, TT>(LB == SUMMARY_LAG_SHORT ? SUMMARY_LAG_SHORT_CG : SUMMARY_LAG_LONG_CG,
+                                                                         LB == SUMMARY_LAG_SHORT ? 2 : 1 << 20));
+        e != hipSuccess)
+      return e;
+    lds_opt_in = true;
+  }
+  const size_t dyn = summary_lag_lds<LB, TT>(a.CG, a.K);
+  hipLaunchKernelGGL((k_summary_lag_fold<LB, TT>),
+                     dim3((unsigned)((a.D + SUMMARY_LAG_DB - 1) / SUMMARY_LAG_DB), (unsigned)G), dim3(SUMMARY_THREADS),
+                     dyn, st, a);
+  return hipGetLastError();
+}
+
+// chains per group at K lags: what the fold's LDS holds (aehmc_summary_lag_group tells the caller, who sizes `work`)
+inline int summary_lag_group(long long K) { return K <= SUMMARY_LAG_SHORT_K ? SUMMARY_LAG_SHORT_CG : SUMMARY_LAG_LONG_CG; }
+
+// Draws t0 ... t0 + T - 1 of a run of N: the part of every segment the chunk holds is folded, and a segment whose last
+// draw it holds is centred and reduced into acov (complete once the run's last draw has been folded).
+inline hipError_t launch_summary_lag_update(const double *x, long long T, long long C, long long D, long long t0,
+                                            long long N, int S, long long K, int CG, double *shift, double *sums,
+                                            double *ring, double *head, double *prod, double *acov, hipStream_t st) {
+  const long long h = N / 2, n = S == 2 ? h : N, Km1 = K - 1, G = (C + CG - 1) / CG;
+  for (int seg = 0; seg < S; ++seg) {
+    const long long slo = seg == 0 ? 0 : N - h, shi = (S == 1) ? N : (seg == 0 ? h : N);
+    const long long lo = t0 > slo ? t0 : slo, hi = (t0 + T) < shi ? (t0 + T) : shi;
+    if (lo >= hi) continue;
+    SummaryLagArgs a;
+    a.x = x; a.shift = shift; a.sums = sums; a.ring = ring; a.head = head; a.prod = prod;
+    a.C = C; a.D = D; a.K = K; a.CG = CG;
+    a.ta = lo - t0; a.T = hi - lo; a.p0 = lo - slo;
+    a.base0 = a.p0 % Km1; a.base1 = (a.p0 + a.T) % Km1;
+    if (hipError_t e = K <= SUMMARY_LAG_SHORT_K
+                           ? launch_summary_lag_fold<SUMMARY_LAG_SHORT, SUMMARY_LAG_SHORT_TILE>(a, G, st)
+                           : launch_summary_lag_fold<SUMMARY_LAG_LONG, SUMMARY_LAG_LONG_TILE>(a, G, st);
+        e != hipSuccess)
+      return e;
+    if (hi < shi) continue;
+    SummaryLagEndArgs f;
+    f.sums = sums; f.ring = ring; f.head = head; f.prod = prod; f.acov = acov;
+    f.C = C; f.D = D; f.K = K; f.G = G; f.n = n; f.basen = n % Km1;
+    f.CG = CG; f.first = seg == 0; f.last = seg == S - 1; f.m = (double)(S * C);
+    hipLaunchKernelGGL(k_summary_lag_center, dim3((unsigned)((G * D + SUMMARY_THREADS - 1) / SUMMARY_THREADS)),
+                       dim3(SUMMARY_THREADS), 0, st, f);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_summary_lag_reduce, dim3((unsigned)((K * D + SUMMARY_THREADS - 1) / SUMMARY_THREADS)),
+                       dim3(SUMMARY_THREADS), 0, st, f);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace aehmc

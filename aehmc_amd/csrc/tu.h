@@ -48,5 +48,9 @@ hipError_t summary_acov(const double *x, const double *mean, double *partial, do
                         long long D, int S, long long K, int G, hipStream_t st);
 hipError_t summary_final(const double *mean, const double *m2, const double *acov, double *out, int *lag_truncated,
                          long long n, long long m, long long D, long long K, hipStream_t st);
+hipError_t summary_lag_update(const double *x, long long T, long long C, long long D, long long t0, long long N, int S,
+                              long long K, int CG, double *shift, double *sums, double *ring, double *head,
+                              double *prod, double *acov, hipStream_t st);
+int summary_lag_group(long long K);
 }  // namespace tu
 }  // namespace aehmc

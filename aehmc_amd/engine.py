@@ -647,6 +647,20 @@ class Engine:
                     "aehmc_summary_autocov")
         return acov
 
+    def summary_lag_group(self, K):
+        """Chains per group of the streaming fold at K lags: work is [ceil(C / group), K, D]."""
+        return int(self.lib.aehmc_summary_lag_group(int(K)))
+
+    def summary_lag_update(self, chunk, t0, num_draws, n_segments, K, shift, sums, ring, head, work, acov):
+        """Fold draws t0 ... t0 + T - 1 (chunk [T, C, D]) into the lagged products work [G, K, D] over the ring of the
+        last K - 1 shifted draws; acov [K, D] is complete once the run's last draw has been folded."""
+        T, C, D = chunk.shape
+        self._check(self.lib.aehmc_summary_lag_update(self.ctx, T, C, D, int(t0), int(num_draws), int(n_segments), int(K),
+                                                      chunk.data_ptr(), shift.data_ptr(),
+                                                      sums.data_ptr(), ring.data_ptr(), head.data_ptr(), work.data_ptr(),
+                                                      acov.data_ptr(), self.stream),
+                    "aehmc_summary_lag_update")
+
     def summary_final(self, num_draws, n_segments, mean, m2, acov=None):
         """out [7, D] (mean, sd, rhat, ess, mcse, ess_chains, mcse_chains) and lag_truncated [D] (None without acov)."""
         _, C, D = mean.shape

@@ -1,5 +1,6 @@
 """Posterior summaries on the device: per-coordinate mean, sd, split R-hat, effective sample size and Monte-Carlo
-standard error of what ``kernel.sample`` draws (``aehmc_summary_update`` / ``_autocov`` / ``_final``, csrc/summary.cuh).
+standard error of what ``kernel.sample`` draws (``aehmc_summary_update`` / ``_autocov`` / ``_lag_update`` / ``_final``,
+csrc/summary.cuh).
 
 The reference leaves this to arviz on the host (tests/test_hmc.py:158-167: ``arviz.ess``, then ``std / sqrt(ess)``).
 Here the draws stay where they are, and a run whose draws cannot be stored at all (4096 chains x 10^4 coordinates are
@@ -12,7 +13,10 @@ Two families of estimators per coordinate, with n draws per (split) chain and m 
   independent chain means: exact whatever the autocorrelation, and sharp with many chains), ess_chains = var+ /
   mcse_chains^2.  They need running moments only, so they stream.
 - along chains -- ``ess``, ``mcse``, ``lag_truncated``: Stan's estimator from the chain-averaged autocovariance with
-  Geyer's initial positive, initial monotone sequence.  It needs every draw, so only ``summarize`` gives it.
+  Geyer's initial positive, initial monotone sequence.  ``summarize`` computes it from the stored draws.  With
+  ``max_lag`` given, ``Accumulator`` and ``run`` stream it too: lagged products of the draws, shifted by the chain's
+  first draw, over a ring of the last ``max_lag`` draws, centred when a segment ends -- the quantity of
+  ``summarize(samples, max_lag=...)`` to rounding, for a run of any length.
 
 fp64, deterministic: two calls on the same draws, and any chunking of them, give the same bits.  No CPU fallback."""
 from __future__ import annotations
@@ -33,7 +37,7 @@ CHUNK_BYTES = 1 << 30
 class Summary(NamedTuple):
     """Per-coordinate device tensors shaped like one chain's position, plus the run's size.  ``ess``, ``mcse`` and
     ``lag_truncated`` (bool: the autocorrelation pairs were still positive at the last lag, so ``ess`` is an
-    over-estimate -- raise ``max_lag`` or run longer) are None in streaming mode."""
+    over-estimate -- raise ``max_lag`` or run longer) are None in streaming mode unless ``max_lag`` is given."""
     mean: torch.Tensor
     sd: torch.Tensor
     rhat: torch.Tensor
@@ -71,17 +75,34 @@ def _check_draws(x, what):
 class Accumulator:
     """Streaming moments of a run of ``num_draws`` draws of ``num_chains`` chains whose position has shape ``shape``
     (``()`` or ``(D,)``): ``update(chunk)`` folds the next draws, in order, ``result()`` gives the ``Summary`` once all
-    have arrived (``ess`` / ``mcse`` / ``lag_truncated`` None).  Where the chunks are cut does not change a bit."""
+    have arrived.  Where the chunks are cut, a chunk of one draw included, does not change a bit.
 
-    def __init__(self, num_draws: int, num_chains: int, shape, split: bool = True):
+    ``max_lag=None``: moments only, ``ess`` / ``mcse`` / ``lag_truncated`` are None.  ``max_lag=L``: they are Stan's ESS
+    from lags 0 ... L of the chain-averaged autocovariance (K = min(L + 1, segment length) lags), streamed as lagged
+    products over a ring of the last K - 1 draws.  That costs memory: a ring and a head of K - 1 draws each, and the
+    products of groups of 4 chains (2 above 48 lags), K / 4 (K / 2) draws more -- about 2.25 (K - 1) draws in all;
+    ``max_lag=32`` at 4096 chains x 10^4 coordinates is about 24 GB."""
+
+    def __init__(self, num_draws: int, num_chains: int, shape, split: bool = True, max_lag: Optional[int] = None):
         self.num_draws, self.num_chains, self.shape = _check_run(num_draws, num_chains, shape, split)
         self.split = bool(split)
         self.D = self.shape[0] if self.shape else 1
+        if max_lag is not None and int(max_lag) < 1:
+            raise ValueError("max_lag must be at least 1")
         self._eng = get_engine()
         S = 2 if self.split else 1
-        self.mean = torch.zeros(S, self.num_chains, self.D, dtype=torch.float64, device=self._eng.device)
+        C, D, dev = self.num_chains, self.D, self._eng.device
+        self.mean = torch.zeros(S, C, D, dtype=torch.float64, device=dev)
         self.m2 = torch.zeros_like(self.mean)
         self.seen = 0
+        self.lags = None if max_lag is None else min(int(max_lag) + 1, self.num_draws // S)
+        if self.lags is not None:
+            K = self.lags
+            self._group = self._eng.summary_lag_group(K)  # chains whose products are summed before they are stored
+            self._shift, self._sums = (torch.zeros(C, D, dtype=torch.float64, device=dev) for _ in range(2))
+            self._ring, self._head = (torch.zeros(K - 1, C, D, dtype=torch.float64, device=dev) for _ in range(2))
+            self._prod = torch.zeros(-(-C // self._group), K, D, dtype=torch.float64, device=dev)
+            self._acov = torch.zeros(K, D, dtype=torch.float64, device=dev)
 
     def _rows(self, chunk, what="chunk"):
         _check_draws(chunk, what)
@@ -101,12 +122,17 @@ class Accumulator:
         if self.seen + x.shape[0] > self.num_draws:
             raise ValueError(f"{self.seen} draws folded, {x.shape[0]} more exceed the run's {self.num_draws}")
         self._eng.summary_update(x, self.seen, self.num_draws, self.mean.shape[0], self.mean, self.m2)
+        if self.lags is not None:
+            self._eng.summary_lag_update(x, self.seen, self.num_draws, self.mean.shape[0], self.lags, self._shift,
+                                         self._sums, self._ring, self._head, self._prod, self._acov)
         self.seen += x.shape[0]
         return self
 
     def result(self, _acov=None) -> Summary:
         if self.seen != self.num_draws:
             raise ValueError(f"{self.seen} of {self.num_draws} draws folded")
+        if _acov is None and self.lags is not None:
+            _acov = self._acov
         out, trunc = self._eng.summary_final(self.num_draws, self.mean.shape[0], self.mean, self.m2, _acov)
         f = [out[i].reshape(self.shape) for i in range(7)]
         have = _acov is not None
@@ -140,7 +166,7 @@ def summarize(samples, *, batched: bool = True, split: bool = True, max_lag: Opt
         raise ValueError(f"the autocovariance kernel holds segment length + lags <= {MAX_ACOV_ROWS}: {N} draws give "
                          f"segments of {n} draws with {K} lags ({fits}); summary.Accumulator gives the cross-chain "
                          "estimators at any length")
-    acc = Accumulator(N, C, shape, split)
+    acc = Accumulator(N, C, shape, split)  # (moments only: the autocovariance comes from the stored draws)
     x = acc._rows(samples, "samples")
     acc._fold(x)
     acov = acc._eng.summary_autocov(x, 2 if split else 1, K, acc.mean)
@@ -160,13 +186,17 @@ def mcse(samples, **kw):
 
 
 def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_integration_steps=None,
-        chunk: Optional[int] = None):
+        chunk: Optional[int] = None, max_lag: Optional[int] = None):
     """Sample ``num_samples`` transitions per chain and summarise them without keeping them: ``kernel.sample`` is
     driven in chunks of ``chunk`` draws into one reused buffer and every chunk is folded into an ``Accumulator``.
     Returns ``(Summary, Diagnostics of the last transition, acceptance history, divergence history)`` -- what
-    ``kernel.sample`` returns with the summary in place of the draws (``n_leapfrog`` is the total of the run; the
-    Summary's ``ess`` / ``mcse`` / ``lag_truncated`` are None, its cross-chain estimators are what many chains are
-    judged by).  The chain states, the generator states and the histories are those of one ``kernel.sample`` call.
+    ``kernel.sample`` returns with the summary in place of the draws (``n_leapfrog`` is the total of the run).  The
+    chain states, the generator states and the histories are those of one ``kernel.sample`` call.
+
+    ``max_lag=None``: the Summary's ``ess`` / ``mcse`` / ``lag_truncated`` are None, its cross-chain estimators are
+    what many chains are judged by.  ``max_lag=L``: they are those of ``summarize(samples, max_lag=L)`` to rounding,
+    from a ring of the last draws instead of all of them -- about 2.25 L draws of extra memory (see ``Accumulator``;
+    ``max_lag=32`` at 4096 chains x 10^4 coordinates is about 24 GB).
 
     An HMC kernel needs ``num_integration_steps`` (as in ``window_adaptation.run``).  ``chunk=None``: the largest
     chunk whose buffer stays under ``CHUNK_BYTES`` (1 GiB), at least one draw."""
@@ -186,7 +216,7 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
     N = int(num_samples)
     if chunk is not None and int(chunk) < 1:
         raise ValueError("chunk must be at least 1")
-    acc = Accumulator(N, C, shape)
+    acc = Accumulator(N, C, shape, max_lag=max_lag)
     per_draw = C * acc.D * 8
     chunk = min(N, int(chunk) if chunk is not None else max(1, CHUNK_BYTES // per_draw))
     dev = acc._eng.device

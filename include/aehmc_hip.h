@@ -397,6 +397,25 @@ int aehmc_summary_final(aehmc_ctx *ctx, int64_t num_draws, int64_t C, int64_t D,
                         const double *mean, const double *m2, const double *acov, double *out,
                         int32_t *lag_truncated, void *stream);
 
+/* The same acov [K, D] without the stored draws, for a run of any length: lag_update folds the chunk samples [T, C, D]
+ * (draws t0 ... t0 + T - 1, in order, as update) into lagged products over a ring of the last K - 1 draws, and leaves
+ * acov complete once the run's last draw has been folded; it then goes into final as it stands.  2 <= K <= n, and no
+ * AEHMC_SUMMARY_MAX_ROWS limit.  Every split chain is shifted by its first draw a (y_t = x_t - a); per chain
+ * R(k) = sum_{t >= k} y_t y_{t-k} and Y = sum y_t are accumulated in ascending t, and at the segment's last draw, with
+ * ybar = Y / n and first_k / last_k the sums of its first / last k shifted draws,
+ *   n acov(k) = R(k) - ybar (2 Y - first_k - last_k) + (n - k) ybar^2,
+ * which is the autocovariance about the chain's own mean.  State between the calls, all ZEROS at the start and not to
+ * be touched in between: shift, sums [C, D] (a, Y), ring, head [K - 1, C, D] (the last and the segment's first K - 1
+ * shifted draws) and work [G, K, D], G = ceil(C / aehmc_summary_lag_group(K)): the products, summed over the chains of
+ * a group for every draw before they are added, groups reduced in ascending order.  lag_group(K) is the number of
+ * consecutive chains per group the engine uses at K lags (the group's rows sit in LDS: 4 up to 48 lags, 2 above; 0 for
+ * K < 2).  Segment 1 reuses the state of segment 0.  No floating-point atomics: the
+ * additions into every accumulator depend on the shapes alone, so where the chunks are cut does not change a bit. */
+int aehmc_summary_lag_update(aehmc_ctx *ctx, int64_t T, int64_t C, int64_t D, int64_t t0, int64_t num_draws,
+                             int32_t n_segments, int64_t K, const double *samples, double *shift, double *sums,
+                             double *ring, double *head, double *work, double *acov, void *stream);
+int64_t aehmc_summary_lag_group(int64_t K);
+
 /* window_adaptation.run (window_adaptation.py:17-116) for a NUTS kernel: num_steps x (one transition
  * with the current per-chain parameters, then aehmc_adapt_update), enqueued in one call.  `stage` /
  * `is_window_end` [num_steps] are HOST arrays from build_schedule.  Before the call the caller binds
