@@ -711,7 +711,7 @@ extern "C" int aehmc_set_custom_target(aehmc_ctx *ctx, const char *source, int64
 static int gemm(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, const double *A, int64_t lda,
                 const double *B, int64_t ldb, double *Cm, int64_t ldc, hipStream_t st,
                 const int *row_idx = nullptr, const int *n_rows = nullptr, int mode = 0, int tri = 0,
-                bool carry_in = false);
+                bool carry_in = false, bool in_place = false);
 
 // Blocked (64-wide) right-looking Cholesky of Lw [D,D] in place (lower triangle; the upper one keeps the input);
 // `inv`, `invT`: [NB,NB] scratch each, `info`: the first failed pivot
@@ -725,7 +725,8 @@ static int dense_cholesky(aehmc_ctx *ctx, double *Lw, int64_t D, double *inv, do
                        invT, info, (int)j0);
     if (M > 0) {
       double *panel = Lw + (j0 + nb) * D + j0;
-      rc = gemm(ctx, M, nb, nb, panel, D, inv, NB, panel, D, st);                     // L21 = A21 L11^-T
+      // L21 = A21 L11^-T, in place: only on kernels whose workgroups own complete rows (launch_gemm_nt_f64: in_place)
+      rc = gemm(ctx, M, nb, nb, panel, D, inv, NB, panel, D, st, nullptr, nullptr, 0, 0, false, true);
       if (!rc) rc = gemm(ctx, M, M, nb, panel, D, panel, D, Lw + (j0 + nb) * D + (j0 + nb), D, st, nullptr,
                          nullptr, 1);                                                   // A22 -= L21 L21^T
     }
@@ -1270,7 +1271,7 @@ extern "C" int aehmc_synchronize(aehmc_ctx *ctx, void *stream) {
 }
 static int gemm(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, const double *A, int64_t lda,
                 const double *B, int64_t ldb, double *Cm, int64_t ldc, hipStream_t st,
-                const int *row_idx, const int *n_rows, int mode, int tri, bool carry_in) {
+                const int *row_idx, const int *n_rows, int mode, int tri, bool carry_in, bool in_place) {
   // tri: triangular hint for B (gemm_f64.cuh).  carry_in: one of white_begin's two input products on the rows that
   // could not be carried -- often none, so it is kept out of the timed launch pairs (its flops are still counted), and
   // its rows are not bounded by rows_hint, which belongs to the lock-step loop
@@ -1284,7 +1285,7 @@ static int gemm(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, const double *A
     if (!carry_in && n_rows && ctx->rows_hint > 0 && ctx->rows_hint < M) M = ctx->rows_hint;
     HIPCHK(tu::gemm_nt_f64(M, N, K, A, lda, B, ldb, Cm, ldc, st, row_idx, n_rows,
                            p ? ctx->d_flops : nullptr, (use_sk && mode == 0) ? &sk : nullptr, ctx->sk_grid,
-                           mode, ctx->opt_streamk == 2 ? ctx->sk_grid_wide : 0, ctx->opt_gemm_small, tri));
+                           mode, ctx->opt_streamk == 2 ? ctx->sk_grid_wide : 0, ctx->opt_gemm_small, tri, in_place));
     return 0;
   };
   if (carry_in) return launch(ctx->prof && !ctx->prof_ev.empty());

@@ -862,16 +862,22 @@ inline hipError_t launch_gemm_nt_f64(int64_t M, int64_t N, int64_t K, const doub
                                      const int *row_idx = nullptr, const int *n_rows = nullptr,
                                      unsigned long long *flop_counter = nullptr,
                                      const GemmStreamK *sk = nullptr, int sk_grid = 0, int mode = 0,
-                                     int sk_grid_wide = 0, int small_tiles = 1, int tri = 0) {
+                                     int sk_grid_wide = 0, int small_tiles = 1, int tri = 0,
+                                     bool in_place = false) {
   // tri: triangular-operand hint (see gemm_nt_f64_streamk_kernel's TRI).  Only the 128 x 256 stream-K kernel honours
   // it; every other kernel computes the full product, which for finite A is the same bits.
+  // in_place: Cm is A (N <= 64, N <= K: the blocked Cholesky's panel product).  Allowed on the kernels in which ONE
+  // workgroup owns complete output rows (every tile here is at least 64 columns wide) and stores them behind the
+  // barrier that follows its last operand read.  The tail kernel is not one of them: its four wavefronts own 16
+  // columns each, read all K columns of A a few K-tiles ahead and store without a barrier between them, so one of them
+  // could overwrite what another has yet to read.  Few rows then take the 128 x 128 kernel: the same bits.
   if (M <= 0 || N <= 0) return hipSuccess;
   const int Tm = (int)((M + GEMM_BM - 1) / GEMM_BM), Tn = (int)((N + GEMM_BN - 1) / GEMM_BN);
   const int total = Tm * Tn;
   const int grid = ((total + 7) / 8) * 8;
   const bool vec = (lda % 2 == 0) && (ldb % 2 == 0) && ((uintptr_t)A % 16 == 0) &&
                    ((uintptr_t)B % 16 == 0);
-  if (mode == 0 && vec && M <= 128) {  // a few rows: bandwidth-bound tail kernel, one wave per 16 columns
+  if (mode == 0 && vec && M <= 128 && !in_place) {  // a few rows: bandwidth-bound tail kernel, one wave per 16 columns
     const dim3 tg((unsigned)((N + 63) / 64));
     if (M <= 16)
       hipLaunchKernelGGL((gemm_nt_f64_tail_kernel<1, 6>), tg, dim3(256), 0, stream, M, N, K, A, lda, B, ldb, Cm, ldc,

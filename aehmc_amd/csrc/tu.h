@@ -16,7 +16,7 @@ namespace tu {
 hipError_t gemm_nt_f64(int64_t M, int64_t N, int64_t K, const double *A, int64_t lda, const double *B, int64_t ldb,
                        double *Cm, int64_t ldc, hipStream_t stream, const int *row_idx, const int *n_rows,
                        unsigned long long *flop_counter, const GemmStreamK *sk, int sk_grid, int mode, int sk_grid_wide,
-                       int small_tiles, int tri);
+                       int small_tiles, int tri, bool in_place);
 hipError_t gemm_streamk_occupancy(int *per_cu);
 // nuts_linreg.cuh, hmc_linreg.cuh
 hipError_t nuts_linreg(const EngineArgs &a, const NutsSampleArgs &m, hipStream_t st);
