@@ -29,6 +29,12 @@ class CAdaptState(ct.Structure):
                                                             ("work", ct.c_void_p)]
 
 
+class CPooledAdaptState(ct.Structure):
+    _fields_ = [(n, ct.c_void_p) for n in ("da_step", "da_x", "da_x_avg", "da_g_avg", "da_mu",
+                                           "wc_mean", "wc_m2", "wc_n", "step_size", "imm",
+                                           "sqrt_mass")] + [("full", ct.c_int32), ("reserved", ct.c_int32)]
+
+
 class CDiagnostics(ct.Structure):
     _fields_ = [("momentum", ct.c_void_p), ("acceptance_probability", ct.c_void_p),
                 ("num_doublings", ct.c_void_p), ("is_turning", ct.c_void_p),
@@ -54,6 +60,9 @@ SYMBOLS = {
     "aehmc_adapt_init": (_I, [_P, _I64, _I64, _D, ct.POINTER(CAdaptState), _P]),
     "aehmc_adapt_update": (_I, [_P, _I64, _I64, ct.c_int32, ct.c_int32, ct.c_int32, _D, _P, _P,
                                 ct.POINTER(CAdaptState), _P]),
+    "aehmc_pooled_adapt_init": (_I, [_P, _I64, _I64, _D, ct.POINTER(CPooledAdaptState), _P]),
+    "aehmc_pooled_adapt_update": (_I, [_P, _I64, _I64, ct.c_int32, ct.c_int32, ct.c_int32, _D, _P, _P,
+                                       ct.POINTER(CPooledAdaptState), _P]),
     "aehmc_dual_averaging_update": (_I, [_P, _I64, _D, _D, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aehmc_welford_update": (_I, [_P, _I64, _I64, ct.c_int32, _P, _P, _P, _P, _P]),
     "aehmc_covariance_final": (_I, [_P, _I64, _I64, ct.c_int32, ct.c_int32, _P, _P, _P, _P]),
@@ -77,6 +86,10 @@ SYMBOLS = {
                                ct.POINTER(CAdaptState), _P]),
     "aehmc_hmc_warmup": (_I, [_P, _I64, _P, _I64, _P, _P, _D, _I64, _D, _P, _P, _P, ct.POINTER(CDiagnostics),
                               ct.POINTER(CAdaptState), _P]),
+    "aehmc_nuts_warmup_pooled": (_I, [_P, _I64, _P, _I64, _P, _P, _D, _I64, _D, _P, _P, _P, ct.POINTER(CDiagnostics),
+                                      ct.POINTER(CPooledAdaptState), _P]),
+    "aehmc_hmc_warmup_pooled": (_I, [_P, _I64, _P, _I64, _P, _P, _D, _I64, _D, _P, _P, _P, ct.POINTER(CDiagnostics),
+                                     ct.POINTER(CPooledAdaptState), _P]),
     "aehmc_leapfrog": (_I, [_P, _I64, _D, _I64, _P, _P, _P, _P, _P]),
     "aehmc_kinetic_energy": (_I, [_P, _I64, _P, _P, _P]),
     "aehmc_is_turning": (_I, [_P, _I64, _P, _P, _P, _P, _P]),
@@ -84,6 +97,7 @@ SYMBOLS = {
     "aehmc_rng_bernoulli": (_I, [_P, _I64, _P, _I64, _P, _P, _P]),
     "aehmc_gemm_nt": (_I, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
     "aehmc_gemm_nt_tri": (_I, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _P, _P, _P]),
+    "aehmc_syrk_tn": (_I, [_P, _I64, _I64, _P, _I64, _P, _D, _P, _P, _I64, _P]),
     "aehmc_profile_enable": (_I, [_P, _I]),
     "aehmc_profile_read": (_I, [_P, ct.POINTER(_D), ct.POINTER(_I64), ct.POINTER(_D)]),
     "aehmc_synchronize": (_I, [_P, _P]),

@@ -25,6 +25,7 @@
 #include "nuts_resident.cuh"
 #include "nuts_wide.cuh"
 #include "nuts_pc_dense.cuh"
+#include "pooled_adapt.cuh"
 
 using namespace aehmc;
 
@@ -98,6 +99,10 @@ struct aehmc_ctx {
   size_t pc_work_bytes = 0;
   double *fd_ws = nullptr;  // small-dense kernels, per-chain metrics: the chains' transposed matrices (kept, grown)
   size_t fd_ws_bytes = 0;
+  double *pool_work = nullptr;  // pooled window adaptation: partial column sums, batch mean, delta (kept, grown)
+  size_t pool_work_bytes = 0;
+  double *syrk_work = nullptr;  // symmetric rank-C update of a mid-size D: the parts of the chain range (kept, grown)
+  size_t syrk_work_bytes = 0;
   double *blk_pack = nullptr;  // block-resident dense kernels: the launch's matrices zero-padded to [Dp][Dp] (kept, grown)
   size_t blk_pack_bytes = 0;
   // user-defined target (aehmc_set_custom_target): its source, the kernels compiled against it (hipRTC code objects
@@ -257,6 +262,8 @@ extern "C" int aehmc_destroy(aehmc_ctx *ctx) {
   if (ctx->pc_work) (void)hipFree(ctx->pc_work);
   if (ctx->fd_ws) (void)hipFree(ctx->fd_ws);
   if (ctx->blk_pack) (void)hipFree(ctx->blk_pack);
+  if (ctx->pool_work) (void)hipFree(ctx->pool_work);
+  if (ctx->syrk_work) (void)hipFree(ctx->syrk_work);
   if (ctx->d_cparams) (void)hipFree(ctx->d_cparams);
   if (ctx->glm_XT) (void)hipFree(ctx->glm_XT);
   if (ctx->glm_z) (void)hipFree(ctx->glm_z);
@@ -737,7 +744,10 @@ static int dense_cholesky(aehmc_ctx *ctx, double *Lw, int64_t D, double *inv, do
 // metrics.py:56-58: L = cholesky(imm); mass_matrix_sqrt = solve_triangular(L, I, lower, trans)
 // = L^-T.  Blocked (64-wide) right-looking Cholesky and blocked triangular inverse; the
 // O(D^3) work is in the fp64 MFMA GEMM.  `out` [D,D] receives L^-T.
-static int dense_sqrt_mass(aehmc_ctx *ctx, const double *imm, int64_t D, double *out, hipStream_t st) {
+// `pd_is_data`: a matrix that is not positive definite is no error -- `out` is filled with NaNs (pooled warm-up: an
+// estimate, as the per-chain warm-up kernel leaves them)
+static int dense_sqrt_mass(aehmc_ctx *ctx, const double *imm, int64_t D, double *out, hipStream_t st,
+                           bool pd_is_data = false) {
   const int NB = FACT_NB;
   double *Lw = nullptr, *Li = nullptr, *small = nullptr, *Tt = nullptr;
   int *info = nullptr;
@@ -783,6 +793,11 @@ static int dense_sqrt_mass(aehmc_ctx *ctx, const double *imm, int64_t D, double 
         hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
       ctx->err = "dense metric: factorisation kernels failed";
       rc = -1;
+    } else if (h_info && pd_is_data) {
+      if (hipMemsetAsync(out, 0xFF, (size_t)D * D * sizeof(double), st) != hipSuccess) {  // (all bits set: a NaN)
+        ctx->err = "dense metric: device fill failed";
+        rc = -1;
+      }
     } else if (h_info) {
       ctx->err = "dense inverse mass matrix is not positive definite (pivot " + std::to_string(h_info) + ")";
       rc = -2;
@@ -936,6 +951,79 @@ extern "C" int aehmc_adapt_update(aehmc_ctx *ctx, int64_t C, int64_t D, int32_t 
     hipLaunchKernelGGL(k_adapt_update, chain_grid(C), dim3(256), 0, (hipStream_t)stream, a);
   }
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- pooled window adaptation (pooled_adapt.cuh, syrk_f64.cuh) ----
+static int grow(aehmc_ctx *ctx, double **buf, size_t *have, size_t need) {
+  if (*have >= need) return 0;
+  if (*buf) HIPCHK(hipFree(*buf));
+  *buf = nullptr;
+  *have = 0;
+  HIPCHK(hipMalloc((void **)buf, need));
+  *have = need;
+  return 0;
+}
+static int pool_args(aehmc_ctx *ctx, int64_t C, int64_t D, const aehmc_pooled_adapt_state *s, PoolArgs &a) {
+  if (!s || C <= 0 || D <= 0) FAIL("pooled adaptation: bad arguments");
+  if (!s->da_step || !s->da_x || !s->da_x_avg || !s->da_g_avg || !s->da_mu || !s->wc_mean || !s->wc_m2 || !s->wc_n ||
+      !s->step_size || !s->imm || !s->sqrt_mass)
+    FAIL("pooled adaptation: state arrays missing");
+  memset(&a, 0, sizeof(a));
+  a.C = C; a.D = D; a.s = *s;
+  a.gamma = 0.05; a.t0 = 10; a.kappa = 0.75;  // step_size.py:9-14
+  pool_parts(C, D, a.P, a.rows_per);
+  if (int rc = grow(ctx, &ctx->pool_work, &ctx->pool_work_bytes, pool_work_doubles(C, D) * sizeof(double))) return rc;
+  a.part = ctx->pool_work;
+  a.b = a.part + (size_t)a.P * (D + 1);
+  a.delta = a.b + D;
+  a.sc = a.delta + D;
+  return 0;
+}
+static int syrk(aehmc_ctx *ctx, int64_t C, int64_t D, const double *X, int64_t ldx, const double *centre, double w,
+                const double *w_dev, const double *delta, double *S, int64_t lds_, hipStream_t st) {
+  if (int rc = grow(ctx, &ctx->syrk_work, &ctx->syrk_work_bytes, tu::syrk_partial_doubles(C, D) * sizeof(double)))
+    return rc;
+  HIPCHK(tu::syrk_tn(C, D, X, ldx, centre, w, w_dev, delta, S, lds_, ctx->syrk_work, st));
+  return 0;
+}
+extern "C" int aehmc_syrk_tn(aehmc_ctx *ctx, int64_t C, int64_t D, const double *X, int64_t ldx, const double *centre,
+                             double w, const double *delta, double *S, int64_t lds_, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (C <= 0 || D <= 0 || !X || !S || ldx < D || lds_ < D) FAIL("syrk_tn: bad arguments");
+  return syrk(ctx, C, D, X, ldx, centre, w, nullptr, delta, S, lds_, (hipStream_t)stream);
+}
+extern "C" int aehmc_pooled_adapt_init(aehmc_ctx *ctx, int64_t C, int64_t D, double initial_step_size,
+                                       const aehmc_pooled_adapt_state *state, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  PoolArgs a;
+  if (int rc = pool_args(ctx, C, D, state, a)) return rc;
+  HIPCHK(tu::pool_init(a, initial_step_size, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int aehmc_pooled_adapt_update(aehmc_ctx *ctx, int64_t C, int64_t D, int32_t stage, int32_t is_window_end,
+                                         int32_t is_last, double target, const double *p_accept,
+                                         const double *position, const aehmc_pooled_adapt_state *state, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  PoolArgs a;
+  if (int rc = pool_args(ctx, C, D, state, a)) return rc;
+  if (!p_accept || !position) FAIL("pooled adaptation: acceptance_probability / position missing");
+  if (is_window_end && stage == 0) FAIL("pooled adaptation: a window ends in a slow stage");
+  a.stage = stage; a.window_end = is_window_end; a.last = is_last; a.target = target;
+  a.p_accept = p_accept; a.position = position;
+  HIPCHK(tu::pool_sums(a, st));
+  if (state->full && stage != 0) {
+    if (int rc = syrk(ctx, C, D, position, D, a.b, 0.0, a.sc, a.delta, state->wc_m2, D, st)) return rc;
+    if (is_window_end) {
+      HIPCHK(tu::pool_imm(a, st));
+      if (int rc = dense_sqrt_mass(ctx, state->imm, D, state->sqrt_mass, st, true)) return rc;
+    }
+  }
+  HIPCHK(tu::pool_scalars(a, st));
   return 0;
 }
 
@@ -2468,6 +2556,68 @@ extern "C" int aehmc_hmc_warmup(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_
     if (int rc = aehmc_adapt_update(ctx, C, D, stage[i], is_window_end[i], i == num_steps - 1,
                                     target_acceptance_rate, out->acceptance_probability, q, state, stream))
       return rc;
+  }
+  return 0;
+}
+
+// window_adaptation.run(..., pooled=True): the transitions run with ONE shared metric and one step size (every entry of
+// state->step_size), on whatever route nuts_run / hmc_run give such a binding; the pooled update follows each
+static int pooled_bound(aehmc_ctx *ctx, int64_t C, const aehmc_pooled_adapt_state *state) {
+  if (!ctx->has_tgt || !ctx->has_met) FAIL("set_target and set_metric must be called first");
+  if (!ctx->eps_c || ctx->eps_n != C || ctx->met.per_chain)
+    FAIL("pooled warm-up needs the step sizes [C] of the adaptation state and a SHARED metric bound");
+  if (ctx->met.imm != state->imm || ctx->met.sqrt_mass != state->sqrt_mass || ctx->eps_c != state->step_size)
+    FAIL("pooled warm-up: the bound metric / step sizes are not the adaptation state's own arrays "
+         "(bind state->imm, state->sqrt_mass with aehmc_set_metric and state->step_size with aehmc_set_step_sizes)");
+  if ((ctx->met.ndim == 2) != (state->full != 0)) FAIL("pooled warm-up: the bound metric and state->full disagree");
+  return 0;
+}
+// after a window end: the same arrays, new content -- the engine drops what it derived from the old one
+static int pooled_rebind(aehmc_ctx *ctx) {
+  const aehmc_metric m = ctx->met;
+  return aehmc_set_metric(ctx, &m);
+}
+extern "C" int aehmc_nuts_warmup_pooled(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_t num_steps,
+                                        const int32_t *stage, const int32_t *is_window_end,
+                                        double target_acceptance_rate, int64_t max_num_expansions,
+                                        double divergence_threshold, double *q, double *U, double *g,
+                                        const aehmc_diagnostics *out, const aehmc_pooled_adapt_state *state,
+                                        void *stream) {
+  if (!ctx || !out || !state || !stage || !is_window_end) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = pooled_bound(ctx, C, state)) return rc;
+  const int64_t D = ctx->tgt.D;
+  for (int64_t i = 0; i < num_steps; i++) {
+    if (int rc = nuts_run(ctx, C, rng, 0.0, max_num_expansions, divergence_threshold, q, U, g, out,
+                          (hipStream_t)stream))
+      return rc;
+    if (int rc = aehmc_pooled_adapt_update(ctx, C, D, stage[i], is_window_end[i], i == num_steps - 1,
+                                           target_acceptance_rate, out->acceptance_probability, q, state, stream))
+      return rc;
+    if (is_window_end[i])
+      if (int rc = pooled_rebind(ctx)) return rc;
+  }
+  return 0;
+}
+extern "C" int aehmc_hmc_warmup_pooled(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_t num_steps,
+                                       const int32_t *stage, const int32_t *is_window_end,
+                                       double target_acceptance_rate, int64_t num_integration_steps,
+                                       double divergence_threshold, double *q, double *U, double *g,
+                                       const aehmc_diagnostics *out, const aehmc_pooled_adapt_state *state,
+                                       void *stream) {
+  if (!ctx || !out || !state || !stage || !is_window_end) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = pooled_bound(ctx, C, state)) return rc;
+  const int64_t D = ctx->tgt.D;
+  for (int64_t i = 0; i < num_steps; i++) {
+    if (int rc = hmc_run(ctx, C, rng, 0.0, num_integration_steps, divergence_threshold, 1, q, U, g, out, nullptr,
+                         nullptr, nullptr, (hipStream_t)stream))
+      return rc;
+    if (int rc = aehmc_pooled_adapt_update(ctx, C, D, stage[i], is_window_end[i], i == num_steps - 1,
+                                           target_acceptance_rate, out->acceptance_probability, q, state, stream))
+      return rc;
+    if (is_window_end[i])
+      if (int rc = pooled_rebind(ctx)) return rc;
   }
   return 0;
 }

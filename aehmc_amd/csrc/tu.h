@@ -11,6 +11,7 @@ struct EngineArgs;
 struct NutsSampleArgs;
 struct HmcFusedArgs;
 struct GemmStreamK;
+struct PoolArgs;
 namespace tu {
 // gemm_f64.cuh
 hipError_t gemm_nt_f64(int64_t M, int64_t N, int64_t K, const double *A, int64_t lda, const double *B, int64_t ldb,
@@ -52,5 +53,13 @@ hipError_t summary_lag_update(const double *x, long long T, long long C, long lo
                               long long K, int CG, double *shift, double *sums, double *ring, double *head,
                               double *prod, double *acov, hipStream_t st);
 int summary_lag_group(long long K);
+// syrk_f64.cuh, pooled_adapt.cuh
+hipError_t syrk_tn(long long C, long long D, const double *X, long long ldx, const double *centre, double w,
+                   const double *w_dev, const double *delta, double *S, long long lds, double *partial, hipStream_t st);
+size_t syrk_partial_doubles(long long C, long long D);
+hipError_t pool_init(const PoolArgs &a, double initial_step_size, hipStream_t st);
+hipError_t pool_sums(const PoolArgs &a, hipStream_t st);
+hipError_t pool_imm(const PoolArgs &a, hipStream_t st);
+hipError_t pool_scalars(const PoolArgs &a, hipStream_t st);
 }  // namespace tu
 }  // namespace aehmc

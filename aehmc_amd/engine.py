@@ -223,8 +223,9 @@ class Engine:
         self._target_key, self.D = key, D
         self._ws = None
 
-    def set_metric(self, inverse_mass_matrix, D: int, force: bool = False):
-        """gaussian_metric(inverse_mass_matrix) -- aehmc/metrics.py:44-63."""
+    def set_metric(self, inverse_mass_matrix, D: int, force: bool = False, sqrt_mass=None):
+        """gaussian_metric(inverse_mass_matrix) -- aehmc/metrics.py:44-63.  ``sqrt_mass``: the caller's own device array
+        of sqrt(1 / imm) / L^-T, bound instead of one computed here (pooled window adaptation keeps both up itself)."""
         imm = inverse_mass_matrix
         if isinstance(imm, PerChain):
             return self._set_metric_per_chain(imm, D)
@@ -254,11 +255,13 @@ class Engine:
                 t = t.reshape(-1)
                 if ndim == 1 and t.numel() != D:
                     raise ValueError(f"diagonal inverse mass matrix must have {D} entries")
-            # sqrt(1 / imm) / L^-T (metrics.py:45,49,56-58), once per metric content
-            sm = torch.empty_like(t)
-            self._check(self.lib.aehmc_metric_sqrt(self.ctx, ndim, D, t.data_ptr(), sm.data_ptr(), self.stream),
-                        "aehmc_metric_sqrt")
-            self.n_metric_factorizations += 1
+            if sqrt_mass is not None:
+                sm = sqrt_mass.reshape(t.shape)
+            else:  # sqrt(1 / imm) / L^-T (metrics.py:45,49,56-58), once per metric content
+                sm = torch.empty_like(t)
+                self._check(self.lib.aehmc_metric_sqrt(self.ctx, ndim, D, t.data_ptr(), sm.data_ptr(), self.stream),
+                            "aehmc_metric_sqrt")
+                self.n_metric_factorizations += 1
             handle = (imm, t, sm)  # (the caller's object too: a torch tensor's id() must stay taken while cached)
             self._metric_cache[key] = handle
             held = 0
@@ -602,6 +605,70 @@ class Engine:
         self._check(self.lib.aehmc_adapt_update(self.ctx, C, D, int(stage), int(window_end), int(last),
                                                 float(target), p_accept.data_ptr(), position.data_ptr(),
                                                 ct.byref(cstate), self.stream), "aehmc_adapt_update")
+
+    # ------------------------------------------------------------------ pooled warm-up
+    def pooled_adapt_alloc(self, C, D, full=False):
+        """The state of a pooled adaptation: one dual-averaging state, one Welford state, one metric; step_size [C]."""
+        dev, f64, i64 = self.device, torch.float64, torch.int64
+        mat = (D, D) if full else (D,)
+        st = dict(da_step=torch.empty(1, dtype=i64, device=dev), da_x=torch.empty(1, dtype=f64, device=dev),
+                  da_x_avg=torch.empty(1, dtype=f64, device=dev), da_g_avg=torch.empty(1, dtype=f64, device=dev),
+                  da_mu=torch.empty(1, dtype=f64, device=dev), wc_mean=torch.empty(D, dtype=f64, device=dev),
+                  wc_m2=torch.empty(mat, dtype=f64, device=dev), wc_n=torch.empty(1, dtype=i64, device=dev),
+                  step_size=torch.empty(C, dtype=f64, device=dev), imm=torch.empty(mat, dtype=f64, device=dev),
+                  sqrt_mass=torch.empty(mat, dtype=f64, device=dev))
+        return st, self.pooled_cstate(st, full)
+
+    @staticmethod
+    def pooled_cstate(st, full):
+        return _lib.CPooledAdaptState(full=int(bool(full)), **{k: v.data_ptr() for k, v in st.items()})
+
+    def pooled_adapt_init(self, C, D, initial_step_size, cstate):
+        self._check(self.lib.aehmc_pooled_adapt_init(self.ctx, C, D, float(initial_step_size), ct.byref(cstate),
+                                                     self.stream), "aehmc_pooled_adapt_init")
+
+    def pooled_adapt_update(self, C, D, stage, window_end, last, target, p_accept, position, cstate):
+        self._check(self.lib.aehmc_pooled_adapt_update(self.ctx, C, D, int(stage), int(window_end), int(last),
+                                                       float(target), p_accept.data_ptr(), position.data_ptr(),
+                                                       ct.byref(cstate), self.stream), "aehmc_pooled_adapt_update")
+
+    def syrk_tn(self, X, S, centre=None, w=0.0, delta=None):
+        """S[i, j] += sum_c (X[c, i] - centre[i]) (X[c, j] - centre[j]) + w delta[i] delta[j] for j <= i, in place
+        (aehmc_syrk_tn; elements above the diagonal are unspecified afterwards)."""
+        C, D = X.shape
+        self._check(self.lib.aehmc_syrk_tn(self.ctx, C, D, X.data_ptr(), X.stride(0),
+                                           centre.data_ptr() if centre is not None else None, float(w),
+                                           delta.data_ptr() if delta is not None else None, S.data_ptr(), S.stride(0),
+                                           self.stream), "aehmc_syrk_tn")
+        return S
+
+    def warmup_pooled(self, nuts, rng, schedule, target_accept, max_exp_or_L, thr, q, U, g, st, cstate, imm):
+        """The pooled window-adaptation loop in one C-ABI call: the state's own arrays bound as the SHARED metric and as
+        the step sizes, which the update kernels rewrite in place."""
+        C, D = q.shape
+        out, c = self._diag(C, D, nuts)
+        n = len(schedule)
+        stage = (ct.c_int32 * n)(*[int(s) for s, _ in schedule])
+        wend = (ct.c_int32 * n)(*[int(bool(e)) for _, e in schedule])
+        self.set_metric(imm, D, force=True, sqrt_mass=st["sqrt_mass"])
+        self.ensure_workspace(C, max_exp_or_L if nuts else 1)
+        self._keep["eps"] = st["step_size"]
+        self._check(self.lib.aehmc_set_step_sizes(self.ctx, st["step_size"].data_ptr(), C), "aehmc_set_step_sizes")
+        fn, what = ((self.lib.aehmc_nuts_warmup_pooled, "aehmc_nuts_warmup_pooled") if nuts else
+                    (self.lib.aehmc_hmc_warmup_pooled, "aehmc_hmc_warmup_pooled"))
+        try:
+            self._step_call(fn, what, self.ctx, C, rng.data_ptr(), n, stage, wend, float(target_accept),
+                            int(max_exp_or_L), float(thr), q.data_ptr(), U.data_ptr(), g.data_ptr(), ct.byref(c),
+                            ct.byref(cstate), self.stream)
+        finally:
+            self.forget_metric()
+        return out
+
+    def forget_metric(self):
+        """Drop the cache entry of the current shared-metric binding: its arrays were rewritten in place by a kernel
+        (which does not move a tensor's version counter), so the key no longer says what they hold."""
+        self._metric_cache.pop(self._metric_key, None)
+        self._metric_key = None
 
     def dual_averaging_update(self, target, gamma, t0, kappa, p_accept, step, x, x_avg, g_avg, mu, step_size_out):
         self._check(self.lib.aehmc_dual_averaging_update(

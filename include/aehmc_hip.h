@@ -104,6 +104,21 @@ typedef struct {
                                             factorisation (smaller D: LDS; may be NULL) */
 } aehmc_adapt_state;
 
+/* warm-up state of window_adaptation.run(..., pooled=True): ONE adaptation from all chains together -- one
+ * DualAveragingState, one Welford state, one inverse mass matrix (shared shapes); only step_size has a chain axis: the
+ * update writes the ONE step size into all C entries, the array aehmc_set_step_sizes binds */
+typedef struct {
+  int64_t *da_step;                      /* [1] */
+  double *da_x, *da_x_avg, *da_g_avg, *da_mu; /* [1] */
+  double *wc_mean, *wc_m2;               /* [D], [D] (diagonal adaptation) */
+  int64_t *wc_n;                         /* [1]: draws in the Welford state (a multiple of C) */
+  double *step_size;                     /* [C], all entries equal */
+  double *imm, *sqrt_mass;               /* [D] */
+  int32_t full;                          /* 1: is_mass_matrix_full -- wc_m2, imm and sqrt_mass are [D,D]; of wc_m2 only
+                                            the lower triangle is kept up (its upper one is unspecified) */
+  int32_t reserved;
+} aehmc_pooled_adapt_state;
+
 /* per-transition outputs == trajectory.py:379-384 Diagnostics (+ n_leapfrog) */
 typedef struct {
   double *momentum;               /* [C,D] Diagnostics.state.momentum */
@@ -335,6 +350,26 @@ int aehmc_adapt_update(aehmc_ctx *ctx, int64_t C, int64_t D, int32_t stage, int3
                        const double *acceptance_probability, const double *position,
                        const aehmc_adapt_state *state, void *stream);
 
+/* Pooled window adaptation: the same schedule, ONE adaptation from all chains.  One update, with
+ * the positions [C,D] and acceptance probabilities [C] after the transition:
+ *   abar = (sum_c a_c) / C goes through the dual-averaging update of aehmc_adapt_update (C = 1: its bits);
+ *   slow stage, batch Welford with b = (sum_c X_c) / C: n' = n + C, d = b - mean, mean' = mean + d (C / n'),
+ *     m2' = m2 + sum_c (X_c - b)(X_c - b)^T + (n C / n') d d^T (aehmc_syrk_tn; a diagonal metric keeps the diagonal);
+ *   window end: imm = (n / (n + 5)) m2 / (n - 1) + 1e-3 (5 / (n + 5)) [on the diagonal when full] with the pooled
+ *     count, written to BOTH triangles from the same value; sqrt_mass = sqrt(1 / imm) or chol(imm)^-T by the
+ *     machinery of aehmc_metric_sqrt on `stream` (a dense window end therefore waits for the stream; an estimate that
+ *     is not positive definite leaves NaNs in sqrt_mass and is not an error); Welford state zeroed, dual averaging
+ *     restarted; after the last step the step size is exp(x_avg).
+ * Sums over the chains run in an order fixed by (C, D) -- no floating-point atomics, two calls are bit-equal.  No D
+ * limit of its own; the ctx keeps the scratch.  A caller who samples with state->imm / state->sqrt_mass bound binds
+ * them again (aehmc_set_metric) after a window end: the engine derives operators from a bound matrix's content. */
+int aehmc_pooled_adapt_init(aehmc_ctx *ctx, int64_t C, int64_t D, double initial_step_size,
+                            const aehmc_pooled_adapt_state *state, void *stream);
+int aehmc_pooled_adapt_update(aehmc_ctx *ctx, int64_t C, int64_t D, int32_t stage, int32_t is_window_end,
+                              int32_t is_last, double target_acceptance_rate,
+                              const double *acceptance_probability, const double *position,
+                              const aehmc_pooled_adapt_state *state, void *stream);
+
 /* step_size.dual_averaging_adaptation(target, gamma, t0, kappa) -> update (step_size.py:9-100 over
  * algorithms.dual_averaging, algorithms.py:17-115) as a stand-alone building block around any kernel
  * (tests/test_step_size.py:13-88 wraps hmc.new_kernel with it): one update of the C per-chain states
@@ -440,6 +475,22 @@ int aehmc_hmc_warmup(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_t num_steps
                      double divergence_threshold, double *q, double *U, double *g, const aehmc_diagnostics *out,
                      const aehmc_adapt_state *state, void *stream);
 
+/* The same loops with POOLED adaptation: num_steps x (one transition, then aehmc_pooled_adapt_update), enqueued in
+ * one call.  Before the call the caller binds the SHARED metric to state->imm / state->sqrt_mass (aehmc_set_metric,
+ * per_chain = 0) and the step sizes to state->step_size (aehmc_set_step_sizes, n = C).  After a window end the loop
+ * binds the metric again, so that the engine drops what it derived from the old content (the whitened operator and
+ * its carry record).  The transitions take the shared-metric routes of aehmc_nuts_step / aehmc_hmc_step. */
+int aehmc_nuts_warmup_pooled(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_t num_steps, const int32_t *stage,
+                             const int32_t *is_window_end, double target_acceptance_rate,
+                             int64_t max_num_expansions, double divergence_threshold, double *q, double *U,
+                             double *g, const aehmc_diagnostics *out, const aehmc_pooled_adapt_state *state,
+                             void *stream);
+int aehmc_hmc_warmup_pooled(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_t num_steps, const int32_t *stage,
+                            const int32_t *is_window_end, double target_acceptance_rate,
+                            int64_t num_integration_steps, double divergence_threshold, double *q, double *U,
+                            double *g, const aehmc_diagnostics *out, const aehmc_pooled_adapt_state *state,
+                            void *stream);
+
 /* num_samples consecutive NUTS transitions per chain (the user-level scan of
  * tests/test_hmc.py:296-324); same optional outputs as aehmc_hmc_sample plus the per-chain
  * leapfrog total [C].  `out` describes the last transition.  (Regression target and register-resident
@@ -488,6 +539,14 @@ int aehmc_gemm_nt(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, const double 
 int aehmc_gemm_nt_tri(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, const double *A, int64_t lda,
                       const double *B, int64_t ldb, double *Cmat, int64_t ldc, int32_t tri, const int32_t *row_idx,
                       const int32_t *n_rows, void *stream);
+
+/* Symmetric rank-C update on the fp64 MFMA, X [C, ldx >= D] chain-major (the product X^T X, summed over the rows):
+ *   S[i,j] += sum_c (X[c,i] - centre[i]) (X[c,j] - centre[j]) + w delta[i] delta[j]     for j <= i
+ * (S [D, lds >= D] row-major; `centre` and `delta` [D] may be NULL: no centring / no rank-one term).  Only tiles on or
+ * below the diagonal are computed; elements strictly above the diagonal are unspecified after the call.  Chains are
+ * summed in ascending tiles of 16, a mid-size D in a fixed number of parts added in order: bit-equal between calls. */
+int aehmc_syrk_tn(aehmc_ctx *ctx, int64_t C, int64_t D, const double *X, int64_t ldx, const double *centre, double w,
+                  const double *delta, double *S, int64_t lds, void *stream);
 
 /* timing hooks for bench.py: HIP events (on the launch stream) around every launch of the
  * dominant kernel (fp64 GEMM, or the fused HMC kernel) since profile_enable(1), and the
