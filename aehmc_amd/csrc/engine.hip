@@ -6,6 +6,8 @@
 
 #include <unistd.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -1130,6 +1132,78 @@ extern "C" int aehmc_summary_lag_update(aehmc_ctx *ctx, int64_t T, int64_t C, in
   return 0;
 }
 extern "C" int64_t aehmc_summary_lag_group(int64_t K) { return K < 2 ? 0 : tu::summary_lag_group(K); }
+
+// Order statistics and quantiles of the stored draws (quantile.cuh): the same conventions -- caller-owned buffers only.
+static int quantile_shape(aehmc_ctx *ctx, const char *what, int64_t R, int64_t D, int64_t M, const void *samples,
+                          const void *host, const void *out, const void *work, int64_t work_bytes) {
+  if (R < 1 || D < 1 || M < 1 || !samples || !host || !out || !work) FAIL(std::string(what) + ": bad arguments");
+  if ((uintptr_t)work % 256) FAIL(std::string(what) + ": work must be 256-byte aligned");
+  if (R >= (int64_t)1 << 31) FAIL(std::string(what) + ": the counts are 32-bit, R must be below 2^31");
+  if (D >= (int64_t)1 << 31) FAIL(std::string(what) + ": D is too large");
+  if (M > AEHMC_SUMMARY_QUANTILE_MAX)
+    FAIL(std::string(what) + ": at most " + std::to_string(AEHMC_SUMMARY_QUANTILE_MAX) + " ranks or probabilities a call");
+  if (work_bytes < (int64_t)tu::quantile_work_bytes(D, M))
+    FAIL(std::string(what) + ": work holds " + std::to_string(work_bytes) + " bytes, aehmc_summary_quantile_work gives " +
+         std::to_string(tu::quantile_work_bytes(D, M)));
+  return 0;
+}
+// the distinct ranks, ascending, and for every entry of `want` its row among them
+static std::vector<long long> quantile_rows(const std::vector<long long> &want, std::vector<int> &row) {
+  std::vector<long long> u(want);
+  std::sort(u.begin(), u.end());
+  u.erase(std::unique(u.begin(), u.end()), u.end());
+  row.resize(want.size());
+  for (size_t i = 0; i < want.size(); ++i) row[i] = (int)(std::lower_bound(u.begin(), u.end(), want[i]) - u.begin());
+  return u;
+}
+extern "C" int64_t aehmc_summary_quantile_work(int64_t R, int64_t D, int64_t M) {
+  if (R < 1 || D < 1 || M < 1 || M > AEHMC_SUMMARY_QUANTILE_MAX || D >= (int64_t)1 << 31) return 0;
+  return (int64_t)tu::quantile_work_bytes(D, M);
+}
+extern "C" int aehmc_summary_order_stats(aehmc_ctx *ctx, int64_t R, int64_t D, int64_t M, const double *samples,
+                                         const int64_t *ranks, double *out, void *work, int64_t work_bytes,
+                                         void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = quantile_shape(ctx, "summary_order_stats", R, D, M, samples, ranks, out, work, work_bytes)) return rc;
+  std::vector<long long> want(M);
+  for (int64_t i = 0; i < M; ++i) {
+    if (ranks[i] < 0 || ranks[i] >= R)
+      FAIL("summary_order_stats: rank " + std::to_string(ranks[i]) + " is outside [0, " + std::to_string(R) + ")");
+    want[i] = ranks[i];
+  }
+  std::vector<int> row;
+  const std::vector<long long> u = quantile_rows(want, row);
+  HIPCHK(tu::quantile_stats(samples, R, D, (int)u.size(), u.data(), work, M, (hipStream_t)stream));
+  HIPCHK(tu::quantile_out(work, D, M, (int)M, row.data(), nullptr, nullptr, out, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int aehmc_summary_quantiles(aehmc_ctx *ctx, int64_t R, int64_t D, int64_t Q, const double *samples,
+                                       const double *probs, double *out, void *work, int64_t work_bytes, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = quantile_shape(ctx, "summary_quantiles", R, D, Q, samples, probs, out, work, work_bytes)) return rc;
+  std::vector<long long> want(2 * Q);
+  std::vector<double> g(Q);
+  for (int64_t i = 0; i < Q; ++i) {
+    const double p = probs[i];
+    if (!(p >= 0.0 && p <= 1.0)) FAIL("summary_quantiles: probability " + std::to_string(p) + " is outside [0, 1]");
+    const double h = p * (double)(R - 1), fl = std::floor(h);  // numpy's "linear" rule: virtual index, its floor, the gap
+    const long long lo = (long long)fl;
+    g[i] = h - fl;
+    want[2 * i] = lo;
+    want[2 * i + 1] = lo + 1 < R ? lo + 1 : R - 1;
+  }
+  std::vector<int> row, lo(Q), hi(Q);
+  const std::vector<long long> u = quantile_rows(want, row);
+  for (int64_t i = 0; i < Q; ++i) {
+    lo[i] = row[2 * i];
+    hi[i] = row[2 * i + 1];
+  }
+  HIPCHK(tu::quantile_stats(samples, R, D, (int)u.size(), u.data(), work, Q, (hipStream_t)stream));
+  HIPCHK(tu::quantile_out(work, D, Q, (int)Q, lo.data(), hi.data(), g.data(), out, (hipStream_t)stream));
+  return 0;
+}
 
 extern "C" int aehmc_set_option(aehmc_ctx *ctx, const char *name, int64_t value) {
   if (!ctx || !name) return -2;

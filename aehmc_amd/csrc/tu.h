@@ -53,6 +53,12 @@ hipError_t summary_lag_update(const double *x, long long T, long long C, long lo
                               long long K, int CG, double *shift, double *sums, double *ring, double *head,
                               double *prod, double *acov, hipStream_t st);
 int summary_lag_group(long long K);
+// quantile.cuh (work: the caller's scratch of quantile_work_bytes(D, M); the statistics land in its stats rows)
+size_t quantile_work_bytes(long long D, long long M);
+hipError_t quantile_stats(const double *x, long long R, long long D, int U, const long long *ranks, void *work,
+                          long long M, hipStream_t st);
+hipError_t quantile_out(void *work, long long D, long long M, int n, const int *lo, const int *hi, const double *g,
+                        double *out, hipStream_t st);  // rows lo of the statistics; with g, interpolated towards rows hi
 // syrk_f64.cuh, pooled_adapt.cuh
 hipError_t syrk_tn(long long C, long long D, const double *X, long long ldx, const double *centre, double w,
                    const double *w_dev, const double *delta, double *S, long long lds, double *partial, hipStream_t st);

@@ -740,6 +740,35 @@ class Engine:
                     "aehmc_summary_final")
         return out, trunc
 
+    def _quantile_work(self, R, D, M):
+        nbytes = int(self.lib.aehmc_summary_quantile_work(int(R), int(D), int(M)))
+        if nbytes <= 0:
+            raise EngineError(f"aehmc_summary_quantile_work: no scratch size for R = {R}, D = {D}, M = {M} (1 <= R < 2^31, "
+                              "at most 64 ranks or probabilities a call)")
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
+    def summary_order_stats(self, samples, ranks):
+        """out [M, D]: the ranks[i]-th smallest (0-based) value of every coordinate of samples [R, D]."""
+        R, D = samples.shape
+        M = len(ranks)
+        work = self._quantile_work(R, D, M)
+        out = torch.empty(M, D, dtype=torch.float64, device=self.device)
+        self._check(self.lib.aehmc_summary_order_stats(self.ctx, R, D, M, samples.data_ptr(), (ct.c_int64 * M)(*ranks),
+                                                       out.data_ptr(), work.data_ptr(), work.numel(), self.stream),
+                    "aehmc_summary_order_stats")
+        return out
+
+    def summary_quantiles(self, samples, probs):
+        """out [Q, D]: the quantiles (numpy's "linear" rule) of every coordinate of samples [R, D] at probs."""
+        R, D = samples.shape
+        Q = len(probs)
+        work = self._quantile_work(R, D, Q)
+        out = torch.empty(Q, D, dtype=torch.float64, device=self.device)
+        self._check(self.lib.aehmc_summary_quantiles(self.ctx, R, D, Q, samples.data_ptr(), (ct.c_double * Q)(*probs),
+                                                     out.data_ptr(), work.data_ptr(), work.numel(), self.stream),
+                    "aehmc_summary_quantiles")
+        return out
+
     def profile_enable(self, on=True):
         self._check(self.lib.aehmc_profile_enable(self.ctx, int(on)), "aehmc_profile_enable")
 

@@ -18,9 +18,15 @@ Two families of estimators per coordinate, with n draws per (split) chain and m 
   first draw, over a ring of the last ``max_lag`` draws, centred when a segment ends -- the quantity of
   ``summarize(samples, max_lag=...)`` to rounding, for a run of any length.
 
+Next to them, from the stored draws and with the chains pooled: exact ``quantiles`` (numpy's default "linear" rule),
+``median``, equal-tailed ``interval``, the raw ``order_statistics`` (a radix select per coordinate, csrc/quantile.cuh:
+no sort) and Stan's ``tail_ess``.
+
 fp64, deterministic: two calls on the same draws, and any chunking of them, give the same bits.  No CPU fallback."""
 from __future__ import annotations
 
+import math
+import operator
 from typing import NamedTuple, Optional
 
 import torch
@@ -32,6 +38,8 @@ from .engine import get_engine
 MAX_ACOV_ROWS = 8192
 # summary.run(chunk=None): the draw buffer of a chunk stays under this many bytes (at least one draw)
 CHUNK_BYTES = 1 << 30
+# aehmc_hip.h: AEHMC_SUMMARY_QUANTILE_MAX -- ranks of one order_statistics call, probabilities of one quantiles call
+MAX_QUANTILES = 64
 
 
 class Summary(NamedTuple):
@@ -142,6 +150,22 @@ class Accumulator:
                        num_draws=self.num_draws, num_chains=self.num_chains)
 
 
+def _check_acov_length(N, split, max_lag):
+    """The number of lags K of ``summarize`` at N draws, or its ValueError where the autocovariance kernel cannot hold
+    them."""
+    n = N // 2 if split else N
+    if max_lag is not None and int(max_lag) < 1:
+        raise ValueError("max_lag must be at least 1")
+    K = n if max_lag is None else min(int(max_lag) + 1, n)
+    if n + K > MAX_ACOV_ROWS:
+        fits = (f"max_lag <= {MAX_ACOV_ROWS - n - 1} fits at this length" if n <= MAX_ACOV_ROWS - 2 else
+                f"no max_lag fits segments above {MAX_ACOV_ROWS - 2} draws")
+        raise ValueError(f"the autocovariance kernel holds segment length + lags <= {MAX_ACOV_ROWS}: {N} draws give "
+                         f"segments of {n} draws with {K} lags ({fits}); summary.Accumulator gives the cross-chain "
+                         "estimators at any length")
+    return K
+
+
 def summarize(samples, *, batched: bool = True, split: bool = True, max_lag: Optional[int] = None) -> Summary:
     """Summary of stored draws ``samples`` [N, ...] as ``kernel.sample`` returns them: [N, C] or [N, C, D] with
     ``batched`` (a leading chain axis, the default), [N] or [N, D] for one chain.  ``split``: every chain counts as
@@ -156,16 +180,7 @@ def summarize(samples, *, batched: bool = True, split: bool = True, max_lag: Opt
     C = samples.shape[1] if batched else 1
     shape = tuple(samples.shape[lo:])
     N, C, shape = _check_run(N, C, shape, split)
-    n = N // 2 if split else N
-    if max_lag is not None and int(max_lag) < 1:
-        raise ValueError("max_lag must be at least 1")
-    K = n if max_lag is None else min(int(max_lag) + 1, n)
-    if n + K > MAX_ACOV_ROWS:
-        fits = (f"max_lag <= {MAX_ACOV_ROWS - n - 1} fits at this length" if n <= MAX_ACOV_ROWS - 2 else
-                f"no max_lag fits segments above {MAX_ACOV_ROWS - 2} draws")
-        raise ValueError(f"the autocovariance kernel holds segment length + lags <= {MAX_ACOV_ROWS}: {N} draws give "
-                         f"segments of {n} draws with {K} lags ({fits}); summary.Accumulator gives the cross-chain "
-                         "estimators at any length")
+    K = _check_acov_length(N, split, max_lag)
     acc = Accumulator(N, C, shape, split)  # (moments only: the autocovariance comes from the stored draws)
     x = acc._rows(samples, "samples")
     acc._fold(x)
@@ -183,6 +198,106 @@ def ess(samples, **kw):
 
 def mcse(samples, **kw):
     return summarize(samples, **kw).mcse
+
+
+def _pooled(samples, batched):
+    """samples as ``summarize`` takes them -> (the draws of all chains as rows [R, D], a coordinate's shape)."""
+    _check_draws(samples, "samples")
+    lo = 2 if batched else 1
+    if samples.ndim not in (lo, lo + 1):
+        raise ValueError(f"samples must be [N, C] or [N, C, D] (batched) or [N] / [N, D], got {tuple(samples.shape)}")
+    shape = tuple(samples.shape[lo:])
+    R = samples.shape[0] * (samples.shape[1] if batched else 1)
+    D = shape[0] if shape else 1
+    if R < 1 or D < 1:
+        raise ValueError(f"samples must hold at least one draw of at least one coordinate, got {tuple(samples.shape)}")
+    if R >= 1 << 31:
+        raise ValueError(f"the selection counts in 32 bits: {R} pooled draws are not below 2^31")
+    return samples.reshape(R, D), shape
+
+
+def _check_probs(probs):
+    scalar = isinstance(probs, (int, float)) and not isinstance(probs, bool)
+    try:
+        p = [float(probs)] if scalar else [float(v) for v in probs]
+    except (TypeError, ValueError):
+        raise ValueError(f"probs must be a float or a sequence of floats, got {probs!r}") from None
+    if not p:
+        raise ValueError("probs must not be empty")
+    if len(p) > MAX_QUANTILES:
+        raise ValueError(f"at most {MAX_QUANTILES} probs a call, got {len(p)}")
+    for v in p:
+        if not (math.isfinite(v) and 0.0 <= v <= 1.0):
+            raise ValueError(f"probs must be finite and within [0, 1], got {v}")
+    return p, scalar
+
+
+def _on_device(eng, x):
+    if x.device != eng.device:
+        raise ValueError(f"samples must be on {eng.device}, they are on {x.device}")
+
+
+def quantiles(samples, probs, *, batched: bool = True):
+    """Quantiles of stored draws at ``probs`` (a float or a sequence of floats in [0, 1]), per coordinate, the chains
+    pooled as the mean and sd of ``Summary`` are: a device tensor [Q, *shape], or ``shape`` for a scalar ``probs``.
+    ``samples`` as ``summarize`` takes them.  Exact: numpy's default "linear" rule (R type 7) between the two
+    neighbouring order statistics, which a radix select finds without sorting; a coordinate with a NaN gives NaN."""
+    x, shape = _pooled(samples, batched)
+    p, scalar = _check_probs(probs)
+    eng = get_engine()
+    _on_device(eng, x)
+    out = eng.summary_quantiles(x, p)
+    return out[0].reshape(shape) if scalar else out.reshape((len(p),) + shape)
+
+
+def median(samples, **kw):
+    return quantiles(samples, 0.5, **kw)
+
+
+def interval(samples, prob: float = 0.9, **kw):
+    """``(lower, upper)``: the equal-tailed interval of mass ``prob``, the quantiles at (1 - prob) / 2 and
+    (1 + prob) / 2."""
+    (prob,), _ = _check_probs(prob)
+    q = quantiles(samples, ((1.0 - prob) / 2.0, (1.0 + prob) / 2.0), **kw)
+    return q[0], q[1]
+
+
+def order_statistics(samples, ranks, *, batched: bool = True):
+    """The ``ranks``-th smallest (0-based ints, any order) of the pooled draws of every coordinate: [M, *shape], the
+    bits of ``sort(draws)[ranks]``."""
+    x, shape = _pooled(samples, batched)
+    try:
+        r = [operator.index(v) for v in ranks]
+    except TypeError:
+        raise ValueError(f"ranks must be a sequence of integers, got {ranks!r}") from None
+    if not r:
+        raise ValueError("ranks must not be empty")
+    if len(r) > MAX_QUANTILES:
+        raise ValueError(f"at most {MAX_QUANTILES} ranks a call, got {len(r)}")
+    for v in r:
+        if not 0 <= v < x.shape[0]:
+            raise ValueError(f"ranks must be within [0, {x.shape[0]}), got {v}")
+    eng = get_engine()
+    _on_device(eng, x)
+    return eng.summary_order_stats(x, r).reshape((len(r),) + shape)
+
+
+def tail_ess(samples, *, batched: bool = True, prob: float = 0.05, max_lag: Optional[int] = None):
+    """Stan's tail ESS: the smaller of the split-chain ``ess`` of the indicators ``x <= q`` at the ``prob`` and the
+    ``1 - prob`` quantile of the pooled draws.  Allocates one indicator array the size of ``samples`` at a time.
+    ``summarize``'s length limit (``MAX_ACOV_ROWS``) applies."""
+    _pooled(samples, batched)
+    (prob,), _ = _check_probs(prob)
+    lo = 2 if batched else 1
+    _check_run(samples.shape[0], samples.shape[1] if batched else 1, samples.shape[lo:], True)
+    _check_acov_length(samples.shape[0], True, max_lag)
+    view = (2,) + (1,) * (lo - 1) + tuple(samples.shape[lo:])  # (a coordinate's quantile against all its draws)
+    q = quantiles(samples, (prob, 1.0 - prob), batched=batched).reshape(view)
+    out = None
+    for i in range(2):
+        e = summarize((samples <= q[i]).to(torch.float64), batched=batched, split=True, max_lag=max_lag).ess
+        out = e if out is None else torch.minimum(out, e)
+    return out
 
 
 def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_integration_steps=None,

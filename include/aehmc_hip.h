@@ -451,6 +451,39 @@ int aehmc_summary_lag_update(aehmc_ctx *ctx, int64_t T, int64_t C, int64_t D, in
                              double *ring, double *head, double *work, double *acov, void *stream);
 int64_t aehmc_summary_lag_group(int64_t K);
 
+/* ---- order statistics and quantiles of the stored draws (aehmc_amd/summary.py) ----
+ * What the reference's users take from arviz on the host (the 5 % / 50 % / 95 % columns of a posterior table), on the
+ * device and without a sort: samples [R, D] is the [num_draws, C, D] array of the sampling calls viewed flat, R = N C
+ * rows (chains pooled, as the mean and sd of `final` are), 1 <= R < 2^31.  Every double maps to a 64-bit key monotone
+ * in its value (negatives: all bits flipped; non-negatives: sign bit set; -0.0 sorts just below +0.0), and the key of
+ * the k-th smallest value of a coordinate is found digit by digit, most significant first: 8 passes of 8 bits, each a
+ * histogram of the keys that still match the digits found so far, a scan, and the choice of the next digit.  Up to 8
+ * ranks share a sweep of 8 passes (a key is counted once however many ranks it still matches), more ranks take
+ * ceil(distinct ranks / 8) sweeps: bytes read = sweeps * 8 * R * D * 8.  Counts are integers (LDS and global integer
+ * atomics: the result does not depend on the order of arrival), fp64 selection is exact: the result is the bits of
+ * np.sort(samples, axis=0)[rank], and two calls on the same input are bit-equal.  A coordinate that holds a NaN gives
+ * NaN for every rank and probability (numpy.quantile does); -inf and +inf are ordinary values.  All buffers are the
+ * caller's; none of these calls touches the workspace, the target or the metric.
+ *
+ * quantile_work: the bytes of scratch `work` (device, 256-byte aligned) that a call with M ranks, or M probabilities,
+ * needs at these shapes; 0 for shapes the calls refuse.  A misaligned `work` is refused with an error code.
+ *
+ * order_stats: out [M, D], out[i] = the ranks[i]-th smallest (0-based) value of every coordinate.  `ranks` is a HOST
+ * array of M values in [0, R), in any order, repeats allowed; M <= AEHMC_SUMMARY_QUANTILE_MAX.
+ *
+ * quantiles: out [Q, D], the quantile at probs[i] by numpy's default "linear" rule (R type 7), evaluated in fp64 on the
+ * device: h = p (R - 1), lo = floor(h), g = h - lo, a = x_(lo), b = x_(min(lo + 1, R - 1)), d = b - a,
+ * q = a + d g if g < 0.5, else b - d (1 - g) (unfused: the bits of numpy.quantile's own formula).  `probs` is a HOST
+ * array of Q values in [0, 1]; Q <= AEHMC_SUMMARY_QUANTILE_MAX.  The two ranks of a probability are neighbours and
+ * share their counters until their keys part, so Q probabilities cost ceil(distinct ranks / 8) sweeps, at most
+ * ceil(Q / 4). */
+#define AEHMC_SUMMARY_QUANTILE_MAX 64
+int64_t aehmc_summary_quantile_work(int64_t R, int64_t D, int64_t M);
+int aehmc_summary_order_stats(aehmc_ctx *ctx, int64_t R, int64_t D, int64_t M, const double *samples,
+                              const int64_t *ranks, double *out, void *work, int64_t work_bytes, void *stream);
+int aehmc_summary_quantiles(aehmc_ctx *ctx, int64_t R, int64_t D, int64_t Q, const double *samples,
+                            const double *probs, double *out, void *work, int64_t work_bytes, void *stream);
+
 /* window_adaptation.run (window_adaptation.py:17-116) for a NUTS kernel: num_steps x (one transition
  * with the current per-chain parameters, then aehmc_adapt_update), enqueued in one call.  `stage` /
  * `is_window_end` [num_steps] are HOST arrays from build_schedule.  Before the call the caller binds
