@@ -659,11 +659,31 @@ class Traced:
 
 
 class _Gen:
-    def __init__(self, elem_var=None, scalar=False):
+    def __init__(self, elem_var=None, scalar=False, acc="s"):
         self.lines, self.ind, self.ntmp = [], 1, 0
         self.names = {}            # loop variable -> C++ name
         self.elem_var, self.scalar = elem_var, scalar
         self.par_local = None
+        self.acc = acc             # prefix of the reductions' accumulators
+        self.uses, self.env, self.nshared = {}, {}, 0
+        self.pre, self.top = [], {}  # statements ahead of all others: reductions over captured arrays alone, met inside a loop
+
+    def count_uses(self, root):
+        """how many parents every inner node has: the recorded expression is a DAG (a named reduction used twice, the
+        running maximum of logsumexp), and a node with several parents is emitted ONCE per scope, as a named temporary"""
+        def go(e):
+            if not isinstance(e, S) or e.op in ("const", "par", "q", "ref"):
+                return
+            self.uses[id(e)] = self.uses.get(id(e), 0) + 1
+            if self.uses[id(e)] > 1:
+                return
+            for x in e.args[:3]:
+                go(x)
+            if e.op == "sum":
+                for _, x in (e.args[3] if len(e.args) > 3 else ()):
+                    go(x)
+
+        go(root)
 
     def put(self, s):
         self.lines.append("  " * self.ind + s)
@@ -680,6 +700,28 @@ class _Gen:
         return f"q[{idx.code(self.names, self.par)}]"
 
     def ex(self, e):
+        """the value of e as a C++ expression (statements it needs -- loops, temporaries -- are put before it)"""
+        if id(e) in self.env:  # (a shared node or a reduction: named already in this scope)
+            return self.env[id(e)]
+        if e.op == "sum" and not e.t and self.ind > 1 and not _free_vars(e):
+            # y.mean() of an `args=` array inside a loop over the coordinates: once, ahead of everything
+            if id(e) not in self.top:
+                here = self.lines, self.ind, self.env
+                self.lines, self.ind, self.env = self.pre, 1, {}
+                self.top[id(e)] = self.ex1(e)
+                self.lines, self.ind, self.env = here
+            return self.top[id(e)]
+        r = self.ex1(e)
+        if e.op == "sum":  # (its accumulator is its name: a reduction used twice is ONE loop)
+            self.env[id(e)] = r
+        elif e.t and self.uses.get(id(e), 1) > 1 and e.op not in ("q", "ref"):
+            name = f"n{self.nshared}"
+            self.nshared += 1
+            self.put(f"const bool {name} = {r};" if e.b else f"const T {name} = T({r});")
+            self.env[id(e)] = r = name
+        return r
+
+    def ex1(self, e):
         op, a = e.op, e.args
         if op == "const":
             return _lit(a[0])
@@ -712,14 +754,16 @@ class _Gen:
             v, n, body = a[:3]
             for k, x in (a[3] if len(a) > 3 else ()):  # loop-invariant sub-expressions (tracing._hoist): once, before the loop
                 self.put(f"const T h{k} = T({self.ex(x)});")
-            acc = f"s{self.ntmp}"
+            acc = f"{self.acc}{self.ntmp}"
             self.ntmp += 1
             iv = f"i{v}"
             self.names[v] = iv
             self.put(f"{'T' if e.t else 'double'} {acc} = {'T(0.0)' if e.t else '0.0'};")
             self.put(f"for (int {iv} = 0; {iv} < {n}; {iv}++) {{")
             self.ind += 1
+            outer, self.env = self.env, dict(self.env)  # (what is named inside the loop is named for its body only)
             b = self.ex(body)
+            self.env = outer
             self.put(f"{acc} += {b};")
             self.ind -= 1
             self.put("}")
@@ -733,15 +777,19 @@ def _elementwise_var(root, dim, scalar):
     if scalar or root.op != "sum" or root.args[1] != dim:
         return None
     v = root.args[0]
+    seen = {}  # (the expression is a DAG: every node once)
 
     def ok(e):
-        if e.op == "q":
-            return e.args[0].is_var(v)
-        if e.op == "par":
-            return e.args[1].terms in ((), ((v, 1),)) and not e.args[1].ind
-        if e.op == "sum":
-            return False
-        return all(ok(x) for x in e.args if isinstance(x, S))
+        if id(e) not in seen:
+            if e.op == "q":
+                seen[id(e)] = e.args[0].is_var(v)
+            elif e.op == "par":
+                seen[id(e)] = e.args[1].terms in ((), ((v, 1),)) and not e.args[1].ind
+            elif e.op == "sum":
+                seen[id(e)] = False
+            else:
+                seen[id(e)] = all(ok(x) for x in e.args if isinstance(x, S))
+        return seen[id(e)]
 
     return v if ok(root.args[2]) else None
 
@@ -758,7 +806,10 @@ def _elementwise_var(root, dim, scalar):
 #     the 64 lanes (i = lane, lane + 64, ...): partial sums and the accumulators of hoisted values are reduced across the
 #     wavefront behind the loop (a xor butterfly: every lane ends with the same bits), the gradient entries written by
 #     the lane that owns the iteration -- O(dim / 64) per gradient;
-#   * everything else runs on all lanes alike (same values), lane 0 adding to the gradient row.
+#   * everything else runs on all lanes alike (same values), lane 0 adding to the gradient row;
+#   * a node with several parents (z = X @ q used twice, a reduction that is named and used again) has its adjoint
+#     collected from all of them and is propagated once, behind the last -- unless a parent sits in a `where` branch: then
+#     it is propagated per use (count_uses), a sum swept once per use under accumulator names of that sweep.
 _UN_BWD = {"exp": "{a} * {v}", "log": "{a} / {x}", "log1p": "{a} / (1.0 + {x})", "expm1": "{a} * exp({x})",
            "sqrt": "0.5 * {a} / {v}", "sin": "{a} * cos({x})", "cos": "-({a} * sin({x}))", "tanh": "{a} * (1.0 - {v} * {v})",
            "fabs": "({x} < 0 ? -{a} : {a})", "erf": "{a} * 1.1283791670955126 * exp(-{x} * {x})",
@@ -770,21 +821,25 @@ _UN_BWD = {"exp": "{a} * {v}", "log": "{a} / {x}", "log1p": "{a} / (1.0 + {x})",
 _REV_FN = {"square": "aehmc_sq", "softplus": "aehmc_softplus", "log": "aehmc::ad::log_fast", "log1p": "aehmc::ad::log1p_fast", "lgamma": "aehmc::ad::lgamma_fast"}
 
 
-def _free_vars(e):
+def _free_vars(e, memo=None):
     """loop variables an expression reads (those of sums inside it are bound there)"""
+    memo = {} if memo is None else memo  # (the expression is a DAG: every node once)
+    if id(e) in memo:
+        return memo[id(e)]
     if e.op in ("q",):
-        return e.args[0].vars()
-    if e.op == "par":
-        return e.args[1].vars()
-    if e.op == "sum":
-        inner = _free_vars(e.args[2]) - {e.args[0]}
+        out = e.args[0].vars()
+    elif e.op == "par":
+        out = e.args[1].vars()
+    elif e.op == "sum":
+        out = _free_vars(e.args[2], memo) - {e.args[0]}
         for _, x in (e.args[3] if len(e.args) > 3 else ()):
-            inner |= _free_vars(x)
-        return inner
-    out = frozenset()
-    for x in e.args:
-        if isinstance(x, S):
-            out |= _free_vars(x)
+            out |= _free_vars(x, memo)
+    else:
+        out = frozenset()
+        for x in e.args:
+            if isinstance(x, S):
+                out |= _free_vars(x, memo)
+    memo[id(e)] = out
     return out
 
 
@@ -800,8 +855,10 @@ def _hoist(e, counter, memo=None):
         local = {}
 
         def go(x):
-            if not isinstance(x, S) or not x.t:
+            if not isinstance(x, S):
                 return x
+            if not x.t:  # (captured arrays and numbers only: stays where it is; sums inside it gain their empty fourth argument)
+                return _hoist(x, counter, memo)
             if id(x) in local:
                 return local[id(x)]
             if x.op != "ref" and v not in _free_vars(x):
@@ -839,8 +896,15 @@ def _private_leaves(e):
     reduced over the wavefront behind the loop.  None if some read fits neither this form nor a * i + c."""
     v = e.args[0]
     out = {}
+    seen = {}
 
     def walk(x, inner):
+        key = (id(x), tuple(sorted(inner)))
+        if key not in seen:
+            seen[key] = walk1(x, inner)
+        return seen[key]
+
+    def walk1(x, inner):
         if x.op == "q":
             t = x.args[0].terms
             if x.args[0].ind:  # a gather: added atomically
@@ -866,8 +930,12 @@ def _mixed_owners(e):
     entry and the additions are atomic."""
     v = e.args[0]
     maps = set()
+    seen = set()
 
     def walk(x):
+        if id(x) in seen:
+            return
+        seen.add(id(x))
         if x.op == "q":
             t = x.args[0].terms
             if not x.args[0].ind and len(t) == 1 and t[0][0] == v:
@@ -916,7 +984,11 @@ class _RevGen:
         self.spine, self.done = spine or {}, set()
         self.used_params = set()
         self.warned = set()
-        self.uses, self.cond = {}, set()
+        self.uses, self.cond, self.counted = {}, set(), False
+        self.ah, self.ah_n = {}, {}  # hoisted value k -> the name of its adjoint accumulator in the sweep being written
+        self.swept = set()    # ids of sums whose backward loop has been written once already
+        self.pre = []         # statements ahead of everything else: reductions over captured arrays alone
+        self.cgen, self.cnames = None, {}
         self.private = {}     # id(q leaf) -> (accumulator array, inner sum node)
         self.unrolled = set()  # ids of inner sums whose loops are written out (their accumulator arrays stay in registers)
 
@@ -946,11 +1018,8 @@ class _RevGen:
             return f"q[{a[0].code(self.names, self.par)}]"
         if op == "ref":
             return env[("let", a[0])]
-        if not e.t and op != "sum":  # parameters and constants only: inlined
-            g = _Gen()
-            g.names = self.names
-            g.par_local = self.used_params
-            return g.ex(e)
+        if not e.t and (op != "sum" or self.depth > 0):  # parameters and constants only: inlined
+            return self.const_expr(e)
         if op == "neg":
             r = f"(-{self.fwd(a[0], env)})"
         elif op == "un":
@@ -972,6 +1041,40 @@ class _RevGen:
         env[id(e)] = name
         return name
 
+    def const_expr(self, e):
+        """an expression over captured arrays and numbers: inlined; a reduction inside it (y.mean() of an `args=` array) is
+        a loop of its own -- ahead of the whole program when it reads no loop variable, else where it is needed"""
+        if id(e) in self.cnames:
+            return self.cnames[id(e)]
+        if self.cgen is None:
+            self.cgen = _Gen(acc="c")
+            self.cgen.names = self.names
+            self.cgen.par_local = self.used_params
+        g = self.cgen
+        invariant = not _free_vars(e)
+        g.ind, g.env = (1 if invariant else self.ind), {}
+        r = g.ex(e)
+        self.pre += g.pre  # (reductions inside it that read no loop variable)
+        g.pre = []
+        if g.lines:
+            if invariant:
+                name = f"c{g.ntmp}"
+                g.ntmp += 1
+                self.pre += g.lines + [f"  const double {name} = {r};"]
+                self.cnames[id(e)] = r = name
+            else:
+                self.lines += g.lines
+            g.lines = []
+        return r
+
+    def ah_new(self, k):
+        """a fresh name for the adjoint accumulator of hoisted value k (a sum that is swept more than once -- a shared
+        sum used in a `where` branch -- declares its accumulators once per sweep)"""
+        c = self.ah_n.get(k, 0)
+        self.ah_n[k] = c + 1
+        self.ah[k] = f"ah{k}" if c == 0 else f"ah{k}_{c}"
+        return self.ah[k]
+
     def loop_head(self, e, dist):
         v, n = e.args[0], e.args[1]
         iv = f"i{v}"
@@ -986,11 +1089,16 @@ class _RevGen:
         self.used_params.add(k)
         return f"prm{k}"
 
-    def has_inner_sum(self, e):
-        return isinstance(e, S) and (e.op == "sum" or any(self.has_inner_sum(x) for x in e.args if isinstance(x, S)))
+    def has_inner_sum(self, e, seen=None):
+        seen = set() if seen is None else seen
+        if not isinstance(e, S) or id(e) in seen:
+            return False
+        seen.add(id(e))
+        return e.op == "sum" or any(self.has_inner_sum(x, seen) for x in e.args)
 
     def fwd_sum(self, e, env):
         v, n, body, lets = e.args
+        assert self.counted, "count_uses runs before the first sum is written: the fusion below reads it"
         dist = self.depth == 0 and _distributable(e)
         if self.depth == 0 and not dist and n >= 1024 and id(e) not in self.warned:
             self.warned.add(id(e))
@@ -1005,12 +1113,15 @@ class _RevGen:
         acc = self.tmp("s")
         self.put(f"double {acc} = 0.0;")
         # a sum on the additive spine of the density (log-density = term + term + ...) has the adjoint +1 / -1 whatever the
-        # other terms are: its backward sweep rides in the forward loop -- one pass over the data instead of two
-        fused = self.spine.get(id(e)) if self.depth == 0 else None
+        # other terms are: its backward sweep rides in the forward loop -- one pass over the data instead of two.  Only
+        # when the spine is its ONE use that carries an adjoint: a sum that is named and used again (s - log(s), a sum in a
+        # `where` branch) has more adjoint coming than the literal, and takes the ordinary backward route with all of it
+        fused = self.spine.get(id(e)) if self.depth == 0 and self.uses.get(id(e), 1) == 1 and id(e) not in self.cond else None
         priv = self.private_begin(e) if dist else []
+        ahs = {k: self.ah_new(k) for k, _ in lets} if fused else {}
         if fused:
             for k, x in lets:
-                self.put(f"double ah{k} = 0.0;")
+                self.put(f"double {ahs[k]} = 0.0;")
             self.private_declare(priv)
         if fused and dist:
             self.put("AEHMC_SYNC();")  # (gradient entries change owner between loops when several wavefronts run the program)
@@ -1035,8 +1146,8 @@ class _RevGen:
             self.private_reduce(priv)
             for k, x in reversed(lets):
                 if dist:
-                    self.put(f"ah{k} = AEHMC_WSUM(ah{k});")
-                self.bwd(x, f"ah{k}", env)
+                    self.put(f"{ahs[k]} = AEHMC_WSUM({ahs[k]});")
+                self.bwd(x, ahs[k], env)
             self.done.add(id(e))
         env[("priv", id(e))] = priv
         env[id(e)] = acc
@@ -1054,7 +1165,7 @@ class _RevGen:
         """how many parents every position-dependent inner node has (a shared node's adjoint is collected from all of them
         and propagated ONCE), and which nodes are reached through a branch of a `where` (those are never merged: the
         statement that would propagate the merged adjoint might sit in the branch that is not taken)"""
-        self.uses, self.cond = {}, set()
+        self.uses, self.cond, self.counted = {}, set(), True
 
         def go(e, cond):
             if not isinstance(e, S) or not e.t or e.op in ("q", "ref", "const", "par", "cmp"):
@@ -1109,7 +1220,7 @@ class _RevGen:
             else:
                 self.put(f"{tgt} += {adj};" if self.depth > 0 and self.lane_owned else f"if (lane == 0) {tgt} += {adj};")
         elif op == "ref":
-            self.put(f"ah{a[0]} += {adj};")
+            self.put(f"{self.ah[a[0]]} += {adj};")
         elif op == "neg":
             self.bwd(a[0], self.let(f"-{adj}", "a"), env)
         elif op == "un":
@@ -1157,9 +1268,14 @@ class _RevGen:
                 return
             v, n, body, lets = a
             dist = env[("dist", id(e))]
+            ahs = {k: self.ah_new(k) for k, _ in lets}
             for k, x in lets:
-                self.put(f"double ah{k} = 0.0;")
-            self.private_declare(env.get(("priv", id(e)), []))
+                self.put(f"double {ahs[k]} = 0.0;")
+            priv = env.get(("priv", id(e)), [])
+            if id(e) in self.swept and dist:  # (swept again in the same scope: its per-lane accumulators under new names)
+                priv = self.private_begin(e)
+            self.swept.add(id(e))
+            self.private_declare(priv)
             if adj[0] not in "at" or not adj[1:].isdigit():  # (an expression: named once, outside the loop)
                 adj = self.let(adj, "a")
             if dist:
@@ -1180,11 +1296,12 @@ class _RevGen:
             self.put("}")
             if dist:
                 self.put("AEHMC_SYNC();")
-            self.private_reduce(env.get(("priv", id(e)), []))
+            self.private_reduce(priv)
             for k, x in reversed(lets):
+                self.ah[k] = ahs[k]  # (a sweep of the same sum written inside this one would have renamed it)
                 if dist:
-                    self.put(f"ah{k} = AEHMC_WSUM(ah{k});")
-                self.bwd(x, f"ah{k}", env)
+                    self.put(f"{ahs[k]} = AEHMC_WSUM({ahs[k]});")
+                self.bwd(x, ahs[k], env)
         else:
             raise AssertionError(op)
 
@@ -1254,13 +1371,18 @@ __device__ inline double aehmc_logp_grad(const double *q, double *g, int lane, c
 """
 
 
-def _distributed_terms(e, top=True):
-    """how many loop iterations the reverse-mode program spreads over the lanes (outermost distributable sums)"""
+def _distributed_terms(e, top=True, seen=None):
+    """how many loop iterations the reverse-mode program spreads over the lanes (outermost distributable sums; a sum
+    with several parents is one loop)"""
+    seen = set() if seen is None else seen
+    if id(e) in seen:
+        return 0
+    seen.add(id(e))
     if e.op == "sum":
         if top and _distributable(e):
-            return e.args[1] + sum(_distributed_terms(x) for _, x in e.args[3])
-        return sum(_distributed_terms(x, top) for _, x in e.args[3])  # (what it hoisted is evaluated outside it)
-    return sum(_distributed_terms(x, top) for x in e.args if isinstance(x, S))
+            return e.args[1] + sum(_distributed_terms(x, True, seen) for _, x in e.args[3])
+        return sum(_distributed_terms(x, top, seen) for _, x in e.args[3])  # (what it hoisted is evaluated outside it)
+    return sum(_distributed_terms(x, top, seen) for x in e.args if isinstance(x, S))
 
 
 def _reverse_source(root, dim):
@@ -1273,7 +1395,7 @@ def _reverse_source(root, dim):
         raise AssertionError
     gen.bwd(tree, "1.0", env)
     ptrs = "".join(f"  const double *__restrict__ const prm{k} = prm[{k}];\n" for k in sorted(gen.used_params))
-    src = _REV_PRELUDE + ptrs + "\n".join(gen.lines) + f"\n  return {val};\n}}\n" + _REV_EPILOGUE
+    src = _REV_PRELUDE + ptrs + "\n".join(gen.pre + gen.lines) + f"\n  return {val};\n}}\n" + _REV_EPILOGUE
     # how many loop iterations the program spreads over its lanes: with few chains and long sweeps the engine gives a
     # chain a whole workgroup (engine.hip: joint_wg_wanted)
     src += f"#define AEHMC_JOINT_SWEEP_TERMS {_distributed_terms(tree)}\n"
@@ -1309,7 +1431,12 @@ def trace(fn, dim, scalar=False, args=(), reverse="auto"):
         raise TraceError("logprob_fn returned a comparison result")
     if not out.t:
         raise TraceError("logprob_fn returned a value that does not depend on the position")
+    visited = set()
+
     def has_sum(e):
+        if id(e) in visited:
+            return False
+        visited.add(id(e))
         return e.op == "sum" or any(has_sum(x) for x in e.args if isinstance(x, S))
 
     if dim == 1 and not scalar and not has_sum(out):  # a vector of one entry used entry by entry: the scalar form
@@ -1317,18 +1444,21 @@ def trace(fn, dim, scalar=False, args=(), reverse="auto"):
     ev = _elementwise_var(out, dim, scalar)
     if scalar or ev is not None:
         g = _Gen(elem_var=ev, scalar=scalar)
+        g.count_uses(out.args[2] if ev is not None else out)
         if ev is not None:
             g.names[ev] = "i"
             body = g.ex(out.args[2])
         else:
             body = g.ex(out)
         src = ("template <class T> __device__ T aehmc_logp(T q, long long i, const double *const *prm) {\n"
-               + "\n".join(g.lines) + ("\n" if g.lines else "") + f"  return T({body});\n}}\n")
+               + "\n".join(g.pre + g.lines) + ("\n" if g.pre or g.lines else "") + f"  return T({body});\n}}\n")
         return Traced(src, ctx.params, True, dim)
     g = _Gen()
-    body = g.ex(_hoist(out, [0]))
+    tree = _hoist(out, [0])
+    g.count_uses(tree)
+    body = g.ex(tree)
     src = ("template <class V> __device__ auto aehmc_logp(const V &q, const double *const *prm) {\n"
-           "  typedef decltype(q[0]) T;\n" + "\n".join(g.lines) + ("\n" if g.lines else "") + f"  return T({body});\n}}\n")
+           "  typedef decltype(q[0]) T;\n" + "\n".join(g.pre + g.lines) + ("\n" if g.pre or g.lines else "") + f"  return T({body});\n}}\n")
     tr = Traced(src, ctx.params, False, dim)
     tr.grad_source = None
     if reverse is not False:  # (above 64 coordinates the engine takes this instead of ceil(dim / 64) forward passes)

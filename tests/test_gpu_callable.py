@@ -404,12 +404,12 @@ def test_named_models_three_ways_on_the_device(name):
     three_way(fn, D, len(name))
 
 
-def three_way(fn, D, seed):
+def three_way(fn, D, seed, q0=None):
     from aehmc_amd import RandomStream, nuts, targets
     from aehmc_amd.engine import get_engine
     eng = get_engine()
     C = 5
-    q0 = 0.4 * np.random.default_rng(50 + seed).normal(size=(C, D))
+    q0 = 0.4 * np.random.default_rng(50 + seed).normal(size=(C, D)) if q0 is None else q0
     imm = 0.5 + np.random.default_rng(seed).random(D)
     out = {}
     try:
@@ -428,6 +428,7 @@ def three_way(fn, D, seed):
         assert np.array_equal(out[name][3], out["forward"][3]) and np.array_equal(out[name][4], out["forward"][4])
         np.testing.assert_allclose(out[name][1], out["forward"][1], rtol=RTOL, atol=1e-10)
         np.testing.assert_allclose(out[name][2], out["forward"][2], rtol=1e-7, atol=1e-10)
+    return out
 
 
 @pytest.mark.parametrize("D, per_chain", [(65, False), (128, True), (200, False), (512, False), (512, True)])
@@ -527,3 +528,46 @@ def test_untraceable_python_logprob_fn_raises_typeerror_before_anything_is_compi
     from aehmc_amd import nuts
     with pytest.raises(TypeError, match="control flow cannot be traced"):
         nuts.new_state(dev(np.zeros((3, 4))), lambda q: q.sum() if q[0] > 0 else -q.sum())
+
+
+def golden_shared_gradients():
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "shared_sum_device_grad_v1.json")) as f:
+        return {name: {int(D): np.array(g) for D, g in by_dim.items()} for name, by_dim in json.load(f).items()}
+
+
+def row_error(got, want):
+    """per chain: the largest error of a gradient row as a fraction of the row's largest entry"""
+    return np.abs(got - want).max(axis=1) / np.abs(want).max(axis=1)
+
+
+@pytest.mark.parametrize("D", [17, 70])
+@pytest.mark.parametrize("name", ["shared_log_of_sum", "shared_centred", "shared_where_spine", "shared_var_twice"])
+def test_shared_reductions_three_ways_on_the_device_and_against_50_digits(name, D):
+    """A reduction that is named and used again (tests/test_tracing.py: SHARED) is not fused into its forward loop: it is
+    reduced across the lanes (AEHMC_WSUM), its merged adjoint goes back into a SECOND distributed loop -- through LDS
+    accumulators and AEHMC_SYNC with a workgroup per chain.  17 coordinates: the smallest size with reverse mode on by
+    default; 70: a second pass over the 64 lanes, the rows kernel.  Forward lanes, reverse on a wavefront, reverse on a
+    workgroup against one another (three_way's bars), and each start gradient against minus the closed-form gradient at
+    50 digits (tests/golden/shared_sum_device_grad_v1.json, checked on the host by test_tracing.py) within 8 x the error
+    of the same closed forms in plain float64 at these positions (largest over the family, as in test_tracing.py).
+    Measured on an MI355X: float64 closed forms 5.4e-16 (bound 4.3e-15); the device gradients within 5.9e-16 in every mode
+    (largest: shared_var_twice D = 70 forward 5.9e-16, shared_log_of_sum D = 17 reverse / workgroup 5.8e-16, shared_centred
+    D = 70 5.5e-16; shared_where_spine, whose chain 0 takes the branch below the threshold, 1.7e-16)."""
+    import test_tracing as tt
+    golden = golden_shared_gradients()
+    out = three_way(tt.SHARED[name][0], D, tt.DEVICE_SHARED[name], q0=tt.device_positions(name, D))
+    eg = max(row_error(np.array([-tt.closed_form_float64(tt.SHARED[m][1], q)[1] for q in tt.device_positions(m, d)]), golden[m][d]).max()
+             for m in tt.DEVICE_SHARED for d in (17, 70))
+    assert 0.0 < eg < 1e-14
+    for mode in ("forward", "reverse", "workgroup"):
+        err = row_error(out[mode][0], golden[name][D])
+        print(f"{name} D={D} {mode}: gradient off by {err.max():.3g} (float64 closed forms: {eg:.3g})")
+        assert err.max() <= tt.ALLOWED_OVER_FLOAT64 * eg, (mode, err)
+
+
+def test_random_density_with_shared_reductions_three_ways_on_the_device():
+    """tests/test_tracing.py: random_shared_density (named reductions on and off the additive spine, in a where branch,
+    inside another reduction's body) at 150 coordinates: three passes over the lanes"""
+    from test_tracing import random_shared_density
+    three_way(random_shared_density(4, 150), 150, 4)

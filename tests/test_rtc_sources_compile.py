@@ -99,7 +99,28 @@ def traced_joint():
         v, x = q[0], q[1:]
         return -v * v / 18.0 + (-0.5 * x * x * np.exp(-v) - 0.5 * v).sum() - np.sum(np.log1p(np.square(x - w))) * np.tanh(v)
 
-    tgt = targets.from_callable(funnel_plus, 100)
+    return traced_program(funnel_plus)
+
+
+def traced_shared_sum():
+    """reductions that are named and used again: a sum under a function and in both branches of a where, a variance
+    twice.  Their backward sweeps are loops of their own behind the forward ones (not fused into them): the adjoint,
+    reduced over the lanes, goes back into a second distributed loop -- the path tests/test_gpu_callable.py runs on the device"""
+    import numpy as np
+    from aehmc_amd import tracing
+
+    def shared(x):
+        s, v = (x * x).sum(), x.var()
+        return -s + 3 * np.log(s) + tracing.where(s > 1, -s - v, -s * s - v * v) - v - np.log(v)
+
+    src = traced_program(shared)
+    assert src.count("for (int i") >= 6 and "ah0_1" in src  # (forward and backward loops apart; an accumulator named per sweep)
+    return src
+
+
+def traced_program(fn):
+    from aehmc_amd import targets
+    tgt = targets.from_callable(fn, 100)
     assert isinstance(tgt, targets.CustomJoint) and "#define AEHMC_JOINT_GRAD 1" in tgt.source
     wg = ("template __global__ void aehmc::k_nuts_resident<64, 2, true, 0, false>(aehmc::EngineArgs, aehmc::NutsSampleArgs);\n"
           "template __global__ void aehmc::k_nuts_resident<64, 8, false, 0, false>(aehmc::EngineArgs, aehmc::NutsSampleArgs);\n"
@@ -112,8 +133,9 @@ def traced_joint():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-@pytest.mark.parametrize("name,source", [("elementwise", ELEMENTWISE), ("joint", JOINT), ("glm", GLM), ("traced_joint", traced_joint)],
-                         ids=["elementwise", "joint", "glm", "traced_joint"])
+@pytest.mark.parametrize("name,source", [("elementwise", ELEMENTWISE), ("joint", JOINT), ("glm", GLM), ("traced_joint", traced_joint),
+                                         ("traced_shared_sum", traced_shared_sum)],
+                         ids=["elementwise", "joint", "glm", "traced_joint", "traced_shared_sum"])
 def test_kernel_templates_instantiate_against_a_user_density(tmp_path, name, source):
     path = tmp_path / f"{name}.hip"
     path.write_text(source() if callable(source) else source)

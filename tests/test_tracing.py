@@ -122,9 +122,152 @@ def mixture(q):  # three-component Gaussian mixture: means q[0:3], log-scales q[
     return np.sum(tracing.logsumexp(comp)) - 60 * tracing.logsumexp(lw) - 0.5 * np.sum(q * q) / 9.0
 
 
+# ---- reductions that are named and used again (s = (x * x).sum(); -s + 3 log s): one `sum` node with several parents.
+# Each entry: the Python density and its closed form -- value and gradient over a plain list `x` of numbers of any kind,
+# `m` supplying log / log1p / sqrt / exp for that kind (numpy for float64, mpmath for the 50-digit reference).
+def _tot(xs):
+    return sum(xs[1:], xs[0])
+
+
+def sh_log_of_sum(x):
+    s = (x * x).sum()
+    return -s + 3 * np.log(s)
+
+
+def cf_log_of_sum(x, m):
+    s = _tot([v * v for v in x])
+    return -s + 3 * m.log(s), [(-1 + 3 / s) * 2 * v for v in x]
+
+
+def sh_sum_twice(x):
+    s = (x * x).sum()
+    return -(s + s)
+
+
+def cf_sum_twice(x, m):
+    s = _tot([v * v for v in x])
+    return -(s + s), [-4 * v for v in x]
+
+
+def sh_centred(x):  # a sum on the spine AND inside the body of another reduction
+    s = x.sum()
+    return s - ((x - s) ** 2).sum()
+
+
+def cf_centred(x, m):
+    s = _tot(x)
+    d = [v - s for v in x]
+    sd = _tot(d)
+    return s - _tot([v * v for v in d]), [1 - 2 * v + 2 * sd for v in d]
+
+
+def sh_where_spine(x):  # a sum on the spine AND in both branches of a where
+    s = (x * x).sum()
+    return tracing.where(s > 1, -s, -s * s) - s
+
+
+def cf_where_spine(x, m):
+    s = _tot([v * v for v in x])
+    c = -2 if s > 1 else -2 * s - 1
+    return (-s if s > 1 else -s * s) - s, [c * 2 * v for v in x]
+
+
+def sh_var_twice(x):  # a shared value over a reduction with a hoisted sub-expression (the mean): one loop, one declaration
+    v = x.var()
+    return -v - np.log(v) - 0.05 * (x * x).sum()
+
+
+def cf_var_twice(x, m):
+    n = len(x)
+    mean = _tot(x) / n
+    d = [v - mean for v in x]
+    var = _tot([v * v for v in d]) / n
+    return -var - m.log(var) - 0.05 * _tot([v * v for v in x]), [(-1 - 1 / var) * 2 * dv / n - 0.1 * v for dv, v in zip(d, x)]
+
+
+def sh_where_shared(x):  # a sum with a hoisted sub-expression swept twice in one where branch: accumulators named per sweep
+    s = ((x - x[0]) ** 2).sum()
+    return tracing.where(x[1] > 0.5, s * 2, s * s) - 0.5 * (x * x).sum()
+
+
+def cf_where_shared(x, m):
+    d = [v - x[0] for v in x]
+    s = _tot([v * v for v in d])
+    c = 2 if x[1] > 0.5 else 2 * s
+    ds = [2 * v for v in d]
+    ds[0] = -2 * _tot(d)
+    return (s * 2 if x[1] > 0.5 else s * s) - 0.5 * _tot([v * v for v in x]), [c * dv - v for dv, v in zip(ds, x)]
+
+
+def sh_spine_and_inner(x):
+    s = (x * x).sum()
+    return -s - 0.1 * ((x - 0.1 * s) ** 2).sum()
+
+
+def cf_spine_and_inner(x, m):
+    s = _tot([v * v for v in x])
+    d = [v - 0.1 * s for v in x]
+    sd = _tot(d)
+    return -s - 0.1 * _tot([v * v for v in d]), [-2 * v - 0.2 * dv + 0.04 * v * sd for dv, v in zip(d, x)]
+
+
+def sh_three_uses(x):
+    s = (x * x).sum()
+    return -s + np.log(s) - 0.1 * np.sqrt(s)
+
+
+def cf_three_uses(x, m):
+    s = _tot([v * v for v in x])
+    return -s + m.log(s) - 0.1 * m.sqrt(s), [(-1 + 1 / s - 0.05 / m.sqrt(s)) * 2 * v for v in x]
+
+
+def sh_cmp_only(x):  # the other use is a comparison, which passes no adjoint on: the sum stays fused
+    s = (x * x).sum()
+    return -s + tracing.where(s > 1, 1.0, 2.0) * x[0]
+
+
+def cf_cmp_only(x, m):
+    s = _tot([v * v for v in x])
+    c = 1 if s > 1 else 2
+    g = [-2 * v for v in x]
+    g[0] = g[0] + c
+    return -s + c * x[0], g
+
+
+def sh_lets_hoisted(x):  # exp(-a) is hoisted out of the shared sum's loop: its adjoint accumulator goes with the sum
+    a = x[0]
+    s = ((x[1:] * np.exp(-a)) ** 2).sum()
+    return -s - np.log1p(s) - 0.5 * a * a
+
+
+def cf_lets_hoisted(x, m):
+    a = x[0]
+    u = m.exp(-a)
+    s = _tot([(v * u) * (v * u) for v in x[1:]])
+    f = -1 - 1 / (1 + s)
+    return -s - m.log1p(s) - 0.5 * a * a, [f * (-2 * s) - a] + [f * 2 * u * u * v for v in x[1:]]
+
+
+SHARED = {"shared_log_of_sum": (sh_log_of_sum, cf_log_of_sum), "shared_sum_twice": (sh_sum_twice, cf_sum_twice),
+          "shared_centred": (sh_centred, cf_centred), "shared_where_spine": (sh_where_spine, cf_where_spine),
+          "shared_var_twice": (sh_var_twice, cf_var_twice), "shared_where_shared": (sh_where_shared, cf_where_shared),
+          "shared_spine_and_inner": (sh_spine_and_inner, cf_spine_and_inner), "shared_three_uses": (sh_three_uses, cf_three_uses),
+          "shared_cmp_only": (sh_cmp_only, cf_cmp_only), "shared_lets_hoisted": (sh_lets_hoisted, cf_lets_hoisted)}
+
+
 CASES = {"student_t": (student_t, 7, True), "hierarchical": (hierarchical, 9, False), "mixture": (mixture, 9, False), "shared_in_comparison": (shared_in_comparison, 5, False), "gamma": (gamma_mixture, 6, False), "logistic": (logistic, 5, False), "bernoulli_expit": (bernoulli_expit, 5, False), "more_functions": (more_functions, 5, False), "numpy_idioms": (numpy_idioms, 6, False), "softmax_regression": (softmax_regression, 12, False),
          "shared_under_where": (shared_under_where, 6, False), "mvn": (mvn, 2, False), "funnel": (funnel, 10, False),
          "regression": (regression, 6, False), "kitchen_sink": (kitchen_sink, 5, False)}
+CASES.update({name: (fn, 6, False) for name, (fn, _) in SHARED.items()})
+
+
+def shared_rows_in_where(q):  # a shared sum over data rows (per-lane accumulators for q through X @ q) swept twice in one where branch
+    z = XL[:40] @ q
+    s = (z * z).sum()
+    return tracing.where(q[0] > 0.1, -s, -0.5 * s * s) - 0.5 * (q * q).sum()
+
+
+CASES["shared_rows_in_where"] = (shared_rows_in_where, 5, False)
 
 HARNESS = r"""
 #include <cstdio>
@@ -256,6 +399,36 @@ def random_density(seed, D):
     return fn
 
 
+def random_shared_density(seed, D):
+    """random_density's kind, with terms that reuse one or two NAMED reductions on and off the additive spine: under a
+    function, in a where branch, inside the body of another reduction, with hoisted hyper-parameters"""
+    r = np.random.default_rng(1000 + seed)
+    n = D - 3
+    w = r.normal(size=n) / np.sqrt(n)
+    A = r.normal(size=(3, n)) / np.sqrt(n)
+    picks = r.integers(0, 7, size=3)
+    thr = (0.2 if seed % 2 else 0.6) * n
+
+    def fn(q):
+        a, b, s = q[0], q[1], q[2]
+        x = q[3:]
+        r1 = (x * x).sum()
+        r2 = (x * w).sum()
+        terms = [lambda: -r1 + 2.0 * np.log(r1),
+                 lambda: r2 - 0.5 * ((x - r2 / n) ** 2).sum(),
+                 lambda: tracing.where(r1 > thr, -r1, -r1 * r1 / n) - 0.5 * r1,
+                 lambda: -r1 - np.sqrt(1.0 + r1) * np.tanh(a) - np.log1p(r1 * np.exp(-2.0 * s)),
+                 lambda: (lambda r3: -r3 - np.log1p(r3))(((x - a) ** 2 * np.exp(-s)).sum()),       # hoisted hyper-parameters
+                 lambda: -r2 - 0.5 * np.sum((A @ x - r2) ** 2),
+                 lambda: (lambda v: -v - np.log(v + 0.1))(x.var())]
+        out = -0.5 * (a * a + b * b + s * s) - 0.05 * np.dot(x, x)
+        for k in picks:
+            out = out + terms[k]()
+        return out
+
+    return fn
+
+
 def test_a_long_reduction_that_cannot_be_spread_over_the_lanes_warns():
     X = np.random.default_rng(0).normal(size=(2000, 80))   # 80 coefficients: the inner reduction exceeds the private accumulators
     with pytest.warns(UserWarning, match="runs on ONE lane"):
@@ -332,3 +505,201 @@ def test_untraceable_operations_raise_typeerror_at_trace_time(fn, match):
 def test_max_over_a_long_vector_is_refused_with_its_length():
     with pytest.raises(TypeError, match="max / min over 100 traced entries"):
         tracing.trace(lambda q: np.max(q), 100)
+
+
+# ------------------------------------------------------------------------------------------ shared reductions
+def loops(tr):
+    """how many loops the reverse-mode program runs: a sum whose backward sweep rides in its forward loop is ONE"""
+    return tr.grad_source.count("for (int i")
+
+
+def test_a_spine_sum_is_fused_only_when_the_spine_is_its_one_use_that_carries_an_adjoint():
+    assert loops(tracing.trace(sh_cmp_only, 6)) == 1             # (the other use is a comparison: still fused)
+    assert loops(tracing.trace(lambda x: -(x * x).sum(), 6)) == 1
+    assert loops(tracing.trace(sh_log_of_sum, 6)) == 2           # forward loop, then ONE backward loop with the merged adjoint
+    assert loops(tracing.trace(sh_three_uses, 6)) == 2
+    assert loops(tracing.trace(lambda x: -(x * x).sum() + 3 * np.log((x * x).sum()), 6)) == 3  # two nodes: one fused, one not
+
+
+def shared_inputs(name, D=6):
+    """two positions per density, entries of one sign (no cancellation in the sums): sum x^2 ~ 2.7 and ~ 0.3 at D = 6 --
+    either side of the where threshold 1 and away from it and from 0 -- and x[1] = 0.8 / <= 0.35 around its threshold 0.5"""
+    r = np.random.default_rng(sum(map(ord, name)))
+    big, small = 0.3 + 0.7 * r.random(D), 0.1 + 0.25 * r.random(D)
+    big[1] = 0.8
+    return [big, small]
+
+
+def closed_form_50_digits(cf, q):
+    import mpmath
+    with mpmath.workdps(50):
+        v, g = cf([mpmath.mpf(float(x)) for x in q], mpmath.mp)
+        return v, list(g)
+
+
+def closed_form_float64(cf, q):
+    v, g = cf([np.float64(x) for x in q], np)
+    return float(v), np.array(g, dtype=np.float64)
+
+
+def float64_error_of_the_closed_forms(cases):
+    """(value, gradient): the largest error of the closed forms evaluated in plain float64 against their 50-digit values,
+    over `cases` = [(closed form, position)], each as a fraction of |value| / of the gradient's largest entry"""
+    ev = eg = 0.0
+    for cf, q in cases:
+        v, g = closed_form_50_digits(cf, q)
+        v64, g64 = closed_form_float64(cf, q)
+        ev = max(ev, float(abs(v64 - v) / abs(v)))
+        eg = max(eg, float(max(abs(a - b) for a, b in zip(g64, g)) / max(abs(b) for b in g)))
+    return ev, eg
+
+
+# What the generated programs may be off by: 8 x the error of the same closed form in plain float64 (they associate the
+# sums differently and log_fast is good to 2 ulp; nothing larger is expected).  A density's own float64 error can be
+# exactly zero (-4 x is exact), which no differently ordered program can be held to, so the figure is the largest over
+# the family and both positions, as a fraction of |value| and of the gradient's largest entry.  Measured at D = 6:
+# value 8.78e-16 (shared_cmp_only, second position), gradient 8.71e-16 (shared_log_of_sum, first position: -1 + 3 / s
+# cancels there) -> bounds 7.0e-15 and 7.0e-15; per density the float64 gradient error runs from 0 (shared_sum_twice,
+# shared_where_spine's first position) to that.  The programs: values within 8.8e-16, gradients within 2.6e-15.
+ALLOWED_OVER_FLOAT64 = 8.0
+
+
+@pytest.fixture(scope="module")
+def float64_error():
+    return float64_error_of_the_closed_forms([(cf, q) for name, (_, cf) in sorted(SHARED.items()) for q in shared_inputs(name)])
+
+
+@pytest.mark.parametrize("name", sorted(SHARED))
+def test_shared_reductions_against_the_closed_form_at_50_digits(name, tmp_path, float64_error):
+    """Two generated programs that agree can be wrong together: value and both gradients against the closed-form
+    gradient evaluated with 50 digits"""
+    fn, cf = SHARED[name]
+    tr = tracing.trace(fn, 6)
+    ev, eg = float64_error
+    print(f"float64 error of the closed forms: value {ev:.3g}, gradient {eg:.3g}")
+    assert 0.0 < ev < 1e-14 and 0.0 < eg < 1e-14
+    for k, q in enumerate(shared_inputs(name)):
+        v50, g50 = closed_form_50_digits(cf, q)
+        assert float(fn(q)) == pytest.approx(float(v50), rel=1e-13)  # (the closed form is this density's)
+        gscale = max(abs(b) for b in g50)
+        for mode, (v, g) in (("forward", run_cpp(tr, q, tmp_path, f"{name}{k}")), ("reverse", run_cpp_reverse(tr, q, tmp_path, f"{name}{k}"))):
+            dv = float(abs(v - v50) / abs(v50))
+            dg = float(max(abs(a - b) for a, b in zip(g, g50)) / gscale)
+            print(f"{name}[{k}] {mode}: value off by {dv:.3g}, gradient by {dg:.3g}")
+            assert dv <= ALLOWED_OVER_FLOAT64 * ev, (mode, dv)
+            assert dg <= ALLOWED_OVER_FLOAT64 * eg, (mode, dg)
+
+
+@pytest.mark.parametrize("D", [9, 17, 70])
+@pytest.mark.parametrize("seed", range(12))
+def test_reverse_mode_equals_forward_mode_on_random_densities_with_shared_reductions(seed, D, tmp_path):
+    fn = random_shared_density(seed, D)
+    tr = tracing.trace(fn, D)
+    assert not tr.elementwise and "aehmc_logp_grad" in tr.grad_source
+    q = 0.6 * np.random.default_rng(100 + seed).normal(size=D)
+    v, g = run_cpp(tr, q, tmp_path, f"rsh{seed}")
+    vr, gr = run_cpp_reverse(tr, q, tmp_path, f"rsh{seed}")
+    assert v == pytest.approx(float(fn(q)), rel=1e-12, abs=1e-12) and vr == pytest.approx(v, rel=1e-13, abs=1e-13)
+    np.testing.assert_allclose(gr, g, rtol=1e-12, atol=1e-12)
+    h = 1e-6
+    fd = np.array([(fn(q + h * np.eye(D)[i]) - fn(q - h * np.eye(D)[i])) / (2 * h) for i in range(D)])
+    np.testing.assert_allclose(gr, fd, rtol=5e-7, atol=5e-7)
+
+
+W64 = np.random.default_rng(64).normal(size=64)
+GROWTH = {"logsumexp": lambda q: tracing.logsumexp(q * W64[:len(q)]) - 0.5 * (q * q).sum(),
+          "max": lambda q: np.max(q * W64[:len(q)]) - 0.5 * (q * q).sum(),
+          "logaddexp_reduce": lambda q: np.logaddexp.reduce(q + W64[:len(q)]) - 0.5 * (q * q).sum()}
+
+
+@pytest.mark.parametrize("name", sorted(GROWTH))
+def test_source_of_a_running_maximum_grows_linearly_with_its_terms(name, tmp_path):
+    """logsumexp / max / logaddexp.reduce are nested where(y > m, y, m) with the running m used twice per level: written
+    out as a tree the forward source doubled per term (0.8 MB at 12 terms).  At the documented limit of 64 terms it is
+    at most 64 / 8 times the 8-term source (x 2: longer names), compiles, and is right."""
+    fn = GROWTH[name]
+    small, big = tracing.trace(fn, 8), tracing.trace(fn, 64)
+    assert len(big.source) < 2 * (64 // 8) * len(small.source), (len(small.source), len(big.source))
+    assert len(big.grad_source) < 2 * (64 // 8) * len(small.grad_source)
+    for tr, D in ((small, 8), (big, 64)):
+        q = 0.7 * np.random.default_rng(D).normal(size=D)
+        v, g = run_cpp(tr, q, tmp_path, f"{name}{D}")
+        vr, gr = run_cpp_reverse(tr, q, tmp_path, f"{name}{D}")
+        assert v == pytest.approx(float(fn(q)), rel=1e-13, abs=1e-13) and vr == pytest.approx(v, rel=1e-14, abs=1e-14)
+        h = 1e-6
+        fd = np.array([(fn(q + h * np.eye(D)[i]) - fn(q - h * np.eye(D)[i])) / (2 * h) for i in range(D)])
+        np.testing.assert_allclose(g, fd, rtol=2e-7, atol=2e-8)
+        np.testing.assert_allclose(gr, g, rtol=1e-12, atol=1e-13)
+
+
+YARG = np.random.default_rng(11).normal(size=7) + 0.5
+ARGS_CASES = {"inside_a_reduction": lambda q, y: -0.5 * ((q - y.mean()) ** 2).sum() - q[0] * q[1],
+              "on_the_spine": lambda q, y: y.sum() - 0.5 * ((q - y.mean()) ** 2).sum() + y.mean() * q[2] - (q * y[:5]).sum() * y.var()}
+
+
+@pytest.mark.parametrize("name", sorted(ARGS_CASES))
+def test_a_reduction_over_an_args_array_alone_traces_and_differentiates(name, tmp_path):
+    """`args=` arrays are lifted to traced constants: y.mean() is a `sum` node that does not depend on the position
+    (IndexError: it kept three arguments where every reader takes four; and its loop was dropped from the reverse program)"""
+    fn = ARGS_CASES[name]
+    tr = tracing.trace(fn, 5, args=(YARG,))
+    assert not tr.elementwise
+    q = 0.7 * np.random.default_rng(3).normal(size=5)
+    v, g = run_cpp(tr, q, tmp_path, name)
+    vr, gr = run_cpp_reverse(tr, q, tmp_path, name)
+    assert v == pytest.approx(float(fn(q, YARG)), rel=1e-13, abs=1e-13) and vr == pytest.approx(v, rel=1e-14, abs=1e-14)
+    h = 1e-6
+    fd = np.array([(fn(q + h * np.eye(5)[i], YARG) - fn(q - h * np.eye(5)[i], YARG)) / (2 * h) for i in range(5)])
+    np.testing.assert_allclose(g, fd, rtol=2e-7, atol=2e-8)
+    np.testing.assert_allclose(gr, g, rtol=1e-12, atol=1e-13)
+    if name == "inside_a_reduction":  # the closed form too: grad = -(q - mean(y)) - [q1, q0, 0, 0, 0]
+        exact = -(q - YARG.mean()) - np.array([q[1], q[0], 0.0, 0.0, 0.0])
+        np.testing.assert_allclose(gr, exact, rtol=1e-14, atol=1e-15)
+
+
+def test_sources_of_densities_without_shared_nodes_are_what_they_were():
+    """A node with one parent is emitted exactly as before shared nodes were named: sha256 of the forward template of
+    the models that share nothing (funnel, mvn, more_functions, student_t) and of every model's reverse-mode program,
+    taken before shared nodes were named; `source_with_named_nodes`: the forward templates of the eleven models with
+    shared nodes, as they are since (tests/golden/traced_source_digests_v1.json; the code-object cache is keyed by the source)"""
+    import hashlib
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "traced_source_digests_v1.json")) as f:
+        pinned = json.load(f)
+    assert sum("source" in d for d in pinned.values()) >= 3 and all(("source" in d) != ("source_with_named_nodes" in d) for d in pinned.values())
+    for name, d in sorted(pinned.items()):
+        fn, D, _ = CASES[name]
+        tr = tracing.trace(fn, D)
+        assert hashlib.sha256(tr.source.encode()).hexdigest() == d.get("source", d.get("source_with_named_nodes")), name
+        if "grad_source" in d:
+            assert hashlib.sha256(tr.grad_source.encode()).hexdigest() == d["grad_source"], name
+
+
+# name -> the seed tests/test_gpu_callable.py hands three_way, which draws the start positions from it: seeds at which sum x^2
+# is away from 1 (the where threshold) and from 3 (where shared_log_of_sum's -1 + 3 / s cancels) in every chain
+DEVICE_SHARED = {"shared_log_of_sum": 4, "shared_centred": 5, "shared_where_spine": 1, "shared_var_twice": 4}
+
+
+def device_positions(name, D, C=5):
+    """the start positions tests/test_gpu_callable.py's three_way draws for this density"""
+    q0 = 0.4 * np.random.default_rng(50 + DEVICE_SHARED[name]).normal(size=(C, D))
+    if name == "shared_where_spine":  # chain 0 shrunk to sum x^2 = 0.25: the branch below the threshold runs on the device too
+        q0[0] *= np.sqrt(0.25 / (q0[0] * q0[0]).sum())
+    return q0
+
+
+def test_device_expected_gradients_are_the_closed_forms_at_50_digits():
+    """tests/golden/shared_sum_device_grad_v1.json -- what the device test compares state.potential_energy_grad with -- is
+    minus the closed-form gradient at 50 digits, rounded once; and no start position sits at the where threshold"""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "shared_sum_device_grad_v1.json")) as f:
+        golden = json.load(f)
+    assert sorted(golden) == sorted(DEVICE_SHARED)
+    for name in DEVICE_SHARED:
+        for D in (17, 70):
+            q0 = device_positions(name, D)
+            s = (q0 * q0).sum(axis=1)
+            assert np.abs(s - {"shared_where_spine": 1.0, "shared_log_of_sum": 3.0}.get(name, 0.0)).min() > 0.7
+            assert name != "shared_where_spine" or ((s < 1).sum() == 1 and (s > 1).sum() == 4)  # both branches
+            want = np.array([[-float(x) for x in closed_form_50_digits(SHARED[name][1], q)[1]] for q in q0])
+            assert np.array_equal(want, np.array(golden[name][str(D)]))
