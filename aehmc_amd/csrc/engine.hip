@@ -1205,6 +1205,30 @@ extern "C" int aehmc_summary_quantiles(aehmc_ctx *ctx, int64_t R, int64_t D, int
   return 0;
 }
 
+// Average ranks and normal scores of the stored draws (rank.cuh): the same conventions.  The scratch decides the tile:
+// as many coordinates as it holds are sorted at a time, and the result does not depend on how many that is.
+extern "C" int64_t aehmc_summary_rank_work(int64_t R, int64_t D) {
+  if (R < 1 || D < 1 || R >= (int64_t)1 << 31 || D >= (int64_t)1 << 31) return 0;
+  return (int64_t)tu::rank_work_bytes(R, tu::rank_default_tile(R, D));
+}
+extern "C" int aehmc_summary_rank(aehmc_ctx *ctx, int64_t R, int64_t D, const double *samples, const double *center,
+                                  int mode, double *out, void *work, int64_t work_bytes, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (R < 1 || D < 1 || !samples || !out || !work) FAIL("summary_rank: bad arguments");
+  if (mode != 0 && mode != 1) FAIL("summary_rank: mode must be 0 (ranks) or 1 (normal scores), got " + std::to_string(mode));
+  if ((uintptr_t)work % 256) FAIL("summary_rank: work must be 256-byte aligned");
+  if (R >= (int64_t)1 << 31) FAIL("summary_rank: the counts are 32-bit, R must be below 2^31");
+  if (D >= (int64_t)1 << 31) FAIL("summary_rank: D is too large");
+  const int64_t T = work_bytes > 0 ? tu::rank_tile_width(R, D, (size_t)work_bytes) : 0;
+  if (T < 1)
+    FAIL("summary_rank: work holds " + std::to_string(work_bytes) + " bytes, one coordinate needs " +
+         std::to_string(tu::rank_work_bytes(R, 1)) + " (aehmc_summary_rank_work gives " +
+         std::to_string(aehmc_summary_rank_work(R, D)) + ")");
+  HIPCHK(tu::rank(samples, center, R, D, mode, out, work, T, (hipStream_t)stream));
+  return 0;
+}
+
 extern "C" int aehmc_set_option(aehmc_ctx *ctx, const char *name, int64_t value) {
   if (!ctx || !name) return -2;
   if (!strcmp(name, "fused_hmc")) {

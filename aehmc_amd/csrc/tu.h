@@ -59,6 +59,13 @@ hipError_t quantile_stats(const double *x, long long R, long long D, int U, cons
                           long long M, hipStream_t st);
 hipError_t quantile_out(void *work, long long D, long long M, int n, const int *lo, const int *hi, const double *g,
                         double *out, hipStream_t st);  // rows lo of the statistics; with g, interpolated towards rows hi
+// rank.cuh (a tile of T coordinates needs rank_work_bytes(R, T) of scratch; rank_tile_width: the widest tile that
+// `bytes` hold, 0 if none; rank_default_tile: what fits under 256 MiB, at least 1)
+size_t rank_work_bytes(long long R, long long T);
+long long rank_tile_width(long long R, long long D, size_t bytes);
+long long rank_default_tile(long long R, long long D);
+hipError_t rank(const double *x, const double *centre, long long R, long long D, int mode, double *out, void *work,
+                long long T, hipStream_t st);
 // syrk_f64.cuh, pooled_adapt.cuh
 hipError_t syrk_tn(long long C, long long D, const double *X, long long ldx, const double *centre, double w,
                    const double *w_dev, const double *delta, double *S, long long lds, double *partial, hipStream_t st);

@@ -769,6 +769,22 @@ class Engine:
                     "aehmc_summary_quantiles")
         return out
 
+    def summary_rank(self, samples, center, mode, _work_bytes=None):
+        """out [R, D]: the average rank (mode 0) or the normal score (mode 1) of every draw of samples [R, D] among the
+        draws of its coordinate; with center [D], of the folded draws |samples - center|.  ``_work_bytes``: scratch
+        other than the default (the tile of coordinates sorted at a time follows it; the result does not)."""
+        R, D = samples.shape
+        nbytes = int(self.lib.aehmc_summary_rank_work(int(R), int(D))) if _work_bytes is None else int(_work_bytes)
+        if nbytes <= 0:
+            raise EngineError(f"aehmc_summary_rank_work: no scratch size for R = {R}, D = {D} (1 <= R < 2^31)")
+        work = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        out = torch.empty(R, D, dtype=torch.float64, device=self.device)
+        self._check(self.lib.aehmc_summary_rank(self.ctx, R, D, samples.data_ptr(),
+                                                center.data_ptr() if center is not None else None, int(mode),
+                                                out.data_ptr(), work.data_ptr(), work.numel(), self.stream),
+                    "aehmc_summary_rank")
+        return out
+
     def profile_enable(self, on=True):
         self._check(self.lib.aehmc_profile_enable(self.ctx, int(on)), "aehmc_profile_enable")
 

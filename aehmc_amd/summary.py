@@ -22,6 +22,12 @@ Next to them, from the stored draws and with the chains pooled: exact ``quantile
 ``median``, equal-tailed ``interval``, the raw ``order_statistics`` (a radix select per coordinate, csrc/quantile.cuh:
 no sort) and Stan's ``tail_ess``.
 
+And the rank-normalised diagnostics of Vehtari, Gelman, Simpson, Carpenter and Buerkner (2021), which see what the
+classical ``rhat`` cannot -- chains that agree in location but not in scale, targets without a variance: ``ranks``
+(average ranks of the pooled draws, a segmented radix sort per coordinate, csrc/rank.cuh), ``rank_normalize`` (their
+normal scores z = Phi^-1((r - 3/8) / (S + 1/4))), ``bulk_ess`` and ``rank_rhat``, and ``rank_summarize`` for all of
+them at once.  The kernels produce ranks and scores only; every estimator after that is ``summarize`` run on z.
+
 fp64, deterministic: two calls on the same draws, and any chunking of them, give the same bits.  No CPU fallback."""
 from __future__ import annotations
 
@@ -298,6 +304,95 @@ def tail_ess(samples, *, batched: bool = True, prob: float = 0.05, max_lag: Opti
         e = summarize((samples <= q[i]).to(torch.float64), batched=batched, split=True, max_lag=max_lag).ess
         out = e if out is None else torch.minimum(out, e)
     return out
+
+
+class RankSummary(NamedTuple):
+    """Rank-normalised diagnostics per coordinate (device tensors shaped like one chain's position): ``rhat`` is the
+    larger of ``rhat_bulk`` (split R-hat of the normal scores of the draws) and ``rhat_folded`` (of the normal scores of
+    the draws folded about their median, which sees a difference in scale); ``ess_bulk`` is the split-chain ``ess`` of
+    the normal scores, ``lag_truncated`` belongs to it; ``ess_tail`` is ``tail_ess``."""
+    rhat: torch.Tensor
+    rhat_bulk: torch.Tensor
+    rhat_folded: torch.Tensor
+    ess_bulk: torch.Tensor
+    ess_tail: torch.Tensor
+    lag_truncated: torch.Tensor
+    num_draws: int
+    num_chains: int
+
+
+def _rank(samples, batched, mode, fold):
+    """ranks (mode 0) or normal scores (mode 1) of the pooled draws, or with ``fold`` of the draws folded about the
+    pooled median -- which is computed on the device and handed to the kernel: no folded copy of the draws is made."""
+    x, _ = _pooled(samples, batched)
+    eng = get_engine()
+    _on_device(eng, x)
+    center = eng.summary_quantiles(x, [0.5]).reshape(-1) if fold else None
+    return eng.summary_rank(x, center, mode).reshape(samples.shape)
+
+
+def ranks(samples, *, batched: bool = True):
+    """Average ranks of stored draws, per coordinate and with the chains pooled: a tensor shaped like ``samples`` whose
+    entry is ``#{y < x} + (#{y == x} + 1) / 2`` over the S pooled draws y of the coordinate (1-based; ties share the
+    mean of their places: the bits of ``scipy.stats.rankdata(method="average")``).  ``samples`` as ``summarize`` takes
+    them.  Values compare as IEEE values (-0.0 and +0.0 tie); a coordinate with a NaN gives NaN for all its draws."""
+    return _rank(samples, batched, 0, False)
+
+
+def rank_normalize(samples, *, batched: bool = True, fold: bool = False):
+    """The normal scores ``z = Phi^-1((r - 3/8) / (S + 1/4))`` of the ranks r of ``ranks``, shaped like ``samples``.
+    ``fold``: of the ranks of ``|x - median|`` instead, the median that of the coordinate's pooled draws (``median``)."""
+    return _rank(samples, batched, 1, bool(fold))
+
+
+def _check_rank_run(samples, batched, max_lag=None, acov=True):
+    """The argument checks of the rank-normalised split estimators, all before any work is done."""
+    _pooled(samples, batched)
+    lo = 2 if batched else 1
+    _check_run(samples.shape[0], samples.shape[1] if batched else 1, samples.shape[lo:], True)
+    if acov:
+        _check_acov_length(samples.shape[0], True, max_lag)
+
+
+def bulk_ess(samples, *, batched: bool = True, max_lag: Optional[int] = None):
+    """Bulk ESS: the split-chain ``ess`` of the normal scores of the draws.  Allocates one array the size of
+    ``samples``.  ``summarize``'s length limit (``MAX_ACOV_ROWS``) applies."""
+    _check_rank_run(samples, batched, max_lag)
+    return summarize(rank_normalize(samples, batched=batched), batched=batched, max_lag=max_lag).ess
+
+
+def _split_rhat(z, batched):
+    """``summarize(z).rhat`` from the moments alone (the same kernels, the same bits; no autocovariance, no limit on
+    the length)."""
+    lo = 2 if batched else 1
+    acc = Accumulator(z.shape[0], z.shape[1] if batched else 1, tuple(z.shape[lo:]), True)
+    acc._fold(acc._rows(z, "samples"))
+    return acc.result().rhat
+
+
+def rank_rhat(samples, *, batched: bool = True):
+    """Rank-normalised split R-hat, ``rank_summarize(samples).rhat``: the larger of the split ``rhat`` of the normal
+    scores of the draws and of the draws folded about their median.  One array the size of ``samples`` at a time."""
+    _check_rank_run(samples, batched, acov=False)
+    out = _split_rhat(rank_normalize(samples, batched=batched), batched)
+    return torch.maximum(out, _split_rhat(rank_normalize(samples, batched=batched, fold=True), batched))
+
+
+def rank_summarize(samples, *, batched: bool = True, max_lag: Optional[int] = None, prob: float = 0.05) -> RankSummary:
+    """``RankSummary`` of stored draws ``samples`` as ``summarize`` takes them.  ``max_lag`` as in ``summarize``, for
+    ``ess_bulk`` and ``ess_tail``; ``prob`` as in ``tail_ess``.  Holds one array of normal scores the size of
+    ``samples`` at a time: the bulk estimators come first, and their array is released before that of the folded draws
+    is made (``tail_ess`` then allocates its indicators, again one array at a time).  ``summarize``'s length limit
+    (``MAX_ACOV_ROWS``) applies and is checked before any work is done."""
+    _check_rank_run(samples, batched, max_lag)
+    (prob,), _ = _check_probs(prob)
+    z = rank_normalize(samples, batched=batched)
+    bulk = summarize(z, batched=batched, max_lag=max_lag)
+    del z
+    folded = _split_rhat(rank_normalize(samples, batched=batched, fold=True), batched)
+    return RankSummary(rhat=torch.maximum(bulk.rhat, folded), rhat_bulk=bulk.rhat, rhat_folded=folded,
+                       ess_bulk=bulk.ess, ess_tail=tail_ess(samples, batched=batched, prob=prob, max_lag=max_lag),
+                       lag_truncated=bulk.lag_truncated, num_draws=bulk.num_draws, num_chains=bulk.num_chains)
 
 
 def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_integration_steps=None,

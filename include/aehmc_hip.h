@@ -484,6 +484,26 @@ int aehmc_summary_order_stats(aehmc_ctx *ctx, int64_t R, int64_t D, int64_t M, c
 int aehmc_summary_quantiles(aehmc_ctx *ctx, int64_t R, int64_t D, int64_t Q, const double *samples,
                             const double *probs, double *out, void *work, int64_t work_bytes, void *stream);
 
+/* ---- average ranks and normal scores of the stored draws (aehmc_amd/summary.py) ----
+ * What the rank-normalised split R-hat and the bulk ESS (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021) are
+ * computed from: samples [R, D] as above, out [R, D].  mode 0: out = the average rank of every draw among the R draws
+ * of its coordinate, r = #{y < x} + (#{y == x} + 1) / 2 (1-based; scipy.stats.rankdata(method="average")), a
+ * half-integer below 2^31 and so exact.  mode 1: out = the normal score Phi^-1((r - 3/8) / (R + 1/4)), Phi^-1 by
+ * Wichura's AS 241 (PPND16) in fp64.  center [D] (device) or NULL: with it the ranks are those of |x - center[d]| (the
+ * folded draws; no copy of them is made).  Values compare as IEEE values: -0.0 and +0.0 tie, -inf and +inf and
+ * denormals are ordinary; a coordinate that holds a NaN (or whose fold makes one) gives NaN for every draw.
+ *
+ * Method (csrc/rank.cuh): per tile of T coordinates the keys are written as columns, sorted by a least-significant-
+ * digit radix sort (8 passes of 8 bits, keys only, every position from counts and scans: the same bits on every run),
+ * and every draw's two bounds are searched in its sorted column.  `work` (device, 256-byte aligned) decides T: the call
+ * takes the widest tile that work_bytes hold, anything from one coordinate's need (2 R keys of 8 bytes, 1 KiB of
+ * counters per started 4096 keys, each rounded up to 256 bytes) upward, and the result does not depend on it.
+ * rank_work: the default scratch -- the widest tile under 256 MiB, at least one coordinate; 0 for shapes the call
+ * refuses (1 <= R < 2^31, 1 <= D < 2^31). */
+int64_t aehmc_summary_rank_work(int64_t R, int64_t D);
+int aehmc_summary_rank(aehmc_ctx *ctx, int64_t R, int64_t D, const double *samples, const double *center, int mode,
+                       double *out, void *work, int64_t work_bytes, void *stream);
+
 /* window_adaptation.run (window_adaptation.py:17-116) for a NUTS kernel: num_steps x (one transition
  * with the current per-chain parameters, then aehmc_adapt_update), enqueued in one call.  `stage` /
  * `is_window_end` [num_steps] are HOST arrays from build_schedule.  Before the call the caller binds
