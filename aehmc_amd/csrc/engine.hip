@@ -1156,6 +1156,32 @@ static std::vector<long long> quantile_rows(const std::vector<long long> &want, 
   for (size_t i = 0; i < want.size(); ++i) row[i] = (int)(std::lower_bound(u.begin(), u.end(), want[i]) - u.begin());
   return u;
 }
+// numpy's "linear" rule over R pooled draws: per probability the virtual index h = p (R - 1), its floor and the gap g;
+// u: the distinct ranks floor(h), min(floor(h) + 1, R - 1) of all probabilities, ascending; lo / hi: their rows in u
+static int quantile_ranks(aehmc_ctx *ctx, const char *what, int64_t R, int64_t Q, const double *probs,
+                          std::vector<long long> &u, std::vector<int> &lo, std::vector<int> &hi, std::vector<double> &g) {
+  std::vector<long long> want(2 * Q);
+  g.resize(Q);
+  for (int64_t i = 0; i < Q; ++i) {
+    const double p = probs[i];
+    if (!(p >= 0.0 && p <= 1.0))
+      FAIL(std::string(what) + ": probability " + std::to_string(p) + " is outside [0, 1]");
+    const double h = p * (double)(R - 1), fl = std::floor(h);
+    const long long k = (long long)fl;
+    g[i] = h - fl;
+    want[2 * i] = k;
+    want[2 * i + 1] = k + 1 < R ? k + 1 : R - 1;
+  }
+  std::vector<int> row;
+  u = quantile_rows(want, row);
+  lo.resize(Q);
+  hi.resize(Q);
+  for (int64_t i = 0; i < Q; ++i) {
+    lo[i] = row[2 * i];
+    hi[i] = row[2 * i + 1];
+  }
+  return 0;
+}
 extern "C" int64_t aehmc_summary_quantile_work(int64_t R, int64_t D, int64_t M) {
   if (R < 1 || D < 1 || M < 1 || M > AEHMC_SUMMARY_QUANTILE_MAX || D >= (int64_t)1 << 31) return 0;
   return (int64_t)tu::quantile_work_bytes(D, M);
@@ -1183,25 +1209,62 @@ extern "C" int aehmc_summary_quantiles(aehmc_ctx *ctx, int64_t R, int64_t D, int
   if (!ctx) return -2;
   HIPCHK(hipSetDevice(ctx->device));
   if (int rc = quantile_shape(ctx, "summary_quantiles", R, D, Q, samples, probs, out, work, work_bytes)) return rc;
-  std::vector<long long> want(2 * Q);
-  std::vector<double> g(Q);
-  for (int64_t i = 0; i < Q; ++i) {
-    const double p = probs[i];
-    if (!(p >= 0.0 && p <= 1.0)) FAIL("summary_quantiles: probability " + std::to_string(p) + " is outside [0, 1]");
-    const double h = p * (double)(R - 1), fl = std::floor(h);  // numpy's "linear" rule: virtual index, its floor, the gap
-    const long long lo = (long long)fl;
-    g[i] = h - fl;
-    want[2 * i] = lo;
-    want[2 * i + 1] = lo + 1 < R ? lo + 1 : R - 1;
-  }
-  std::vector<int> row, lo(Q), hi(Q);
-  const std::vector<long long> u = quantile_rows(want, row);
-  for (int64_t i = 0; i < Q; ++i) {
-    lo[i] = row[2 * i];
-    hi[i] = row[2 * i + 1];
-  }
+  std::vector<int> lo, hi;
+  std::vector<double> g;
+  std::vector<long long> u;
+  if (int rc = quantile_ranks(ctx, "summary_quantiles", R, Q, probs, u, lo, hi, g)) return rc;
   HIPCHK(tu::quantile_stats(samples, R, D, (int)u.size(), u.data(), work, Q, (hipStream_t)stream));
   HIPCHK(tu::quantile_out(work, D, Q, (int)Q, lo.data(), hi.data(), g.data(), out, (hipStream_t)stream));
+  return 0;
+}
+
+// Streaming quantiles (sketch.cuh): a fixed-grid histogram per coordinate, the same conventions.
+static int sketch_shape(aehmc_ctx *ctx, const char *what, int64_t D, int64_t B) {
+  if (D < 1) FAIL(std::string(what) + ": bad arguments");
+  if (D >= (int64_t)1 << 31) FAIL(std::string(what) + ": D is too large");
+  if (B < AEHMC_SUMMARY_SKETCH_MIN_BINS || B > AEHMC_SUMMARY_SKETCH_MAX_BINS || (B & (B - 1)))
+    FAIL(std::string(what) + ": the number of bins must be a power of two in [" +
+         std::to_string(AEHMC_SUMMARY_SKETCH_MIN_BINS) + ", " + std::to_string(AEHMC_SUMMARY_SKETCH_MAX_BINS) + "], got " +
+         std::to_string(B));
+  return 0;
+}
+extern "C" int aehmc_summary_sketch_update(aehmc_ctx *ctx, int64_t T, int64_t C, int64_t D, int64_t B,
+                                           const double *samples, const double *lo, const double *inv_width,
+                                           int64_t *counts, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = sketch_shape(ctx, "summary_sketch_update", D, B)) return rc;
+  if (T < 1 || C < 1 || !samples || !lo || !inv_width || !counts) FAIL("summary_sketch_update: bad arguments");
+  if (T >= (int64_t)1 << 31 || C >= (int64_t)1 << 31 || T * C >= (int64_t)1 << 31)
+    FAIL("summary_sketch_update: a workgroup counts in 32 bits, T * C must be below 2^31");
+  HIPCHK(tu::sketch_update(samples, T * C, D, (int)B, lo, inv_width, (unsigned long long *)counts, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int aehmc_summary_sketch_quantiles(aehmc_ctx *ctx, int64_t D, int64_t B, int64_t Q, const double *probs,
+                                              const int64_t *counts, const double *lo, const double *width,
+                                              double *estimate, int32_t *resolved, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = sketch_shape(ctx, "summary_sketch_quantiles", D, B)) return rc;
+  if (Q < 1 || !probs || !counts || !lo || !width || !estimate || !resolved)
+    FAIL("summary_sketch_quantiles: bad arguments");
+  if (Q > AEHMC_SUMMARY_QUANTILE_MAX)
+    FAIL("summary_sketch_quantiles: at most " + std::to_string(AEHMC_SUMMARY_QUANTILE_MAX) + " probabilities a call");
+  // the ranks need the number of pooled draws: every coordinate has counted the same, the first one's counters say it
+  std::vector<unsigned long long> first(B + 3);
+  HIPCHK(hipMemcpyAsync(first.data(), counts, first.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                        (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  unsigned long long total = 0;
+  for (unsigned long long n : first) total += n;
+  if (total < 1) FAIL("summary_sketch_quantiles: no draw has been counted");
+  if (total >= 1ULL << 53) FAIL("summary_sketch_quantiles: the ranks are computed in fp64, the count must be below 2^53");
+  std::vector<int> lo_row, hi_row;
+  std::vector<double> g;
+  std::vector<long long> u;
+  if (int rc = quantile_ranks(ctx, "summary_sketch_quantiles", (int64_t)total, Q, probs, u, lo_row, hi_row, g)) return rc;
+  HIPCHK(tu::sketch_quantiles((const unsigned long long *)counts, lo, width, D, (int)B, (int)Q, (int)u.size(), u.data(),
+                              lo_row.data(), hi_row.data(), g.data(), estimate, resolved, (hipStream_t)stream));
   return 0;
 }
 

@@ -59,6 +59,13 @@ hipError_t quantile_stats(const double *x, long long R, long long D, int U, cons
                           long long M, hipStream_t st);
 hipError_t quantile_out(void *work, long long D, long long M, int n, const int *lo, const int *hi, const double *g,
                         double *out, hipStream_t st);  // rows lo of the statistics; with g, interpolated towards rows hi
+// sketch.cuh (x [R][D] into counts [D][B + 3]; U distinct ascending ranks, rows lo_row / hi_row of them and the gap g
+// behind each of Q probabilities: all host arrays)
+hipError_t sketch_update(const double *x, long long R, long long D, int B, const double *lo, const double *inv,
+                         unsigned long long *counts, hipStream_t st);
+hipError_t sketch_quantiles(const unsigned long long *counts, const double *lo, const double *width, long long D, int B,
+                            int Q, int U, const long long *ranks, const int *lo_row, const int *hi_row, const double *g,
+                            double *estimate, int *resolved, hipStream_t st);
 // rank.cuh (a tile of T coordinates needs rank_work_bytes(R, T) of scratch; rank_tile_width: the widest tile that
 // `bytes` hold, 0 if none; rank_default_tile: what fits under 256 MiB, at least 1)
 size_t rank_work_bytes(long long R, long long T);

@@ -769,6 +769,24 @@ class Engine:
                     "aehmc_summary_quantiles")
         return out
 
+    def summary_sketch_update(self, chunk, bins, lo, inv_width, counts):
+        """Fold chunk [T, C, D] into the histogram counts [D, bins + 3] (int64) on the grid lo, inv_width [D]."""
+        T, C, D = chunk.shape
+        self._check(self.lib.aehmc_summary_sketch_update(self.ctx, T, C, D, int(bins), chunk.data_ptr(), lo.data_ptr(),
+                                                         inv_width.data_ptr(), counts.data_ptr(), self.stream),
+                    "aehmc_summary_sketch_update")
+
+    def summary_sketch_quantiles(self, counts, bins, lo, width, probs):
+        """(estimate [Q, D], resolved [Q, D] int32) of the histogram counts [D, bins + 3] at probs."""
+        D, Q = counts.shape[0], len(probs)
+        est = torch.empty(Q, D, dtype=torch.float64, device=self.device)
+        res = torch.empty(Q, D, dtype=torch.int32, device=self.device)
+        self._check(self.lib.aehmc_summary_sketch_quantiles(self.ctx, D, int(bins), Q, (ct.c_double * Q)(*probs),
+                                                            counts.data_ptr(), lo.data_ptr(), width.data_ptr(),
+                                                            est.data_ptr(), res.data_ptr(), self.stream),
+                    "aehmc_summary_sketch_quantiles")
+        return est, res
+
     def summary_rank(self, samples, center, mode, _work_bytes=None):
         """out [R, D]: the average rank (mode 0) or the normal score (mode 1) of every draw of samples [R, D] among the
         draws of its coordinate; with center [D], of the folded draws |samples - center|.  ``_work_bytes``: scratch

@@ -28,6 +28,10 @@ classical ``rhat`` cannot -- chains that agree in location but not in scale, tar
 normal scores z = Phi^-1((r - 3/8) / (S + 1/4))), ``bulk_ess`` and ``rank_rhat``, and ``rank_summarize`` for all of
 them at once.  The kernels produce ranks and scores only; every estimator after that is ``summarize`` run on z.
 
+Without the stored draws: ``QuantileSketch``, a fixed-grid histogram per coordinate that ``run`` can feed next to its
+``Accumulator`` (csrc/sketch.cuh) -- ``quantiles``, ``median`` and ``interval`` of the pooled draws to within one bin
+width, with ``resolved`` to say where that bound holds.
+
 fp64, deterministic: two calls on the same draws, and any chunking of them, give the same bits.  No CPU fallback."""
 from __future__ import annotations
 
@@ -86,6 +90,19 @@ def _check_draws(x, what):
         raise ValueError(f"{what} must be contiguous")
 
 
+def _chunk_rows(eng, chunk, num_chains, shape, what):
+    """chunk [T, num_chains, *shape] (one chain: the chain axis may be missing), checked, as [T, C, D]."""
+    _check_draws(chunk, what)
+    T = chunk.shape[0] if chunk.ndim else 0
+    tails = [(num_chains,) + shape] + ([shape] if num_chains == 1 else [])  # (one chain: no axis)
+    if T < 1 or tuple(chunk.shape[1:]) not in tails:
+        raise ValueError(f"{what} must be [T, {num_chains}" + "".join(f", {s}" for s in shape) +
+                         f"], got {tuple(chunk.shape)}")
+    if chunk.device != eng.device:
+        raise ValueError(f"{what} must be on {eng.device}, it is on {chunk.device}")
+    return chunk.reshape(T, num_chains, shape[0] if shape else 1)
+
+
 class Accumulator:
     """Streaming moments of a run of ``num_draws`` draws of ``num_chains`` chains whose position has shape ``shape``
     (``()`` or ``(D,)``): ``update(chunk)`` folds the next draws, in order, ``result()`` gives the ``Summary`` once all
@@ -119,15 +136,7 @@ class Accumulator:
             self._acov = torch.zeros(K, D, dtype=torch.float64, device=dev)
 
     def _rows(self, chunk, what="chunk"):
-        _check_draws(chunk, what)
-        T = chunk.shape[0] if chunk.ndim else 0
-        tails = [(self.num_chains,) + self.shape] + ([self.shape] if self.num_chains == 1 else [])  # (one chain: no axis)
-        if T < 1 or tuple(chunk.shape[1:]) not in tails:
-            raise ValueError(f"{what} must be [T, {self.num_chains}" + "".join(f", {s}" for s in self.shape) +
-                             f"], got {tuple(chunk.shape)}")
-        if chunk.device != self._eng.device:
-            raise ValueError(f"{what} must be on {self._eng.device}, it is on {chunk.device}")
-        return chunk.reshape(T, self.num_chains, self.D)
+        return _chunk_rows(self._eng, chunk, self.num_chains, self.shape, what)
 
     def update(self, chunk):
         return self._fold(self._rows(chunk))
@@ -395,8 +404,168 @@ def rank_summarize(samples, *, batched: bool = True, max_lag: Optional[int] = No
                        lag_truncated=bulk.lag_truncated, num_draws=bulk.num_draws, num_chains=bulk.num_chains)
 
 
+# aehmc_hip.h: AEHMC_SUMMARY_SKETCH_MIN_BINS / _MAX_BINS -- the grids of QuantileSketch (a power of two in between)
+MIN_SKETCH_BINS, MAX_SKETCH_BINS = 64, 4096
+
+
+def _grid_edge(v, shape, D, what):
+    """An edge of a QuantileSketch grid -- a float or a [*shape] tensor -- as a host fp64 tensor [D]."""
+    if isinstance(v, torch.Tensor):
+        if tuple(v.shape) != shape:
+            raise ValueError(f"grid {what} must be a float or a tensor of shape {shape}, got shape {tuple(v.shape)}")
+        return v.detach().to(device="cpu", dtype=torch.float64).reshape(D).clone()
+    if isinstance(v, (int, float)) and not isinstance(v, bool):
+        return torch.full((D,), float(v), dtype=torch.float64)
+    raise ValueError(f"grid {what} must be a float or a tensor of shape {shape}, got {type(v).__name__}")
+
+
+class QuantileSketch:
+    """Streaming quantiles of draws that are not kept: a fixed-grid histogram per coordinate, the chains pooled
+    (``aehmc_summary_sketch_update`` / ``_sketch_quantiles``, csrc/sketch.cuh).  ``update(chunk)`` folds draws
+    [T, num_chains, *shape] -- the chunks ``Accumulator.update`` takes, in any order --, ``quantiles`` / ``median`` /
+    ``interval`` answer at any time after the first.  ``summary.run(..., sketch=sk)`` feeds one while it samples.
+
+    Coordinate d has ``bins`` (a power of two in [64, 4096]) equal bins between ``lo[d]`` and ``hi[d]``, one counter
+    below, one above and one for NaN: ``counts`` [D, bins + 3], int64, is the whole state.  An estimate interpolates
+    inside the bin that holds the rank; where ``resolved(probs)`` is True -- both neighbouring ranks in interior bins,
+    no NaN counted -- it lies within ``bound`` (the bin width, [*shape]) of the exact quantile of the pooled draws.  Where
+    it is False the estimate lies outside the grid and carries no bound (NaN where a NaN was counted, as ``quantiles``
+    of stored draws gives).  Counts are integers: any chunking of the same draws gives the same bits.
+
+    The grid: ``grid=(lo, hi)``, floats or [*shape] tensors with finite ``lo < hi``; or ``fit(samples)`` on stored
+    draws; or, by default, fitted to the FIRST chunk folded: with its exact quartiles q25, q50, q75 and
+    scale = (q75 - q25) / 1.349 (1 where that is 0 or not finite), lo, hi = q50 -+ span * scale.  That assumes chains
+    which are warmed up when the first chunk is drawn, as ``summary.run`` expects; it is ``resolved`` that says
+    otherwise -- then pass ``grid`` or more ``span``.  ``span=8`` with 2048 bins is a bin of 1 / 128 of a standard
+    deviation for a normal coordinate."""
+
+    def __init__(self, num_chains: int, shape, *, bins: int = 2048, span: float = 8.0, grid=None):
+        self.num_chains, self.shape = int(num_chains), tuple(int(v) for v in shape)
+        if len(self.shape) > 1:
+            raise ValueError(f"a chain's position must be a scalar or a vector, got shape {self.shape}")
+        if self.num_chains < 1 or (self.shape and self.shape[0] < 1):
+            raise ValueError("num_chains and the position's length must be positive")
+        try:
+            self.bins = operator.index(bins)
+        except TypeError:
+            raise ValueError(f"bins must be an integer, got {bins!r}") from None
+        if not MIN_SKETCH_BINS <= self.bins <= MAX_SKETCH_BINS or self.bins & (self.bins - 1):
+            raise ValueError(f"bins must be a power of two in [{MIN_SKETCH_BINS}, {MAX_SKETCH_BINS}], got {bins}")
+        self.span = float(span)
+        if not (math.isfinite(self.span) and self.span > 0.0):
+            raise ValueError(f"span must be positive and finite, got {span}")
+        self.D = self.shape[0] if self.shape else 1
+        self._lo = self._hi = self._width = self._inv = None
+        if grid is not None:
+            try:
+                lo, hi = grid
+            except (TypeError, ValueError):
+                raise ValueError("grid must be a pair (lo, hi)") from None
+            lo, hi = _grid_edge(lo, self.shape, self.D, "lo"), _grid_edge(hi, self.shape, self.D, "hi")
+            if not bool((torch.isfinite(lo) & torch.isfinite(hi) & (lo < hi)).all()):
+                raise ValueError("grid needs finite edges with lo < hi in every coordinate")
+        self._eng = get_engine()
+        self.counts = torch.zeros(self.D, self.bins + 3, dtype=torch.int64, device=self._eng.device)
+        self._started = False
+        if grid is not None:
+            self._set_grid(lo, hi)
+
+    def _set_grid(self, lo, hi):
+        """lo, hi: host fp64 [D].  width and 1 / width are computed here, once, and the kernels read them."""
+        width = (hi - lo) / float(self.bins)
+        inv = 1.0 / width
+        self._lo, self._hi, self._width, self._inv = (t.to(self._eng.device) for t in (lo, hi, width, inv))
+
+    def _fit(self, x):  # x: [T, C, D]
+        rows = x.reshape(-1, self.D)
+        if rows.shape[0] >= 1 << 31:
+            raise ValueError(f"the selection counts in 32 bits: {rows.shape[0]} pooled draws are not below 2^31")
+        q = self._eng.summary_quantiles(rows, [0.25, 0.5, 0.75]).cpu()
+        scale = (q[2] - q[0]) / 1.349
+        scale = torch.where(torch.isfinite(scale) & (scale != 0.0), scale, torch.ones_like(scale))
+        reach = self.span * scale
+        self._set_grid(q[1] - reach, q[1] + reach)
+
+    def fit(self, samples):
+        """Set the grid from stored draws [T, num_chains, *shape] (their quartiles, as the default does with the first
+        chunk) without counting them; before any ``update``."""
+        if self._started:
+            raise ValueError("fit comes before the first update: the counts belong to the grid they were made on")
+        self._fit(_chunk_rows(self._eng, samples, self.num_chains, self.shape, "samples"))
+        return self
+
+    def update(self, chunk):
+        x = _chunk_rows(self._eng, chunk, self.num_chains, self.shape, "chunk")
+        if x.shape[0] * x.shape[1] >= 1 << 31:
+            raise ValueError(f"a call counts in 32 bits: {x.shape[0] * x.shape[1]} pooled draws are not below 2^31")
+        if self._lo is None:
+            self._fit(x)
+        self._eng.summary_sketch_update(x, self.bins, self._lo, self._inv, self.counts)
+        self._started = True
+        return self
+
+    def merge(self, other):
+        """Add the counts of ``other``, a sketch of other draws on the SAME grid (``bins`` and the bits of both edges)."""
+        if not isinstance(other, QuantileSketch):
+            raise ValueError(f"merge takes a QuantileSketch, got {type(other).__name__}")
+        if other.bins != self.bins or other.shape != self.shape:
+            raise ValueError(f"sketches of {self.bins} bins and shape {self.shape} and of {other.bins} bins and shape "
+                             f"{other.shape} do not merge")
+        if self._lo is None or other._lo is None:
+            raise ValueError("both sketches need their grid before they merge (grid=, fit or a first update)")
+        for mine, theirs in ((self._lo, other._lo), (self._hi, other._hi)):
+            if not torch.equal(mine.view(torch.int64), theirs.view(torch.int64)):
+                raise ValueError("sketches merge on one grid only: lo and hi must be bit-equal")
+        self.counts += other.counts
+        self._started = self._started or other._started
+        return self
+
+    def _query(self, probs):
+        p, scalar = _check_probs(probs)
+        if not self._started:
+            raise ValueError("the sketch has counted no draw yet")
+        est, res = self._eng.summary_sketch_quantiles(self.counts, self.bins, self._lo, self._width, p)
+        view = self.shape if scalar else (len(p),) + self.shape
+        return est.reshape(view), res.bool().reshape(view)
+
+    def quantiles(self, probs):
+        """Estimates at ``probs`` (a float or a sequence of floats in [0, 1]): [Q, *shape], or ``shape`` for a float."""
+        return self._query(probs)[0]
+
+    def resolved(self, probs):
+        """bool, shaped like ``quantiles(probs)``: the estimate lies within ``bound`` of the exact quantile."""
+        return self._query(probs)[1]
+
+    def median(self):
+        return self.quantiles(0.5)
+
+    def interval(self, prob: float = 0.9):
+        """``(lower, upper)``: the estimates at (1 - prob) / 2 and (1 + prob) / 2."""
+        (prob,), _ = _check_probs(prob)
+        q = self.quantiles(((1.0 - prob) / 2.0, (1.0 + prob) / 2.0))
+        return q[0], q[1]
+
+    @property
+    def lo(self):
+        return None if self._lo is None else self._lo.reshape(self.shape)
+
+    @property
+    def hi(self):
+        return None if self._hi is None else self._hi.reshape(self.shape)
+
+    @property
+    def bound(self):
+        """The bin width [*shape]: the error bound of a resolved estimate (None until the grid is set)."""
+        return None if self._width is None else self._width.reshape(self.shape)
+
+    @property
+    def num_draws(self):
+        """Pooled draws counted so far, NaN included (read from the counters)."""
+        return int(self.counts[0].sum().item())
+
+
 def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_integration_steps=None,
-        chunk: Optional[int] = None, max_lag: Optional[int] = None):
+        chunk: Optional[int] = None, max_lag: Optional[int] = None, sketch: Optional[QuantileSketch] = None):
     """Sample ``num_samples`` transitions per chain and summarise them without keeping them: ``kernel.sample`` is
     driven in chunks of ``chunk`` draws into one reused buffer and every chunk is folded into an ``Accumulator``.
     Returns ``(Summary, Diagnostics of the last transition, acceptance history, divergence history)`` -- what
@@ -407,6 +576,10 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
     what many chains are judged by.  ``max_lag=L``: they are those of ``summarize(samples, max_lag=L)`` to rounding,
     from a ring of the last draws instead of all of them -- about 2.25 L draws of extra memory (see ``Accumulator``;
     ``max_lag=32`` at 4096 chains x 10^4 coordinates is about 24 GB).
+
+    ``sketch``: a ``QuantileSketch`` of the run's chains and position shape; every chunk is folded into it too, so that
+    median and intervals are there when the run ends (``sketch.quantiles`` / ``interval`` / ``resolved``).  What is
+    returned does not change.
 
     An HMC kernel needs ``num_integration_steps`` (as in ``window_adaptation.run``).  ``chunk=None``: the largest
     chunk whose buffer stays under ``CHUNK_BYTES`` (1 GiB), at least one draw."""
@@ -427,6 +600,9 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
     if chunk is not None and int(chunk) < 1:
         raise ValueError("chunk must be at least 1")
     acc = Accumulator(N, C, shape, max_lag=max_lag)
+    if sketch is not None and not (isinstance(sketch, QuantileSketch) and sketch.num_chains == C
+                                   and sketch.shape == acc.shape):
+        raise ValueError(f"sketch must be a QuantileSketch of {C} chains and shape {acc.shape}")
     per_draw = C * acc.D * 8
     chunk = min(N, int(chunk) if chunk is not None else max(1, CHUNK_BYTES // per_draw))
     dev = acc._eng.device
@@ -437,6 +613,8 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
         T = min(chunk, N - done)
         samples, info, a, d = kernel.sample(state, step_size, inverse_mass_matrix, *extra, T, into=buf)
         acc.update(samples.reshape((T, C) + shape))
+        if sketch is not None:
+            sketch.update(samples.reshape((T, C) + shape))
         if acc_hist is None:
             acc_hist = torch.empty((N,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
             div_hist = torch.empty((N,) + tuple(d.shape[1:]), dtype=d.dtype, device=d.device)

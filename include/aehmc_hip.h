@@ -484,6 +484,39 @@ int aehmc_summary_order_stats(aehmc_ctx *ctx, int64_t R, int64_t D, int64_t M, c
 int aehmc_summary_quantiles(aehmc_ctx *ctx, int64_t R, int64_t D, int64_t Q, const double *samples,
                             const double *probs, double *out, void *work, int64_t work_bytes, void *stream);
 
+/* ---- streaming quantiles: a histogram sketch of draws that are not stored (aehmc_amd/summary.py) ----
+ * What `update` above is to the moments, for quantiles: every chunk samples [T, C, D] of a run is folded into a
+ * fixed-grid histogram per coordinate and may then be discarded; the chains are pooled.  Coordinate d has the grid
+ * lo[d] ... hi[d] in B bins of width[d] = (hi[d] - lo[d]) / B, with inv_width[d] = 1 / width[d]; the CALLER computes
+ * width and inv_width once, in fp64, and hands the same [D] device arrays to every call -- the kernels never recompute
+ * them.  B is a power of two in [AEHMC_SUMMARY_SKETCH_MIN_BINS, AEHMC_SUMMARY_SKETCH_MAX_BINS].  counts [D, B + 3]
+ * (device, 64-bit, ZEROS at the start): slot 0 below the grid, slots 1 ... B interior, slot B + 1 above, slot B + 2 NaN.
+ * A value x goes to the slot of t = (x - lo) * inv_width (two rounded fp64 operations): NaN -> B + 2, t < 0 -> 0,
+ * t >= B -> B + 1, else 1 + (long long)t; -inf / +inf land below / above without a special case.  The map is monotone
+ * in x, so the k-th order statistic lies in the slot in which the cumulative count passes k.  Integer additions only
+ * (LDS atomics per workgroup, one 64-bit global atomic per non-empty counter): counts do not depend on where the chunks
+ * are cut, on the order of arrival or on the launch geometry, and counts of runs that share a grid may be added.  All
+ * buffers are the caller's; none of these calls touches the workspace, the target or the metric.
+ *
+ * sketch_update: folds samples [T, C, D] into counts.  A workgroup counts in 32 bits: 1 <= T C < 2^31 rows a call (the
+ * 64-bit totals have no such limit).
+ *
+ * sketch_quantiles: estimate [Q, D] and resolved [Q, D] at probs (a HOST array of Q values in [0, 1];
+ * Q <= AEHMC_SUMMARY_QUANTILE_MAX).  With R the total of a coordinate's B + 3 counters (read back from the first
+ * coordinate: the call waits for the stream; R >= 1), the ranks are those of `quantiles` above: h = p (R - 1),
+ * k = floor(h), g = h - k, k1 = min(k + 1, R - 1).  Rank r lies in the slot j with cum[j-1] <= r < cum[j] (cum over
+ * slots 0 ... B + 1) at pos(r) = lo + width ((j - 1) + (r - cum[j-1] + 0.5) / count[j]), and
+ * estimate = pos(k) + g (pos(k1) - pos(k)).  resolved = 1 where both slots are interior and the coordinate counted no
+ * NaN: there |estimate - exact quantile| <= width up to rounding.  A coordinate that counted a NaN gives NaN (as
+ * `quantiles` does); otherwise an unresolved estimate is the formula's value, outside the grid and without a bound. */
+#define AEHMC_SUMMARY_SKETCH_MIN_BINS 64
+#define AEHMC_SUMMARY_SKETCH_MAX_BINS 4096
+int aehmc_summary_sketch_update(aehmc_ctx *ctx, int64_t T, int64_t C, int64_t D, int64_t B, const double *samples,
+                                const double *lo, const double *inv_width, int64_t *counts, void *stream);
+int aehmc_summary_sketch_quantiles(aehmc_ctx *ctx, int64_t D, int64_t B, int64_t Q, const double *probs,
+                                   const int64_t *counts, const double *lo, const double *width, double *estimate,
+                                   int32_t *resolved, void *stream);
+
 /* ---- average ranks and normal scores of the stored draws (aehmc_amd/summary.py) ----
  * What the rank-normalised split R-hat and the bulk ESS (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021) are
  * computed from: samples [R, D] as above, out [R, D].  mode 0: out = the average rank of every draw among the R draws
