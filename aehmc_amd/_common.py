@@ -1,11 +1,11 @@
-"""Shape plumbing shared by hmc.py / nuts.py: the reference works on one chain
+"""What hmc.py / nuts.py share: the kernel factory, and the shape plumbing -- the reference works on one chain
 (position of shape () or (D,)); the engine adds a leading chain axis."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from .engine import _dev_f64, get_engine
+from .engine import _dev_f64, get_engine, rng_to_device
 from .integrators import IntegratorState
 from .trajectory import Diagnostics
 
@@ -102,3 +102,43 @@ def histories(layout: Layout, out, n: int, keep_samples: bool):
     hist_shape = (n,) + layout.scalar_chain_shape
     return (samples, out["acceptance_history"].reshape(hist_shape),
             out["divergence_history"].bool().reshape(hist_shape))
+
+
+def bind_target(k, eng, state: IntegratorState, layout: Layout, scalar):
+    """Before an engine call of the kernel with the settings ``k`` (``step._hmc`` / ``step._nuts``): its generator states
+    placed on the engine's device, the state as rows ``q, U, g`` and its target bound (``scalar``: what
+    ``Engine.set_target`` hands to ``targets.as_target`` should a Python function still have to be traced)."""
+    holder = k["holder"]
+    if "rng" not in holder or holder["rng"].device != eng.device:  # (uploaded at construction when a GPU is there)
+        holder["rng"] = holder["rng"].to(eng.device) if "rng" in holder else rng_to_device(k["rng_host"], eng.device)
+    q, U, g = state_rows(state, layout, eng.device)
+    eng.set_target(k["logprob_fn"], layout.D, scalar=scalar)
+    return q, U, g
+
+
+def make_kernel(srng, logprob_fn, *, nuts: bool, n_sites: int, settings: dict):
+    """What ``hmc.new_kernel`` and ``nuts.new_kernel`` build alike, as ``(holder, bind, finish)``: ``holder["rng"]`` is
+    the live device tensor of the ``n_sites`` generator states per chain drawn from ``srng``; ``bind(state,
+    inverse_mass_matrix) -> eng, layout, q, U, g`` readies the engine for one call; ``finish(step, sample)`` returns
+    ``step`` with ``sample``, the chain layout and the settings (``_nuts`` / ``_hmc``: for tests, resuming and the
+    one-call warm-up of window_adaptation.run) attached."""
+    rng_host = srng.sites(n_sites)
+    holder = {}
+    if torch.cuda.is_available():  # the generator states go to the device with the kernel, not with its first call
+        holder["rng"] = rng_to_device(rng_host, get_engine().device)
+    k = dict(srng=srng, rng_host=rng_host, holder=holder, logprob_fn=logprob_fn, **settings)
+
+    def _bind(state: IntegratorState, inverse_mass_matrix):
+        eng = get_engine()
+        layout = Layout(tuple(state.position.shape), srng.batched, srng.num_chains)
+        q, U, g = bind_target(k, eng, state, layout, layout.scalar)
+        eng.set_metric(inverse_mass_matrix, layout.D)
+        return eng, layout, q, U, g
+
+    def finish(step, sample):
+        step.sample = sample
+        step.num_chains, step.batched = srng.num_chains, srng.batched
+        setattr(step, "_nuts" if nuts else "_hmc", k)
+        return step
+
+    return holder, _bind, finish

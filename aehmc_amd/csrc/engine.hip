@@ -12,6 +12,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/aehmc_hip.h"
@@ -2272,6 +2273,51 @@ extern "C" int aehmc_nuts_step(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double 
                   (hipStream_t)stream);
 }
 
+// What the four warm-up entry points check before they enqueue anything (`State`: aehmc_adapt_state, one adaptation per
+// chain, or aehmc_pooled_adapt_state, ONE for all chains): the arguments, then that the bound step sizes and metric are
+// the adaptation state's own arrays -- every path samples with the bound arrays while the update kernel rewrites the
+// state's, so they must be the same.
+template <class State>
+static int warmup_bound(aehmc_ctx *ctx, int64_t C, const aehmc_diagnostics *out, const State *state,
+                        const int32_t *stage, const int32_t *is_window_end) {
+  constexpr bool pooled = std::is_same<State, aehmc_pooled_adapt_state>::value;
+  if (!ctx || !out || !state || !stage || !is_window_end) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx->has_tgt || (pooled && !ctx->has_met)) FAIL("set_target and set_metric must be called first");
+  if (!ctx->eps_c || (pooled ? ctx->eps_n != C || ctx->met.per_chain : !ctx->met.per_chain))
+    FAIL(pooled ? "pooled warm-up needs the step sizes [C] of the adaptation state and a SHARED metric bound"
+                : "warm-up needs per-chain step sizes and a per-chain metric bound to the adaptation state");
+  if (ctx->met.imm != state->imm || ctx->met.sqrt_mass != state->sqrt_mass || ctx->eps_c != state->step_size)
+    FAIL(pooled ? "pooled warm-up: the bound metric / step sizes are not the adaptation state's own arrays "
+                  "(bind state->imm, state->sqrt_mass with aehmc_set_metric and state->step_size with aehmc_set_step_sizes)"
+                : "warm-up: the bound per-chain metric / step sizes are not the adaptation state's own arrays "
+                  "(bind state->imm, state->sqrt_mass with aehmc_set_metric and state->step_size with aehmc_set_step_sizes)");
+  if (pooled && (ctx->met.ndim == 2) != (state->full != 0)) FAIL("pooled warm-up: the bound metric and state->full disagree");
+  return 0;
+}
+
+// The warm-up loop (window_adaptation.py:66-77): num_steps x (`transition()`, then `update` -- aehmc_adapt_update or
+// aehmc_pooled_adapt_update -- on its acceptance probabilities and positions), enqueued in one call: the same kernels in
+// the same order as the caller's own loop.  `rebind` (pooled): after a window end the shared metric is bound again --
+// the same arrays, new content: the engine drops what it derived from the old one.
+template <class Transition, class Update, class State>
+static int warmup_loop(aehmc_ctx *ctx, int64_t C, int64_t num_steps, const int32_t *stage, const int32_t *is_window_end,
+                       double target_acceptance_rate, const double *q, const aehmc_diagnostics *out, const State *state,
+                       void *stream, bool rebind, Update update, Transition transition) {
+  const int64_t D = ctx->tgt.D;
+  for (int64_t i = 0; i < num_steps; i++) {
+    if (int rc = transition()) return rc;
+    if (int rc = update(ctx, C, D, stage[i], is_window_end[i], i == num_steps - 1, target_acceptance_rate,
+                        out->acceptance_probability, q, state, stream))
+      return rc;
+    if (rebind && is_window_end[i]) {
+      const aehmc_metric m = ctx->met;
+      if (int rc = aehmc_set_metric(ctx, &m)) return rc;
+    }
+  }
+  return 0;
+}
+
 // window_adaptation.run (window_adaptation.py:17-116): the whole warm-up loop -- one NUTS transition
 // with the current per-chain parameters, then the adaptation update -- enqueued without returning
 // to the host language between steps.  The caller has bound the per-chain metric (state->imm /
@@ -2281,14 +2327,7 @@ extern "C" int aehmc_nuts_warmup(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64
                                  double target_acceptance_rate, int64_t max_num_expansions,
                                  double divergence_threshold, double *q, double *U, double *g,
                                  const aehmc_diagnostics *out, const aehmc_adapt_state *state, void *stream) {
-  if (!ctx || !out || !state || !stage || !is_window_end) return -2;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->has_tgt) FAIL("set_target and set_metric must be called first");
-  if (!ctx->eps_c || !ctx->met.per_chain) FAIL("warm-up needs per-chain step sizes and a per-chain metric bound to the adaptation state");
-  // every path samples with the bound arrays while the update kernel rewrites the state's: they must be the same
-  if (ctx->met.imm != state->imm || ctx->met.sqrt_mass != state->sqrt_mass || ctx->eps_c != state->step_size)
-    FAIL("warm-up: the bound per-chain metric / step sizes are not the adaptation state's own arrays "
-         "(bind state->imm, state->sqrt_mass with aehmc_set_metric and state->step_size with aehmc_set_step_sizes)");
+  if (int rc = warmup_bound(ctx, C, out, state, stage, is_window_end)) return rc;
   const int64_t D = ctx->tgt.D;
   // diagonal mass matrix, regression target or a coordinate-wise target with D <= 512: the whole warm-up
   // in ONE launch, the chains adapting and moving on at their own pace (nuts_linreg.cuh: every chain;
@@ -2328,14 +2367,27 @@ extern "C" int aehmc_nuts_warmup(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64
     if (!all_done) FAIL("internal: the fused warm-up kernel was not taken");
     return 0;
   }
-  for (int64_t i = 0; i < num_steps; i++) {
-    if (int rc = nuts_run(ctx, C, rng, 0.0, max_num_expansions, divergence_threshold, q, U, g, out,
-                          (hipStream_t)stream))
-      return rc;
-    if (int rc = aehmc_adapt_update(ctx, C, D, stage[i], is_window_end[i], i == num_steps - 1,
-                                    target_acceptance_rate, out->acceptance_probability, q, state, stream))
-      return rc;
-  }
+  return warmup_loop(ctx, C, num_steps, stage, is_window_end, target_acceptance_rate, q, out, state, stream, false,
+                     aehmc_adapt_update, [&] {
+                       return nuts_run(ctx, C, rng, 0.0, max_num_expansions, divergence_threshold, q, U, g, out,
+                                       (hipStream_t)stream);
+                     });
+}
+
+// one transition of a sample() call into the caller's histories (each optional): the positions after transition t, its
+// acceptance probabilities and divergence flags
+static int record_transition(aehmc_ctx *ctx, int64_t C, int64_t D, int64_t t, const double *q,
+                             const aehmc_diagnostics *out, double *samples, double *acceptance_history,
+                             int32_t *divergence_history, hipStream_t st) {
+  if (samples)
+    HIPCHK(hipMemcpyAsync(samples + (size_t)t * C * D, q, (size_t)C * D * sizeof(double),
+                          hipMemcpyDeviceToDevice, st));
+  if (acceptance_history)
+    HIPCHK(hipMemcpyAsync(acceptance_history + (size_t)t * C, out->acceptance_probability,
+                          C * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (divergence_history)
+    HIPCHK(hipMemcpyAsync(divergence_history + (size_t)t * C, out->is_diverging, C * sizeof(int32_t),
+                          hipMemcpyDeviceToDevice, st));
   return 0;
 }
 
@@ -2367,15 +2419,7 @@ extern "C" int aehmc_nuts_sample(aehmc_ctx *ctx, int64_t C, uint64_t *rng, doubl
                           out, st, t == 0 ? &multi : nullptr, &all_done))
       return rc;
     if (all_done) return 0;  // every transition ran inside that one launch
-    if (samples)
-      HIPCHK(hipMemcpyAsync(samples + (size_t)t * C * D, q, (size_t)C * D * sizeof(double),
-                            hipMemcpyDeviceToDevice, st));
-    if (acceptance_history)
-      HIPCHK(hipMemcpyAsync(acceptance_history + (size_t)t * C, out->acceptance_probability,
-                            C * sizeof(double), hipMemcpyDeviceToDevice, st));
-    if (divergence_history)
-      HIPCHK(hipMemcpyAsync(divergence_history + (size_t)t * C, out->is_diverging, C * sizeof(int32_t),
-                            hipMemcpyDeviceToDevice, st));
+    if (int rc = record_transition(ctx, C, D, t, q, out, samples, acceptance_history, divergence_history, st)) return rc;
     if (n_leapfrog_total)
       LAUNCH(k_add_i64, C, st, (long long *)n_leapfrog_total, (const long long *)out->n_leapfrog, (long long)C);
   }
@@ -2661,15 +2705,7 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
     else LAUNCH(k_hmc_end<false>, C, st, e, (long long)L);
     if (white)
       if (int rc = white_end(ctx, a, wb, st)) return rc;
-    if (samples)
-      HIPCHK(hipMemcpyAsync(samples + (size_t)t * C * D, q, (size_t)C * D * sizeof(double),
-                            hipMemcpyDeviceToDevice, st));
-    if (acc_hist)
-      HIPCHK(hipMemcpyAsync(acc_hist + (size_t)t * C, out->acceptance_probability, C * sizeof(double),
-                            hipMemcpyDeviceToDevice, st));
-    if (div_hist)
-      HIPCHK(hipMemcpyAsync(div_hist + (size_t)t * C, out->is_diverging, C * sizeof(int32_t),
-                            hipMemcpyDeviceToDevice, st));
+    if (int rc = record_transition(ctx, C, D, t, q, out, samples, acc_hist, div_hist, st)) return rc;
   }
   return fill_n_leapfrog(ctx, C, L, T, out, true, st);
 }
@@ -2702,63 +2738,28 @@ extern "C" int aehmc_hmc_warmup(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_
                                 int64_t num_integration_steps, double divergence_threshold, double *q, double *U,
                                 double *g, const aehmc_diagnostics *out, const aehmc_adapt_state *state,
                                 void *stream) {
-  if (!ctx || !out || !state || !stage || !is_window_end) return -2;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (!ctx->has_tgt) FAIL("set_target and set_metric must be called first");
-  if (!ctx->eps_c || !ctx->met.per_chain) FAIL("warm-up needs per-chain step sizes and a per-chain metric bound to the adaptation state");
-  if (ctx->met.imm != state->imm || ctx->met.sqrt_mass != state->sqrt_mass || ctx->eps_c != state->step_size)
-    FAIL("warm-up: the bound per-chain metric / step sizes are not the adaptation state's own arrays "
-         "(bind state->imm, state->sqrt_mass with aehmc_set_metric and state->step_size with aehmc_set_step_sizes)");
-  const int64_t D = ctx->tgt.D;
-  for (int64_t i = 0; i < num_steps; i++) {
-    if (int rc = hmc_run(ctx, C, rng, 0.0, num_integration_steps, divergence_threshold, 1, q, U, g, out, nullptr,
-                         nullptr, nullptr, (hipStream_t)stream))
-      return rc;
-    if (int rc = aehmc_adapt_update(ctx, C, D, stage[i], is_window_end[i], i == num_steps - 1,
-                                    target_acceptance_rate, out->acceptance_probability, q, state, stream))
-      return rc;
-  }
-  return 0;
+  if (int rc = warmup_bound(ctx, C, out, state, stage, is_window_end)) return rc;
+  return warmup_loop(ctx, C, num_steps, stage, is_window_end, target_acceptance_rate, q, out, state, stream, false,
+                     aehmc_adapt_update, [&] {
+                       return hmc_run(ctx, C, rng, 0.0, num_integration_steps, divergence_threshold, 1, q, U, g, out,
+                                      nullptr, nullptr, nullptr, (hipStream_t)stream);
+                     });
 }
 
 // window_adaptation.run(..., pooled=True): the transitions run with ONE shared metric and one step size (every entry of
 // state->step_size), on whatever route nuts_run / hmc_run give such a binding; the pooled update follows each
-static int pooled_bound(aehmc_ctx *ctx, int64_t C, const aehmc_pooled_adapt_state *state) {
-  if (!ctx->has_tgt || !ctx->has_met) FAIL("set_target and set_metric must be called first");
-  if (!ctx->eps_c || ctx->eps_n != C || ctx->met.per_chain)
-    FAIL("pooled warm-up needs the step sizes [C] of the adaptation state and a SHARED metric bound");
-  if (ctx->met.imm != state->imm || ctx->met.sqrt_mass != state->sqrt_mass || ctx->eps_c != state->step_size)
-    FAIL("pooled warm-up: the bound metric / step sizes are not the adaptation state's own arrays "
-         "(bind state->imm, state->sqrt_mass with aehmc_set_metric and state->step_size with aehmc_set_step_sizes)");
-  if ((ctx->met.ndim == 2) != (state->full != 0)) FAIL("pooled warm-up: the bound metric and state->full disagree");
-  return 0;
-}
-// after a window end: the same arrays, new content -- the engine drops what it derived from the old one
-static int pooled_rebind(aehmc_ctx *ctx) {
-  const aehmc_metric m = ctx->met;
-  return aehmc_set_metric(ctx, &m);
-}
 extern "C" int aehmc_nuts_warmup_pooled(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_t num_steps,
                                         const int32_t *stage, const int32_t *is_window_end,
                                         double target_acceptance_rate, int64_t max_num_expansions,
                                         double divergence_threshold, double *q, double *U, double *g,
                                         const aehmc_diagnostics *out, const aehmc_pooled_adapt_state *state,
                                         void *stream) {
-  if (!ctx || !out || !state || !stage || !is_window_end) return -2;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (int rc = pooled_bound(ctx, C, state)) return rc;
-  const int64_t D = ctx->tgt.D;
-  for (int64_t i = 0; i < num_steps; i++) {
-    if (int rc = nuts_run(ctx, C, rng, 0.0, max_num_expansions, divergence_threshold, q, U, g, out,
-                          (hipStream_t)stream))
-      return rc;
-    if (int rc = aehmc_pooled_adapt_update(ctx, C, D, stage[i], is_window_end[i], i == num_steps - 1,
-                                           target_acceptance_rate, out->acceptance_probability, q, state, stream))
-      return rc;
-    if (is_window_end[i])
-      if (int rc = pooled_rebind(ctx)) return rc;
-  }
-  return 0;
+  if (int rc = warmup_bound(ctx, C, out, state, stage, is_window_end)) return rc;
+  return warmup_loop(ctx, C, num_steps, stage, is_window_end, target_acceptance_rate, q, out, state, stream, true,
+                     aehmc_pooled_adapt_update, [&] {
+                       return nuts_run(ctx, C, rng, 0.0, max_num_expansions, divergence_threshold, q, U, g, out,
+                                       (hipStream_t)stream);
+                     });
 }
 extern "C" int aehmc_hmc_warmup_pooled(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_t num_steps,
                                        const int32_t *stage, const int32_t *is_window_end,
@@ -2766,21 +2767,12 @@ extern "C" int aehmc_hmc_warmup_pooled(aehmc_ctx *ctx, int64_t C, uint64_t *rng,
                                        double divergence_threshold, double *q, double *U, double *g,
                                        const aehmc_diagnostics *out, const aehmc_pooled_adapt_state *state,
                                        void *stream) {
-  if (!ctx || !out || !state || !stage || !is_window_end) return -2;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (int rc = pooled_bound(ctx, C, state)) return rc;
-  const int64_t D = ctx->tgt.D;
-  for (int64_t i = 0; i < num_steps; i++) {
-    if (int rc = hmc_run(ctx, C, rng, 0.0, num_integration_steps, divergence_threshold, 1, q, U, g, out, nullptr,
-                         nullptr, nullptr, (hipStream_t)stream))
-      return rc;
-    if (int rc = aehmc_pooled_adapt_update(ctx, C, D, stage[i], is_window_end[i], i == num_steps - 1,
-                                           target_acceptance_rate, out->acceptance_probability, q, state, stream))
-      return rc;
-    if (is_window_end[i])
-      if (int rc = pooled_rebind(ctx)) return rc;
-  }
-  return 0;
+  if (int rc = warmup_bound(ctx, C, out, state, stage, is_window_end)) return rc;
+  return warmup_loop(ctx, C, num_steps, stage, is_window_end, target_acceptance_rate, q, out, state, stream, true,
+                     aehmc_pooled_adapt_update, [&] {
+                       return hmc_run(ctx, C, rng, 0.0, num_integration_steps, divergence_threshold, 1, q, U, g, out,
+                                      nullptr, nullptr, nullptr, (hipStream_t)stream);
+                     });
 }
 
 extern "C" int aehmc_leapfrog(aehmc_ctx *ctx, int64_t C, double step_size, int64_t nsteps, double *q,

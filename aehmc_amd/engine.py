@@ -325,12 +325,14 @@ class Engine:
     def set_step_sizes(self, eps):
         """eps: PerChain -> per-chain step sizes; anything else -> scalar (returned)."""
         if isinstance(eps, PerChain):
-            t = _dev_f64(eps.value, self.device).reshape(-1)
-            self._keep["eps"] = t
-            self._check(self.lib.aehmc_set_step_sizes(self.ctx, t.data_ptr(), t.numel()), "aehmc_set_step_sizes")
+            self._bind_step_sizes(_dev_f64(eps.value, self.device).reshape(-1))
             return 0.0
         self._clear_step_sizes()
         return float(eps)
+
+    def _bind_step_sizes(self, t):
+        self._keep["eps"] = t
+        self._check(self.lib.aehmc_set_step_sizes(self.ctx, t.data_ptr(), t.numel()), "aehmc_set_step_sizes")
 
     def _clear_step_sizes(self):
         """Per-chain step sizes apply to ONE step/sample call: the ctx is shared per device and
@@ -435,26 +437,27 @@ class Engine:
                         int(L), float(thr), q.data_ptr(), U.data_ptr(), g.data_ptr(), ct.byref(c), self.stream)
         return out
 
-    def _samples_buffer(self, n, C, D, keep_samples, into):
-        """The [n, C, D] array a sample() call writes its draws to: fresh, or the head of the caller's buffer ``into``
-        (summary.run folds chunk after chunk from one buffer)."""
+    def _history_buffers(self, n, C, D, keep_samples, into):
+        """What a sample() call records per transition: the draws [n, C, D] -- fresh, or the head of the caller's buffer
+        ``into`` (summary.run folds chunk after chunk from one buffer); None without ``keep_samples`` -- and the
+        acceptance [n, C] and divergence [n, C] histories."""
         if not keep_samples:
-            return None
-        if into is None:
-            return torch.empty(n, C, D, dtype=torch.float64, device=self.device)
-        if into.dtype != torch.float64 or into.device != self.device or not into.is_contiguous() or into.numel() < n * C * D:
+            samples = None
+        elif into is None:
+            samples = torch.empty(n, C, D, dtype=torch.float64, device=self.device)
+        elif into.dtype != torch.float64 or into.device != self.device or not into.is_contiguous() or into.numel() < n * C * D:
             raise ValueError(f"samples buffer must be a contiguous float64 tensor on {self.device} with at least "
                              f"{n * C * D} elements")
-        return into.reshape(-1)[:n * C * D].reshape(n, C, D)
+        else:
+            samples = into.reshape(-1)[:n * C * D].reshape(n, C, D)
+        return (samples, torch.empty(n, C, dtype=torch.float64, device=self.device),
+                torch.empty(n, C, dtype=torch.int32, device=self.device))
 
     def hmc_sample(self, rng, eps, L, thr, n, q, U, g, keep_samples=True, into=None):
         C, D = q.shape
         self.ensure_workspace(C, 1)
         out, c = self._diag(C, D, False)
-        dev = self.device
-        samples = self._samples_buffer(n, C, D, keep_samples, into)
-        acc = torch.empty(n, C, dtype=torch.float64, device=dev)
-        div = torch.empty(n, C, dtype=torch.int32, device=dev)
+        samples, acc, div = self._history_buffers(n, C, D, keep_samples, into)
         self._step_call(
             self.lib.aehmc_hmc_sample, "aehmc_hmc_sample",
             self.ctx, C, rng.data_ptr(), float(eps), int(L), float(thr), int(n), q.data_ptr(),
@@ -476,11 +479,8 @@ class Engine:
         C, D = q.shape
         self.ensure_workspace(C, max_exp)
         out, c = self._diag(C, D, True)
-        dev = self.device
-        samples = self._samples_buffer(n, C, D, keep_samples, into)
-        acc = torch.empty(n, C, dtype=torch.float64, device=dev)
-        div = torch.empty(n, C, dtype=torch.int32, device=dev)
-        total = torch.zeros(C, dtype=torch.int64, device=dev)
+        samples, acc, div = self._history_buffers(n, C, D, keep_samples, into)
+        total = torch.zeros(C, dtype=torch.int64, device=self.device)
         self._step_call(
             self.lib.aehmc_nuts_sample, "aehmc_nuts_sample",
             self.ctx, C, rng.data_ptr(), float(eps), int(max_exp), float(thr), int(n), q.data_ptr(),
@@ -490,37 +490,30 @@ class Engine:
         out["n_leapfrog"] = total
         return out
 
-    def nuts_warmup(self, rng, schedule, target_accept, max_exp, thr, q, U, g, st, cstate, imm_param):
-        """The whole window-adaptation loop in one C-ABI call (no Python between warm-up steps)."""
+    def _warmup(self, nuts, pooled, rng, schedule, target_accept, length, thr, q, U, g, st, cstate, imm):
+        """The whole window-adaptation loop around a NUTS (``length``: max_num_expansions) or HMC (``length``:
+        num_integration_steps) kernel in one C-ABI call (no Python between warm-up steps).  The adaptation state's own
+        arrays are bound as the step sizes and as the metric -- per chain (``imm``: a PerChain), or ``pooled`` the SHARED
+        one -- because the update kernels rewrite them in place."""
         C, D = q.shape
-        out, c = self._diag(C, D, True)
+        out, c = self._diag(C, D, nuts)
         n = len(schedule)
         stage = (ct.c_int32 * n)(*[int(s) for s, _ in schedule])
         wend = (ct.c_int32 * n)(*[int(bool(e)) for _, e in schedule])
-        # bind the adaptation state's own arrays: the update kernel rewrites them in place
-        self.set_metric(imm_param, D)
-        self.ensure_workspace(C, max_exp)  # (after the metric: a dense one needs more work vectors)
-        self._keep["eps"] = st["step_size"]
-        self._check(self.lib.aehmc_set_step_sizes(self.ctx, st["step_size"].data_ptr(), C), "aehmc_set_step_sizes")
-        self._step_call(self.lib.aehmc_nuts_warmup, "aehmc_nuts_warmup", self.ctx, C, rng.data_ptr(), n, stage, wend,
-                        float(target_accept), int(max_exp), float(thr), q.data_ptr(), U.data_ptr(), g.data_ptr(),
-                        ct.byref(c), ct.byref(cstate), self.stream)
-        return out
-
-    def hmc_warmup(self, rng, schedule, target_accept, L, thr, q, U, g, st, cstate, imm_param):
-        """window_adaptation.run around an HMC kernel in one C-ABI call (no Python between warm-up steps)."""
-        C, D = q.shape
-        out, c = self._diag(C, D, False)
-        n = len(schedule)
-        stage = (ct.c_int32 * n)(*[int(s) for s, _ in schedule])
-        wend = (ct.c_int32 * n)(*[int(bool(e)) for _, e in schedule])
-        self.set_metric(imm_param, D)
-        self.ensure_workspace(C, 1)
-        self._keep["eps"] = st["step_size"]
-        self._check(self.lib.aehmc_set_step_sizes(self.ctx, st["step_size"].data_ptr(), C), "aehmc_set_step_sizes")
-        self._step_call(self.lib.aehmc_hmc_warmup, "aehmc_hmc_warmup", self.ctx, C, rng.data_ptr(), n, stage, wend,
-                        float(target_accept), int(L), float(thr), q.data_ptr(), U.data_ptr(), g.data_ptr(),
-                        ct.byref(c), ct.byref(cstate), self.stream)
+        if pooled:
+            self.set_metric(imm, D, force=True, sqrt_mass=st["sqrt_mass"])
+        else:
+            self.set_metric(imm, D)
+        self.ensure_workspace(C, length if nuts else 1)  # (after the metric: a dense one needs more work vectors)
+        self._bind_step_sizes(st["step_size"])
+        what = f"aehmc_{'nuts' if nuts else 'hmc'}_warmup{'_pooled' if pooled else ''}"
+        try:
+            self._step_call(getattr(self.lib, what), what, self.ctx, C, rng.data_ptr(), n, stage, wend,
+                            float(target_accept), int(length), float(thr), q.data_ptr(), U.data_ptr(), g.data_ptr(),
+                            ct.byref(c), ct.byref(cstate), self.stream)
+        finally:
+            if pooled:
+                self.forget_metric()
         return out
 
     def leapfrog(self, eps, nsteps, q, p, U, g):
@@ -595,7 +588,11 @@ class Engine:
                   sqrt_mass=torch.empty(mat, dtype=f64, device=dev))
         if full and D > 64:  # scratch of the window-end factorisation (LDS holds it up to D = 64)
             st["work"] = torch.empty(mat, dtype=f64, device=dev)
-        return st, _lib.CAdaptState(full=int(bool(full)), **{k: v.data_ptr() for k, v in st.items()})
+        return st, self.adapt_cstate(st, full)
+
+    @staticmethod
+    def adapt_cstate(st, full):
+        return _lib.CAdaptState(full=int(bool(full)), **{k: v.data_ptr() for k, v in st.items()})
 
     def adapt_init(self, C, D, initial_step_size, cstate):
         self._check(self.lib.aehmc_adapt_init(self.ctx, C, D, float(initial_step_size), ct.byref(cstate),
@@ -641,28 +638,6 @@ class Engine:
                                            delta.data_ptr() if delta is not None else None, S.data_ptr(), S.stride(0),
                                            self.stream), "aehmc_syrk_tn")
         return S
-
-    def warmup_pooled(self, nuts, rng, schedule, target_accept, max_exp_or_L, thr, q, U, g, st, cstate, imm):
-        """The pooled window-adaptation loop in one C-ABI call: the state's own arrays bound as the SHARED metric and as
-        the step sizes, which the update kernels rewrite in place."""
-        C, D = q.shape
-        out, c = self._diag(C, D, nuts)
-        n = len(schedule)
-        stage = (ct.c_int32 * n)(*[int(s) for s, _ in schedule])
-        wend = (ct.c_int32 * n)(*[int(bool(e)) for _, e in schedule])
-        self.set_metric(imm, D, force=True, sqrt_mass=st["sqrt_mass"])
-        self.ensure_workspace(C, max_exp_or_L if nuts else 1)
-        self._keep["eps"] = st["step_size"]
-        self._check(self.lib.aehmc_set_step_sizes(self.ctx, st["step_size"].data_ptr(), C), "aehmc_set_step_sizes")
-        fn, what = ((self.lib.aehmc_nuts_warmup_pooled, "aehmc_nuts_warmup_pooled") if nuts else
-                    (self.lib.aehmc_hmc_warmup_pooled, "aehmc_hmc_warmup_pooled"))
-        try:
-            self._step_call(fn, what, self.ctx, C, rng.data_ptr(), n, stage, wend, float(target_accept),
-                            int(max_exp_or_L), float(thr), q.data_ptr(), U.data_ptr(), g.data_ptr(), ct.byref(c),
-                            ct.byref(cstate), self.stream)
-        finally:
-            self.forget_metric()
-        return out
 
     def forget_metric(self):
         """Drop the cache entry of the current shared-metric binding: its arrays were rewritten in place by a kernel

@@ -8,11 +8,11 @@ the mean acceptance probability into dual averaging, a batch Welford update per 
 values, which the kernels take on their shared-metric routes."""
 from __future__ import annotations
 
-from typing import Dict, List, NamedTuple, Optional, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
-from ._common import Layout
+from ._common import Layout, bind_target, diagnostics
 from .engine import PerChain, _dev_f64, get_engine
 from .integrators import IntegratorState
 from .step_size import DualAveragingState
@@ -42,6 +42,47 @@ def build_schedule(num_steps: int, initial_buffer_size: int = 75, final_buffer_s
     return labels + [(0, False)] * (num_steps - slow_end)
 
 
+def _layout(position, num_chains=None, batched=None):
+    """``(Layout, the chain position is a scalar)`` of a position; without ``batched`` a leading chain axis is read off
+    ``num_chains`` being given or the position being 2-D."""
+    shape = tuple(position.shape)
+    if batched is None:
+        batched = num_chains is not None or len(shape) == 2
+    layout = Layout(shape, batched, num_chains if num_chains is not None else (shape[0] if batched else 1))
+    return layout, layout.scalar
+
+
+class _Adaptation(NamedTuple):
+    """The engine calls of an adaptation: one state per chain, or the pooled one."""
+    alloc: Callable
+    init: Callable
+    update: Callable
+    cstate: Callable
+
+
+def _adaptation(eng, pooled) -> _Adaptation:
+    if pooled:
+        return _Adaptation(eng.pooled_adapt_alloc, eng.pooled_adapt_init, eng.pooled_adapt_update, eng.pooled_cstate)
+    return _Adaptation(eng.adapt_alloc, eng.adapt_init, eng.adapt_update, eng.adapt_cstate)
+
+
+def _start(eng, pooled, layout, full, initial_step_size):
+    """A fresh adaptation state ``(arrays, C struct)``: identity metric, dual averaging started at ``initial_step_size``."""
+    ad = _adaptation(eng, pooled)
+    st, cst = ad.alloc(layout.C, layout.D, full)
+    ad.init(layout.C, layout.D, float(initial_step_size), cst)
+    return st, cst
+
+
+def _params(pooled, layout, scalar_position, st):
+    """The state's arrays as the kernel's ``(step_size, inverse_mass_matrix)``: ``PerChain`` values, or pooled the step
+    size as ``PerChain([C])`` with all entries equal and the shared metric as a plain tensor."""
+    if pooled:
+        return PerChain(st["step_size"]), (st["imm"].reshape(()) if scalar_position else st["imm"])
+    return (PerChain(layout.per_chain(st["step_size"])),
+            PerChain(st["imm"].reshape(layout.C) if scalar_position else st["imm"], st["sqrt_mass"]))
+
+
 def run(kernel, initial_state: IntegratorState, num_steps=1000, *, is_mass_matrix_full=False,
         initial_step_size=1.0, target_acceptance_rate=0.80, fused=True, num_integration_steps=None,
         pooled=False) -> Tuple[IntegratorState, Tuple, Dict]:
@@ -69,116 +110,58 @@ def run(kernel, initial_state: IntegratorState, num_steps=1000, *, is_mass_matri
         raise ValueError("window_adaptation.run with an HMC kernel needs num_integration_steps")
     extra = () if num_integration_steps is None else (int(num_integration_steps),)
     eng = get_engine()
-    if pooled:
-        return _run_pooled(eng, kernel, initial_state, int(num_steps), bool(is_mass_matrix_full),
-                           float(initial_step_size), float(target_acceptance_rate), bool(fused), extra)
+    target = float(target_acceptance_rate)
     pos = initial_state.position
-    srng_chains = getattr(kernel, "num_chains", None)
-    batched = getattr(kernel, "batched", pos.ndim == 2)
-    layout = Layout(tuple(pos.shape), batched, srng_chains or (pos.shape[0] if batched else 1))
+    layout, scalar_position = _layout(pos, getattr(kernel, "num_chains", None) or None,
+                                      getattr(kernel, "batched", pos.ndim == 2))
     C, D = layout.C, layout.D
-    scalar_position = (len(layout.user_shape) - (1 if batched else 0)) == 0
     full = bool(is_mass_matrix_full) and not scalar_position  # mass_matrix.py:54-57: a scalar stays a scalar
-    if full and D > 2048:  # one wavefront factors each chain's matrix (tests: up to D = 1024)
+    if full and not pooled and D > 2048:  # one wavefront factors each chain's matrix (tests: up to D = 1024)
         raise ValueError("is_mass_matrix_full keeps one dense D x D matrix per chain (as the reference does) and "
                          "is supported up to D = 2048")
-    st, cst = eng.adapt_alloc(C, D, full)
-    eng.adapt_init(C, D, float(initial_step_size), cst)
+    st, cst = _start(eng, pooled, layout, full, initial_step_size)
     schedule = build_schedule(int(num_steps))
-
-    def imm_param():
-        return PerChain(st["imm"].reshape(C) if scalar_position else st["imm"], st["sqrt_mass"])
-
+    # The transitions read the state's own arrays, which the update kernels rewrite in place -- pooled: the step size from
+    # all C entries of ``step_size``, so that no value returns to the host between steps, the metric as a SHARED one
+    # (one object: Engine.set_metric keys it by identity).  One ``PerChain`` pair serves every step of the per-chain loop
+    # too: with ``sqrt_mass`` handed over the engine keeps nothing by the object's identity, it binds the arrays each call.
+    eps = PerChain(st["step_size"])
+    _, imm = _params(pooled, layout, scalar_position, st)
     nk = getattr(kernel, "_nuts", None)
-    if fused and nk is not None and len(schedule) > 0:
-        from ._common import diagnostics, state_rows
-        from .engine import rng_to_device
-        if "rng" not in nk["holder"] or nk["holder"]["rng"].device != eng.device:  # (uploaded at construction, maybe elsewhere)
-            nk["holder"]["rng"] = (nk["holder"]["rng"].to(eng.device) if "rng" in nk["holder"]
-                                   else rng_to_device(nk["rng_host"], eng.device))
-        q, U, g = state_rows(initial_state, layout, eng.device)
-        eng.set_target(nk["logprob_fn"], D)
-        out = eng.nuts_warmup(nk["holder"]["rng"], schedule, float(target_acceptance_rate),
-                              nk["max_num_expansions"], nk["divergence_threshold"], q, U, g, st, cst, imm_param())
-        info = diagnostics(layout, q, U, g, out, True)
-        state, updates = info.state._replace(momentum=None), {nk["srng"]: nk["holder"]["rng"]}
-        schedule = []
-    elif fused and getattr(kernel, "_hmc", None) is not None and len(schedule) > 0:
-        from ._common import diagnostics, state_rows
-        from .engine import rng_to_device
-        hk = kernel._hmc
-        if "rng" not in hk["holder"] or hk["holder"]["rng"].device != eng.device:
-            hk["holder"]["rng"] = (hk["holder"]["rng"].to(eng.device) if "rng" in hk["holder"]
-                                   else rng_to_device(hk["rng_host"], eng.device))
-        q, U, g = state_rows(initial_state, layout, eng.device)
-        eng.set_target(hk["logprob_fn"], D)
-        out = eng.hmc_warmup(hk["holder"]["rng"], schedule, float(target_acceptance_rate), extra[0],
-                             hk["divergence_threshold"], q, U, g, st, cst, imm_param())
-        info = diagnostics(layout, q, U, g, out, False)
-        state, updates = info.state._replace(momentum=None), {hk["srng"]: hk["holder"]["rng"]}
-        schedule = []
-    else:
-        state, updates = initial_state, {}
-    for i, (stage, window_end) in enumerate(schedule):
-        info, updates = kernel(state, PerChain(st["step_size"]), imm_param(), *extra)
-        state = info.state._replace(momentum=None)
-        eng.adapt_update(C, D, stage, window_end, i == len(schedule) - 1, float(target_acceptance_rate),
-                         info.acceptance_probability.reshape(C).contiguous(),
-                         state.position.reshape(C, D).contiguous(), cst)
-    step_size = st["step_size"].clone()
-    imm, sqrt_mass = st["imm"].clone(), st["sqrt_mass"].clone()
-    return state, (PerChain(layout.per_chain(step_size)),
-                   PerChain(imm.reshape(C) if scalar_position else imm, sqrt_mass)), updates
-
-
-def _run_pooled(eng, kernel, initial_state, num_steps, is_mass_matrix_full, initial_step_size, target, fused, extra):
-    """``run(..., pooled=True)``: the loop of ``run`` around ONE adaptation state (Engine.pooled_adapt_alloc).  The
-    transitions read the state's own arrays -- the step size from all C entries of ``step_size``, bound as per-chain
-    step sizes so that no value returns to the host between steps, the metric as a SHARED one -- and after a window end
-    the metric is bound again (``force=True``: a kernel's in-place rewrite does not move ``_version``)."""
-    pos = initial_state.position
-    srng_chains = getattr(kernel, "num_chains", None)
-    batched = getattr(kernel, "batched", pos.ndim == 2)
-    layout = Layout(tuple(pos.shape), batched, srng_chains or (pos.shape[0] if batched else 1))
-    C, D = layout.C, layout.D
-    scalar_position = (len(layout.user_shape) - (1 if batched else 0)) == 0
-    full = is_mass_matrix_full and not scalar_position  # mass_matrix.py:54-57: a scalar stays a scalar
-    st, cst = eng.pooled_adapt_alloc(C, D, full)
-    eng.pooled_adapt_init(C, D, initial_step_size, cst)
-    schedule = build_schedule(num_steps)
-    imm = st["imm"].reshape(()) if scalar_position else st["imm"]  # (one object: Engine.set_metric keys it by identity)
-    nk, hk = getattr(kernel, "_nuts", None), getattr(kernel, "_hmc", None)
-    k = nk if nk is not None else hk
+    k = nk if nk is not None else getattr(kernel, "_hmc", None)
     if fused and k is not None and len(schedule) > 0:
-        from ._common import diagnostics, state_rows
-        from .engine import rng_to_device
-        if "rng" not in k["holder"] or k["holder"]["rng"].device != eng.device:
-            k["holder"]["rng"] = (k["holder"]["rng"].to(eng.device) if "rng" in k["holder"]
-                                  else rng_to_device(k["rng_host"], eng.device))
-        q, U, g = state_rows(initial_state, layout, eng.device)
-        eng.set_target(k["logprob_fn"], D)
-        out = eng.warmup_pooled(nk is not None, k["holder"]["rng"], schedule, target,
-                                nk["max_num_expansions"] if nk is not None else extra[0], k["divergence_threshold"],
-                                q, U, g, st, cst, imm)
+        # (no ``scalar`` for set_target here: a Python function not yet traced is read as the kernels' own calls leave it)
+        q, U, g = bind_target(k, eng, initial_state, layout, None)
+        out = eng._warmup(nk is not None, pooled, k["holder"]["rng"], schedule, target,
+                          nk["max_num_expansions"] if nk is not None else extra[0], k["divergence_threshold"],
+                          q, U, g, st, cst, imm)
         info = diagnostics(layout, q, U, g, out, nk is not None)
         state, updates = info.state._replace(momentum=None), {k["srng"]: k["holder"]["rng"]}
     else:
         state, updates = initial_state, {}
+        update = _adaptation(eng, pooled).update
         try:
-            eng.set_metric(imm, D, force=True, sqrt_mass=st["sqrt_mass"])
+            # pooled: the metric is bound here, and again after a window end (``force``: a kernel's in-place rewrite does
+            # not move ``_version``)
+            if pooled:
+                eng.set_metric(imm, D, force=True, sqrt_mass=st["sqrt_mass"])
             for i, (stage, window_end) in enumerate(schedule):
-                info, updates = kernel(state, PerChain(st["step_size"]), imm, *extra)
+                info, updates = kernel(state, eps, imm, *extra)
                 state = info.state._replace(momentum=None)
-                eng.pooled_adapt_update(C, D, stage, window_end, i == len(schedule) - 1, target,
-                                        _dev_f64(info.acceptance_probability, eng.device).reshape(C).contiguous(),
-                                        _dev_f64(state.position, eng.device).reshape(C, D).contiguous(), cst)
-                if window_end:
+                update(C, D, stage, window_end, i == len(schedule) - 1, target,
+                       _dev_f64(info.acceptance_probability, eng.device).reshape(C).contiguous(),
+                       _dev_f64(state.position, eng.device).reshape(C, D).contiguous(), cst)
+                if pooled and window_end:
                     eng.set_metric(imm, D, force=True, sqrt_mass=st["sqrt_mass"])
         finally:
-            eng.forget_metric()
-    step_size = float(st["step_size"][0])  # the one read-back
-    out_imm = st["imm"].clone()
-    return state, (step_size, out_imm.reshape(()) if scalar_position else out_imm), updates
+            if pooled:
+                eng.forget_metric()
+    if pooled:
+        step_size = float(st["step_size"][0])  # the one read-back
+        imm = st["imm"].clone()
+        return state, (step_size, imm.reshape(()) if scalar_position else imm), updates
+    return state, _params(False, layout, scalar_position,
+                          {name: st[name].clone() for name in ("step_size", "imm", "sqrt_mass")}), updates
 
 
 class WarmupState(NamedTuple):
@@ -193,6 +176,17 @@ class WarmupState(NamedTuple):
     work: Optional[torch.Tensor] = None
     position_shape: Tuple = ()   # user-facing shape of the chain position and whether it has a leading chain axis
     batched: bool = False
+
+
+_FIELDS = ("da_step", "da_x", "da_x_avg", "da_g_avg", "da_mu", "wc_mean", "wc_m2", "wc_n", "step_size", "imm", "sqrt_mass")
+
+
+def _warmup_state(pooled, layout, scalar_position, st):
+    """``(WarmupState, parameters)`` over the arrays ``st`` of an adaptation state."""
+    ws = WarmupState(DualAveragingState(*(st[name] for name in _FIELDS[:5])), tuple(st[name] for name in _FIELDS[5:8]),
+                     st["step_size"], st["imm"], st["sqrt_mass"], st.get("work"), layout.user_shape,
+                     bool(layout.scalar_chain_shape))
+    return ws, _params(pooled, layout, scalar_position, st)
 
 
 def window_adaptation(num_steps: int, is_mass_matrix_full: bool = False, initial_step_size=1.0,
@@ -217,47 +211,14 @@ def window_adaptation(num_steps: int, is_mass_matrix_full: bool = False, initial
     as ``PerChain([C])`` with all entries equal (it stays on the device; ``float(p.value[0])`` reads it) and the shared
     inverse mass matrix as a plain tensor."""
     schedule = build_schedule(int(num_steps))
-    if pooled:
-        return _pooled_pair(schedule, bool(is_mass_matrix_full), float(initial_step_size),
-                            float(target_acceptance_rate))
-
-    def _layout(position, num_chains):
-        shape = tuple(position.shape)
-        batched = num_chains is not None or len(shape) == 2
-        C = (num_chains if num_chains is not None else shape[0]) if batched else 1
-        layout = Layout(shape, batched, C)
-        scalar_position = (len(shape) - (1 if batched else 0)) == 0
-        return layout, scalar_position
-
-    def _params(layout, scalar_position, ws: WarmupState):
-        C = layout.C
-        return (PerChain(layout.per_chain(ws.step_size)),
-                PerChain(ws.imm.reshape(C) if scalar_position else ws.imm, ws.sqrt_mass))
-
-    def _cstate(eng, ws: WarmupState, full):
-        from . import _lib
-        da, (mean, m2, n) = ws.da_state, ws.mm_state
-        ptr = dict(da_step=da.step, da_x=da.iterates, da_x_avg=da.iterates_avg, da_g_avg=da.gradient_avg,
-                   da_mu=da.shrinkage_pts, wc_mean=mean, wc_m2=m2, wc_n=n, step_size=ws.step_size, imm=ws.imm,
-                   sqrt_mass=ws.sqrt_mass)
-        if ws.work is not None:
-            ptr["work"] = ws.work
-        return _lib.CAdaptState(full=int(bool(full)), **{k: v.data_ptr() for k, v in ptr.items()})
+    target = float(target_acceptance_rate)
 
     def init(initial_chain_state: IntegratorState, num_chains: Optional[int] = None):
         """window_adaptation.py:130-143: identity metric, dual averaging started at ``initial_step_size`` (so the
         first step size is exp(0) = 1, algorithms.py:56-76)."""
-        eng = get_engine()
         layout, scalar_position = _layout(initial_chain_state.position, num_chains)
-        C, D = layout.C, layout.D
-        full = bool(is_mass_matrix_full) and not scalar_position
-        st, cst = eng.adapt_alloc(C, D, full)
-        eng.adapt_init(C, D, float(initial_step_size), cst)
-        ws = WarmupState(DualAveragingState(st["da_step"], st["da_x"], st["da_x_avg"], st["da_g_avg"], st["da_mu"]),
-                         (st["wc_mean"], st["wc_m2"], st["wc_n"]), st["step_size"], st["imm"], st["sqrt_mass"],
-                         st.get("work"), layout.user_shape, layout.C > 1 or num_chains is not None or
-                         len(layout.user_shape) == 2)
-        return ws, _params(layout, scalar_position, ws)
+        st, _ = _start(get_engine(), pooled, layout, bool(is_mass_matrix_full) and not scalar_position, initial_step_size)
+        return _warmup_state(pooled, layout, scalar_position, st)
 
     def update(step: int, warmup_state: WarmupState, parameters, chain_state):
         """window_adaptation.py:192-214 for warm-up step ``step`` (0-based) after the transition ``chain_state``."""
@@ -269,71 +230,17 @@ def window_adaptation(num_steps: int, is_mass_matrix_full: bool = False, initial
             raise ValueError(f"position has shape {tuple(position.shape)}, the warm-up was initialised with "
                              f"{tuple(warmup_state.position_shape)}")
         layout, scalar_position = _layout(position, C if warmup_state.batched else None)
-        D = layout.D
-        full = warmup_state.imm.ndim == 3
-        da, (mean, m2, n) = warmup_state.da_state, warmup_state.mm_state
-        ws = WarmupState(DualAveragingState(*(t.clone() for t in da)), (mean.clone(), m2.clone(), n.clone()),
-                         warmup_state.step_size.clone(), warmup_state.imm.clone(), warmup_state.sqrt_mass.clone(),
-                         warmup_state.work, warmup_state.position_shape, warmup_state.batched)
+        full = warmup_state.imm.ndim == (2 if pooled else 3)
+        da, mm = warmup_state.da_state, warmup_state.mm_state
+        old = zip(_FIELDS, (*da, *mm, warmup_state.step_size, warmup_state.imm, warmup_state.sqrt_mass))
+        st = {name: t.clone() for name, t in old}  # states are values
+        if warmup_state.work is not None:  # (scratch of the window-end factorisation, not state)
+            st["work"] = warmup_state.work
         stage, window_end = schedule[int(step)]
-        eng.adapt_update(C, D, stage, window_end, int(step) == len(schedule) - 1, float(target_acceptance_rate),
-                         _dev_f64(chain_state.acceptance_probability, eng.device).reshape(C).contiguous(),
-                         _dev_f64(position, eng.device).reshape(C, D).contiguous(), _cstate(eng, ws, full))
-        return ws, _params(layout, scalar_position, ws)
-
-    return init, update
-
-
-_POOLED_FIELDS = ("da_step", "da_x", "da_x_avg", "da_g_avg", "da_mu", "wc_mean", "wc_m2", "wc_n", "step_size", "imm",
-                  "sqrt_mass")
-
-
-def _pooled_pair(schedule, is_mass_matrix_full, initial_step_size, target):
-    """``window_adaptation(..., pooled=True)``: see there."""
-
-    def _shape(position, num_chains):
-        shape = tuple(position.shape)
-        batched = num_chains is not None or len(shape) == 2
-        C = (num_chains if num_chains is not None else shape[0]) if batched else 1
-        return Layout(shape, batched, C), (len(shape) - (1 if batched else 0)) == 0
-
-    def _ws(st, layout, batched):
-        return WarmupState(DualAveragingState(st["da_step"], st["da_x"], st["da_x_avg"], st["da_g_avg"], st["da_mu"]),
-                           (st["wc_mean"], st["wc_m2"], st["wc_n"]), st["step_size"], st["imm"], st["sqrt_mass"], None,
-                           layout.user_shape, batched)
-
-    def _params(scalar_position, ws):
-        return PerChain(ws.step_size), (ws.imm.reshape(()) if scalar_position else ws.imm)
-
-    def init(initial_chain_state: IntegratorState, num_chains: Optional[int] = None):
-        eng = get_engine()
-        layout, scalar_position = _shape(initial_chain_state.position, num_chains)
-        full = is_mass_matrix_full and not scalar_position
-        st, cst = eng.pooled_adapt_alloc(layout.C, layout.D, full)
-        eng.pooled_adapt_init(layout.C, layout.D, initial_step_size, cst)
-        ws = _ws(st, layout, layout.C > 1 or num_chains is not None or len(layout.user_shape) == 2)
-        return ws, _params(scalar_position, ws)
-
-    def update(step: int, warmup_state: WarmupState, parameters, chain_state):
-        del parameters  # (the arrays in warmup_state ARE the current parameters)
-        eng = get_engine()
-        position = chain_state.state.position
-        C = warmup_state.step_size.numel()
-        if tuple(position.shape) != tuple(warmup_state.position_shape):
-            raise ValueError(f"position has shape {tuple(position.shape)}, the warm-up was initialised with "
-                             f"{tuple(warmup_state.position_shape)}")
-        layout, scalar_position = _shape(position, C if warmup_state.batched else None)
-        D = layout.D
-        full = warmup_state.imm.ndim == 2
-        da, (mean, m2, n) = warmup_state.da_state, warmup_state.mm_state
-        old = dict(zip(_POOLED_FIELDS, (*da, mean, m2, n, warmup_state.step_size, warmup_state.imm,
-                                        warmup_state.sqrt_mass)))
-        st = {k: v.clone() for k, v in old.items()}  # states are values
-        stage, window_end = schedule[int(step)]
-        eng.pooled_adapt_update(C, D, stage, window_end, int(step) == len(schedule) - 1, target,
-                                _dev_f64(chain_state.acceptance_probability, eng.device).reshape(C).contiguous(),
-                                _dev_f64(position, eng.device).reshape(C, D).contiguous(), eng.pooled_cstate(st, full))
-        ws = _ws(st, layout, warmup_state.batched)
-        return ws, _params(scalar_position, ws)
+        ad = _adaptation(eng, pooled)
+        ad.update(C, layout.D, stage, window_end, int(step) == len(schedule) - 1, target,
+                  _dev_f64(chain_state.acceptance_probability, eng.device).reshape(C).contiguous(),
+                  _dev_f64(position, eng.device).reshape(C, layout.D).contiguous(), ad.cstate(st, full))
+        return _warmup_state(pooled, layout, scalar_position, st)
 
     return init, update
