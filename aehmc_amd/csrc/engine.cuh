@@ -89,6 +89,10 @@ struct EngineArgs {
   double *psum, *psub;
   double *ckp, *cks, *ckv;          // [max_exp][C][D]
   double *vhalf, *rbuf, *zbuf;
+  // whitened NUTS lock-step, "dense_whiten_ahead" (k_step_white_ahead): the half-step momentum p_half has a vector of
+  // its own (cur_p always holds a full-step p'), and cur_q / rbuf are a ping-pong pair of position buffers -- cur_q the
+  // chain's current point, rbuf the one the next product multiplies; the host swaps the two after every lock-step
+  double *phalf;
   double *linreg_part;  // [ceil(C/8)][S][16] slice sums of the regression target
   ChainCtl *ctl;
   // dense metric, "linear" mode: w = imm g is carried with the state so that
@@ -547,17 +551,23 @@ __device__ inline void nuts_book(const EngineArgs &a, long long c, int lane, Cha
                 }
               });
     ct.U_cur = target_finish(a, wave_sum(usum));
-  } else if (FUSE == 3) {
+  } else if (FUSE == 3 || FUSE == 4) {
     // identity metric, dense target (whitened mode, engine.hip): leap_stages<0,0,1> on the fly -- p' = p_half - b g',
-    // U' = 0.5 r.g' -- then the bookkeeping pass and the first U-turn level of an odd step, as FUSE = 1 does
+    // U' = 0.5 r.g' -- then the bookkeeping pass and the first U-turn level of an odd step, as FUSE = 1 does.
+    // FUSE = 4 ("dense_whiten_ahead"): r = z' is read from cur_q (the same bits: the whitened mu is 0.0), p_half from
+    // its own vector, and the element's next half step is formed AHEAD of the tree's decision from the p', g', z' in
+    // registers -- leap_stages<1,1,0>'s expressions on the values it would load: p_half'' = p' - b g' in place,
+    // z'' = z' + aa v(p_half'') into the other position buffer.  k_step_white_ahead says when that work stands.
+    constexpr bool AHEAD = FUSE == 4;
     const double step_size = (ct.dir ? 1.0 : -1.0) * (a.eps_c ? a.eps_c[c] : a.eps);
-    const double b = 0.5 * step_size;
+    const double b = 0.5 * step_size, aa = 1 * step_size;
     const double *kp = a.ckp + ((size_t)tmax * a.C + c) * a.D;
     const double *ks = a.cks + ((size_t)tmax * a.C + c) * a.D;
+    const double *zin = AHEAD ? a.cur_q : a.rbuf, *pin = AHEAD ? a.phalf : a.cur_p;
     double usum = 0.0;
     wave_pass(a.D, lane,
               [&](long long i) {
-                return Ld6{a.cur_g[row + i], a.rbuf[row + i], a.cur_p[row + i], step == 0 ? 0.0 : a.psub[row + i],
+                return Ld6{a.cur_g[row + i], zin[row + i], pin[row + i], step == 0 ? 0.0 : a.psub[row + i],
                            f_turn ? kp[i] : 0.0, f_turn ? ks[i] : 0.0};
               },
               [&](long long i, const Ld6 &x) {
@@ -579,6 +589,11 @@ __device__ inline void nuts_book(const EngineArgs &a, long long c, int lane, Cha
                   const double rho = sub - (p + pl) / 2;
                   f_dl += vl * rho;
                   f_dr += v * rho;
+                }
+                if (AHEAD) {                            // leap_stages<1,1,0> of the next leapfrog
+                  const double ph = p - b * x.a;
+                  a.phalf[row + i] = ph;
+                  a.rbuf[row + i] = x.b + aa * vel_diag(a, c, i, ph);
                 }
               });
     ct.U_cur = target_finish(a, wave_sum(usum));
@@ -987,6 +1002,46 @@ AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_step_white(EngineArgs a)
     __threadfence_block();
     double U_next = 0.0;
     (void)leap_stages<true, true, false, false>(a, c, lane, ct.dir, U_next);  // (dense target: no U here)
+  }
+  if (lane == 0) a.ctl[c] = ct;
+}
+
+// "dense_whiten_ahead": the first two stages of a whitened leapfrog from the chain's full-step state -- leap_stages<1,1,0>'s
+// expressions, with p_half and the new position written beside cur_p and cur_q instead of over them
+__device__ __forceinline__ void white_half_step(const EngineArgs &a, long long c, int lane, int dir) {
+  const double step_size = (dir ? 1.0 : -1.0) * (a.eps_c ? a.eps_c[c] : a.eps);
+  const double b = 0.5 * step_size, aa = 1 * step_size;
+  const size_t row = (size_t)c * a.D;
+  wave_pass(a.D, lane,
+            [&](long long i) { return Ld3{a.cur_p[row + i], a.cur_g[row + i], a.cur_q[row + i]}; },
+            [&](long long i, const Ld3 &x) {
+              const double ph = x.a - b * x.b;
+              a.phalf[row + i] = ph;
+              a.rbuf[row + i] = x.c + aa * vel_diag(a, c, i, ph);
+            });
+}
+// first lock-step of a transition (in place of k_step<true, true, false, false, false>)
+AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_white_half_step(EngineArgs a) {
+  AEHMC_CHAIN_OF_WAVE();
+  const ChainCtl ct = a.ctl[c];
+  if (ct.done) return;
+  white_half_step(a, c, lane, ct.dir);
+}
+// k_step_white with the next half step formed inside the bookkeeping pass (nuts_book FUSE = 4).  That work stands unless
+// the chain is done (its rows are never read again) or its direction changed -- exactly when nuts_begin_expansion has
+// rewritten the cur_* rows; the phantom continuation after a finalised step 0 follows the same rule.  A live chain that
+// turned round forms the half step from its new rows.
+AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_step_white_ahead(EngineArgs a) {
+  AEHMC_CHAIN_OF_WAVE();
+  ChainCtl ct = a.ctl[c];
+  if (ct.done) return;
+  ChainRng rng = rng_load(a, c);
+  const int dir = ct.dir;
+  nuts_book<false, 4>(a, c, lane, ct, rng);
+  rng_store(a, c, lane, rng, 1, 3);
+  if (!ct.done && ct.dir != dir) {
+    __threadfence_block();
+    white_half_step(a, c, lane, ct.dir);
   }
   if (lane == 0) a.ctl[c] = ct;
 }

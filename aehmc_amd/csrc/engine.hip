@@ -138,6 +138,8 @@ struct aehmc_ctx {
   // chain whose incoming state is that record, bit for bit.  Dropped (carry_drop) by whatever may write those vectors
   // or change what they mean.
   bool opt_dense_whiten_carry = true;
+  // whitened NUTS lock-step: the next half step is formed inside the bookkeeping pass (k_step_white_ahead)
+  bool opt_dense_whiten_ahead = true;
   struct {
     bool valid = false;
     int64_t C = 0, D = 0;
@@ -1326,6 +1328,11 @@ extern "C" int aehmc_set_option(aehmc_ctx *ctx, const char *name, int64_t value)
     ctx->opt_dense_whiten_carry = value != 0;
     return 0;
   }
+  if (!strcmp(name, "dense_whiten_ahead")) {
+    if (ctx->opt_dense_whiten_ahead != (value != 0)) carry_drop(ctx);
+    ctx->opt_dense_whiten_ahead = value != 0;
+    return 0;
+  }
   if (!strcmp(name, "gemm_small_tiles")) {
     ctx->opt_gemm_small = (int)value;
     return 0;
@@ -1761,7 +1768,9 @@ struct WhiteBufs {
 // With "dense_whiten_carry" the two products run on the chains whose incoming state is not the carry record's
 // (k_white_match, k_compact: all of them when there is no record, none in a chained run); the others keep the z and
 // H z the previous transition ended on.  Decided on the device, per chain, by content.
-static int white_begin(aehmc_ctx *ctx, const EngineArgs &a, EngineArgs &b, WhiteBufs &w, hipStream_t st) {
+// `ahead` (NUTS, "dense_whiten_ahead"): the half-step momentum gets a vector of its own -- vhalf, which only the literal
+// dense mode uses.
+static int white_begin(aehmc_ctx *ctx, const EngineArgs &a, EngineArgs &b, WhiteBufs &w, hipStream_t st, bool ahead = false) {
   if (int rc = white_prepare(ctx, st)) {  // (settles a pending record: valid again, or dropped)
     carry_drop(ctx);
     return rc;
@@ -1799,6 +1808,7 @@ static int white_begin(aehmc_ctx *ctx, const EngineArgs &a, EngineArgs &b, White
   for (int e = 0; e < 2; e++) b.end_v[e] = b.end_w[e] = nullptr;
   b.q = w.z; b.g = w.hz; b.U = w.Uw;
   b.out.momentum = w.r;
+  b.phalf = ahead ? a.vhalf : nullptr;
   return 0;
 }
 // p = L^-T r (today's momentum product), q = mu + L z, then (U, g) evaluated afresh at q as aehmc_new_state does; a
@@ -1882,6 +1892,23 @@ static int launch_leapfrog(aehmc_ctx *ctx, const EngineArgs &a, bool book, bool 
   if (need_v || book)
     if (metric_mul(ctx, C, a.cur_p, ctx->met.imm, a.cur_v, st, ri, nr)) return -1;
   if (book) LAUNCH((k_step<false, false, false, true, true>), C, st, a);
+  return 0;
+}
+
+// One lock-step of the whitened NUTS loop under "dense_whiten_ahead": `GEMM | stage`, the stage being
+// k_step_white_ahead.  a.cur_q holds every live chain's current point and a.rbuf receives the position the next product
+// multiplies, so the two pointers change places after every kernel that writes the latter: the first lock-step's
+// k_white_half_step, then each stage launch.  (The caller's copy of the arguments is the one that is swapped.)
+static int launch_white_ahead(aehmc_ctx *ctx, EngineArgs &a, hipStream_t st, const int *ri, const int *nr) {
+  const int64_t C = a.C, D = a.D;
+  if (!ctx->pre_done) {
+    LAUNCH(k_white_half_step, C, st, a);
+    std::swap(a.cur_q, a.rbuf);
+    ctx->pre_done = true;
+  }
+  if (gemm(ctx, C, D, D, a.cur_q, D, a.white_prec, D, a.cur_g, D, st, ri, nr)) return -1;
+  LAUNCH(k_step_white_ahead, C, st, a);
+  std::swap(a.cur_q, a.rbuf);
   return 0;
 }
 
@@ -2216,8 +2243,9 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
   EngineArgs wa;  // whitened mode: the transition runs on the whitened problem (white_begin), mapped back at the end
   WhiteBufs wb{};
   if (white)
-    if (int rc = white_begin(ctx, a, wa, wb, st)) return rc;
-  const EngineArgs &e = white ? wa : a;
+    if (int rc = white_begin(ctx, a, wa, wb, st, ctx->opt_dense_whiten_ahead)) return rc;
+  EngineArgs &e = white ? wa : a;
+  const bool ahead = white && e.phalf;
   ctx->fuse_pre = a.linear != 0 || white;
   ctx->pre_done = false;
   if (int rc = launch_begin(ctx, e, true, st)) return rc;
@@ -2242,7 +2270,7 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
     }
     const int slot = batch % NRING;
     for (int k = 0; k < STEP_BATCH && s < maxsteps; k++, s++) {
-      if (int rc = launch_leapfrog(ctx, e, true, true, st, ri, nr)) return rc;
+      if (int rc = ahead ? launch_white_ahead(ctx, e, st, ri, nr) : launch_leapfrog(ctx, e, true, true, st, ri, nr)) return rc;
       if (compact) {
         const bool last = (k == STEP_BATCH - 1) || (s == maxsteps - 1);
         hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, st, (const ChainCtl *)a.ctl,

@@ -247,6 +247,12 @@ int aehmc_set_metric(aehmc_ctx *ctx, const aehmc_metric *metric);
  *                   has compared it).  The record is dropped by anything that replaces the workspace or may write it (any other call that uses the workspace, another chain count or tree
  *                   depth).  Same discrete outputs, reals equal up to rounding (z is not rounded through q).
  *                   0 = every transition maps in from q
+ *  "dense_whiten_ahead" 1  whitened mode, NUTS: the lock-step's bookkeeping pass also forms the chain's next half step
+ *                   (p_half, z') from the values it holds, in a momentum vector of its own and a second position
+ *                   buffer (two workspace vectors the mode left unused: the workspace does not grow), instead of a
+ *                   second pass that reads them back; a chain that turns round forms it from its new rows.  The same
+ *                   operations on the same bits: every output and the generator states equal 0's bit for bit.
+ *                   0 = the two-pass stage
  *  "gemm_small_tiles" 1  fp64 GEMM of a mid-size problem (fewer than 256 tiles of 128 x 128, N <= 2048):
  *                   1 = 64 x 128, 64 x 64 or 32 x 64 tiles, the largest that gives every CU two
  *                   workgroups (bitwise the results of the 128 x 128 kernel); 2 / 3 / 4 force
