@@ -35,6 +35,11 @@ class CPooledAdaptState(ct.Structure):
                                            "sqrt_mass")] + [("full", ct.c_int32), ("reserved", ct.c_int32)]
 
 
+class CCheesState(ct.Structure):
+    _fields_ = [(n, ct.c_void_p) for n in ("step", "log_T", "log_T_avg", "adam_m", "adam_v", "h", "num_steps",
+                                           "da_step", "da_x", "da_x_avg", "da_g_avg", "da_mu", "step_size", "sums")]
+
+
 class CDiagnostics(ct.Structure):
     _fields_ = [("momentum", ct.c_void_p), ("acceptance_probability", ct.c_void_p),
                 ("num_doublings", ct.c_void_p), ("is_turning", ct.c_void_p),
@@ -63,6 +68,9 @@ SYMBOLS = {
     "aehmc_pooled_adapt_init": (_I, [_P, _I64, _I64, _D, ct.POINTER(CPooledAdaptState), _P]),
     "aehmc_pooled_adapt_update": (_I, [_P, _I64, _I64, ct.c_int32, ct.c_int32, ct.c_int32, _D, _P, _P,
                                        ct.POINTER(CPooledAdaptState), _P]),
+    "aehmc_chees_init": (_I, [_P, _I64, _D, _D, ct.POINTER(CCheesState), _P]),
+    "aehmc_chees_update": (_I, [_P, _I64, _I64, ct.c_int32, _D, _D, _I64, _P, _P, _P, _P, _D, _P, _P,
+                                ct.POINTER(CCheesState), _P]),
     "aehmc_dual_averaging_update": (_I, [_P, _I64, _D, _D, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P]),
     "aehmc_welford_update": (_I, [_P, _I64, _I64, ct.c_int32, _P, _P, _P, _P, _P]),
     "aehmc_covariance_final": (_I, [_P, _I64, _I64, ct.c_int32, ct.c_int32, _P, _P, _P, _P]),

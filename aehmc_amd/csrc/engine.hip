@@ -29,6 +29,7 @@
 #include "nuts_wide.cuh"
 #include "nuts_pc_dense.cuh"
 #include "pooled_adapt.cuh"
+#include "chees.cuh"
 
 using namespace aehmc;
 
@@ -104,6 +105,8 @@ struct aehmc_ctx {
   size_t fd_ws_bytes = 0;
   double *pool_work = nullptr;  // pooled window adaptation: partial column sums, batch mean, delta (kept, grown)
   size_t pool_work_bytes = 0;
+  double *chees_work = nullptr;  // ChEES warm-up: partial column sums, the two means, the per-chain criterion (kept, grown)
+  size_t chees_work_bytes = 0;
   double *syrk_work = nullptr;  // symmetric rank-C update of a mid-size D: the parts of the chain range (kept, grown)
   size_t syrk_work_bytes = 0;
   double *blk_pack = nullptr;  // block-resident dense kernels: the launch's matrices zero-padded to [Dp][Dp] (kept, grown)
@@ -268,6 +271,7 @@ extern "C" int aehmc_destroy(aehmc_ctx *ctx) {
   if (ctx->fd_ws) (void)hipFree(ctx->fd_ws);
   if (ctx->blk_pack) (void)hipFree(ctx->blk_pack);
   if (ctx->pool_work) (void)hipFree(ctx->pool_work);
+  if (ctx->chees_work) (void)hipFree(ctx->chees_work);
   if (ctx->syrk_work) (void)hipFree(ctx->syrk_work);
   if (ctx->d_cparams) (void)hipFree(ctx->d_cparams);
   if (ctx->glm_XT) (void)hipFree(ctx->glm_XT);
@@ -1029,6 +1033,54 @@ extern "C" int aehmc_pooled_adapt_update(aehmc_ctx *ctx, int64_t C, int64_t D, i
     }
   }
   HIPCHK(tu::pool_scalars(a, st));
+  return 0;
+}
+
+// ---- ChEES warm-up: trajectory length and step size from all chains (chees.cuh) ----
+static int chees_args(aehmc_ctx *ctx, int64_t C, int64_t D, const aehmc_chees_state *s, CheesArgs &a) {
+  if (!s || C <= 0 || D <= 0) FAIL("chees: bad arguments");
+  if (!s->step || !s->log_T || !s->log_T_avg || !s->adam_m || !s->adam_v || !s->h || !s->num_steps || !s->da_step ||
+      !s->da_x || !s->da_x_avg || !s->da_g_avg || !s->da_mu || !s->step_size)
+    FAIL("chees: state arrays missing");
+  memset(&a, 0, sizeof(a));
+  a.C = C; a.D = D; a.s = *s;
+  chees_parts(C, D, a.P, a.rows_per);
+  if (int rc = grow(ctx, &ctx->chees_work, &ctx->chees_work_bytes, chees_work_doubles(C, D) * sizeof(double))) return rc;
+  a.part = ctx->chees_work;
+  a.m0 = a.part + (size_t)a.P * (2 * D + 2);
+  a.m1 = a.m0 + D;
+  a.sc = a.m1 + D;
+  return 0;
+}
+extern "C" int aehmc_chees_init(aehmc_ctx *ctx, int64_t C, double initial_step_size, double initial_trajectory_length,
+                                const aehmc_chees_state *state, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  CheesArgs a;
+  if (int rc = chees_args(ctx, C, 1, state, a)) return rc;
+  if (!(initial_step_size > 0) || !(initial_trajectory_length > 0))
+    FAIL("chees: initial_step_size and initial_trajectory_length must be positive");
+  a.max_steps = (long long)1 << 62;  // (the cap comes with the first update)
+  HIPCHK(tu::chees_init(a, initial_step_size, initial_trajectory_length, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int aehmc_chees_update(aehmc_ctx *ctx, int64_t C, int64_t D, int32_t is_last, double target_acceptance_rate,
+                                  double learning_rate, int64_t max_num_steps, const double *position_before,
+                                  const double *position_after, const double *velocity_or_momentum,
+                                  const double *inverse_mass_diag, double inverse_mass_scalar, const int32_t *accepted,
+                                  const double *acceptance_probability, const aehmc_chees_state *state, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  CheesArgs a;
+  if (int rc = chees_args(ctx, C, D, state, a)) return rc;
+  if (!position_before || !position_after || !velocity_or_momentum || !accepted || !acceptance_probability)
+    FAIL("chees: positions / momentum / accept flags / acceptance_probability missing");
+  if (max_num_steps < 1) FAIL("chees: max_num_steps must be at least 1");
+  a.last = is_last; a.target = target_acceptance_rate; a.lr = learning_rate; a.max_steps = max_num_steps;
+  a.q0 = position_before; a.q1 = position_after; a.mom = velocity_or_momentum;
+  a.imm = inverse_mass_diag; a.imm_scalar = inverse_mass_scalar;
+  a.accepted = accepted; a.p_accept = acceptance_probability;
+  HIPCHK(tu::chees_update(a, (hipStream_t)stream));
   return 0;
 }
 

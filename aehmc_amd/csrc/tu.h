@@ -12,6 +12,7 @@ struct NutsSampleArgs;
 struct HmcFusedArgs;
 struct GemmStreamK;
 struct PoolArgs;
+struct CheesArgs;
 namespace tu {
 // gemm_f64.cuh
 hipError_t gemm_nt_f64(int64_t M, int64_t N, int64_t K, const double *A, int64_t lda, const double *B, int64_t ldb,
@@ -81,5 +82,8 @@ hipError_t pool_init(const PoolArgs &a, double initial_step_size, hipStream_t st
 hipError_t pool_sums(const PoolArgs &a, hipStream_t st);
 hipError_t pool_imm(const PoolArgs &a, hipStream_t st);
 hipError_t pool_scalars(const PoolArgs &a, hipStream_t st);
+// chees.cuh
+hipError_t chees_init(const CheesArgs &a, double initial_step_size, double initial_trajectory_length, hipStream_t st);
+hipError_t chees_update(const CheesArgs &a, hipStream_t st);
 }  // namespace tu
 }  // namespace aehmc

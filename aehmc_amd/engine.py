@@ -629,6 +629,35 @@ class Engine:
                                                        float(target), p_accept.data_ptr(), position.data_ptr(),
                                                        ct.byref(cstate), self.stream), "aehmc_pooled_adapt_update")
 
+    # ------------------------------------------------------------------ ChEES warm-up
+    def chees_alloc(self, C, D=None):
+        """The state of a ChEES adaptation: every array [1] but step_size [C]; with ``D`` also ``sums`` [3 + 2 D], which
+        an update fills with S, A, abar and the column means m0, m1."""
+        dev, f64, i64 = self.device, torch.float64, torch.int64
+        st = {name: torch.empty(1, dtype=i64 if name in ("step", "num_steps", "da_step") else f64, device=dev)
+              for name, _ in _lib.CCheesState._fields_[:-2]}
+        st["step_size"] = torch.empty(C, dtype=f64, device=dev)
+        if D is not None:
+            st["sums"] = torch.empty(3 + 2 * D, dtype=f64, device=dev)
+        return st, self.chees_cstate(st)
+
+    @staticmethod
+    def chees_cstate(st):
+        return _lib.CCheesState(**{k: v.data_ptr() for k, v in st.items()})
+
+    def chees_init(self, C, initial_step_size, initial_trajectory_length, cstate):
+        self._check(self.lib.aehmc_chees_init(self.ctx, C, float(initial_step_size), float(initial_trajectory_length),
+                                              ct.byref(cstate), self.stream), "aehmc_chees_init")
+
+    def chees_update(self, C, D, last, target, learning_rate, max_num_steps, position_before, position_after, momentum,
+                     inverse_mass_diag, inverse_mass_scalar, accepted, p_accept, cstate):
+        """``inverse_mass_diag``: a [D] tensor or None (then ``inverse_mass_scalar``); ``accepted``: int32 [C]."""
+        self._check(self.lib.aehmc_chees_update(
+            self.ctx, C, D, int(last), float(target), float(learning_rate), int(max_num_steps),
+            position_before.data_ptr(), position_after.data_ptr(), momentum.data_ptr(),
+            inverse_mass_diag.data_ptr() if inverse_mass_diag is not None else None, float(inverse_mass_scalar),
+            accepted.data_ptr(), p_accept.data_ptr(), ct.byref(cstate), self.stream), "aehmc_chees_update")
+
     def syrk_tn(self, X, S, centre=None, w=0.0, delta=None):
         """S[i, j] += sum_c (X[c, i] - centre[i]) (X[c, j] - centre[j]) + w delta[i] delta[j] for j <= i, in place
         (aehmc_syrk_tn; elements above the diagonal are unspecified afterwards)."""

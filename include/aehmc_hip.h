@@ -119,6 +119,22 @@ typedef struct {
   int32_t reserved;
 } aehmc_pooled_adapt_state;
 
+/* warm-up state of chees.run: ONE trajectory length and ONE step size adapted from all chains (ChEES-HMC); every array
+ * is [1] but step_size */
+typedef struct {
+  int64_t *step;                         /* n >= 1: the update about to run */
+  double *log_T, *log_T_avg;             /* log trajectory length, its weighted average */
+  double *adam_m, *adam_v;               /* Adam moments of the ascent on log_T */
+  double *h;                             /* Halton weight of the transition the next update will see */
+  int64_t *num_steps;                    /* L of that transition: max(1, ceil(h T / step size)), capped */
+  int64_t *da_step;                      /* dual averaging, as in aehmc_pooled_adapt_state */
+  double *da_x, *da_x_avg, *da_g_avg, *da_mu;
+  double *step_size;                     /* [C], all entries equal */
+  double *sums;                          /* NULL, or [3 + 2 D]: a copy of what the last update summed -- S, A, abar,
+                                            then the column means m0 [D] and m1 [D] (diagnostics; the update itself
+                                            runs the same either way) */
+} aehmc_chees_state;
+
 /* per-transition outputs == trajectory.py:379-384 Diagnostics (+ n_leapfrog) */
 typedef struct {
   double *momentum;               /* [C,D] Diagnostics.state.momentum */
@@ -375,6 +391,38 @@ int aehmc_pooled_adapt_update(aehmc_ctx *ctx, int64_t C, int64_t D, int32_t stag
                               int32_t is_last, double target_acceptance_rate,
                               const double *acceptance_probability, const double *position,
                               const aehmc_pooled_adapt_state *state, void *stream);
+
+/* ChEES warm-up for static HMC (Hoffman, Radul, Sountsov 2021): the trajectory length T and the step
+ * size adapted from all chains, around aehmc_hmc_step with a FIXED shared metric.  The transitions export the returned
+ * state and the accept flag (aehmc_diagnostics.is_turning), not the proposal: the accept flag stands in for the
+ * acceptance probability as the weight, and on accept the returned momentum is the flipped end momentum, so the end
+ * velocity is v = -imm o momentum.  One update with n = step, T = exp(log_T), h as stored, positions [C,D] before and
+ * after the transition:
+ *   m0, m1 = column means of position_before / position_after over ALL chains;
+ *   s_c = (|q1_c - m1|^2 - |q0_c - m0|^2) <q1_c - m1, v_c>;  A = sum_c accepted_c,  S = sum_c (accepted_c ? s_c : 0)
+ *     (a select: the rows of a rejected chain are not read into S, whatever they hold);
+ *   G = h T S / max(A, 1), 0 when A = 0 or G is not finite;  Adam ascent on log_T: m = 0.9 m + 0.1 G,
+ *     v = 0.999 v + 0.001 G^2, log_T += learning_rate (m / (1 - 0.9^n)) / (sqrt(v / (1 - 0.999^n)) + 1e-8);
+ *   abar = (sum_c a_c) / C through the dual-averaging update of aehmc_pooled_adapt_update (gamma 0.05, t0 10,
+ *     kappa 0.75); the new step size eps goes into all C entries of step_size;
+ *   log_T clamped to [log eps, log(max_num_steps eps)];  log_T_avg = w log_T + (1 - w) log_T_avg, w = n^-kappa;
+ *   is_last: step size = exp(x_avg), log_T = log_T_avg;
+ *   step = n + 1, h = base-2 radical inverse of n + 1 (1/2, 1/4, 3/4, 1/8, ...),
+ *     num_steps = max(1, ceil(h T / eps)) capped at max_num_steps.
+ * `velocity_or_momentum` [C,D] is read as the momentum: v = -inverse_mass_diag o momentum with inverse_mass_diag [D], or
+ * v = -inverse_mass_scalar momentum when it is NULL.  For a shared DENSE metric the caller forms momentum . imm
+ * (aehmc_gemm_nt) and passes it with inverse_mass_scalar = 1; an array that already holds the velocity goes with -1.
+ * init: step 1, log_T = log_T_avg = log(initial_trajectory_length), Adam moments 0, dual averaging as
+ * aehmc_pooled_adapt_init leaves it (first step size exp(0) = 1), h = 1/2, num_steps from these (no cap yet).
+ * Sums over the chains run in an order fixed by (C, D) -- no floating-point atomics, two calls are bit-equal.  Five
+ * reads of [C,D] per update; the ctx keeps the scratch. */
+int aehmc_chees_init(aehmc_ctx *ctx, int64_t C, double initial_step_size, double initial_trajectory_length,
+                     const aehmc_chees_state *state, void *stream);
+int aehmc_chees_update(aehmc_ctx *ctx, int64_t C, int64_t D, int32_t is_last, double target_acceptance_rate,
+                       double learning_rate, int64_t max_num_steps, const double *position_before,
+                       const double *position_after, const double *velocity_or_momentum,
+                       const double *inverse_mass_diag, double inverse_mass_scalar, const int32_t *accepted,
+                       const double *acceptance_probability, const aehmc_chees_state *state, void *stream);
 
 /* step_size.dual_averaging_adaptation(target, gamma, t0, kappa) -> update (step_size.py:9-100 over
  * algorithms.dual_averaging, algorithms.py:17-115) as a stand-alone building block around any kernel
