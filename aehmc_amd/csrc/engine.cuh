@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <string>
 #endif
 
 #include "../../include/aehmc_hip.h"
@@ -51,7 +52,7 @@ struct ChainCtl {
 // amdgpu_waves_per_eu(1)): a code object that cannot be launched -- HSA_STATUS_ERROR_INVALID_ISA, the process aborts.
 // One wavefront more is asked for (W = 8: three per SIMD, <= 168 + accumulation registers; measured 228).
 // (AEHMC_WG_MIN_WAVES: the engine compiles the eight-wavefront kernels for FOUR per SIMD first -- two workgroups per CU -- and
-//  falls back to three when that program spills: engine.hip wg_program.)
+//  falls back to three when that program spills: engine.hip wg_program, which returns the number the program is built with.)
 #ifdef AEHMC_WG_MIN_WAVES
 constexpr int wg_min_waves(int W) { return W == 8 ? AEHMC_WG_MIN_WAVES : (W >= 4 ? W / 4 : 1) + 1; }
 #else
@@ -1249,6 +1250,25 @@ __global__ __launch_bounds__(FUSED_DENSE_BLOCK) AEHMC_USER_DENSITY_512 void k_hm
   __threadfence_block();  // the next transition's lanes read the energy lane 0 has just written
   }
 }
+#ifndef __HIPCC_RTC__  // (host side)
+// One instantiation as the engine launches its run-time compiled copy: the name hipRTC is asked for -- the kernel's
+// template arguments in the order of its declaration -- and the launch geometry.  Each family header builds these next
+// to the plan / dispatcher that picks the instantiation of the library's own targets, so the order is known once.
+struct KernelLaunch {
+  std::string name;
+  dim3 grid, block;
+  size_t dyn;
+};
+inline const char *bool_arg(bool b) { return b ? "true" : "false"; }
+inline KernelLaunch hmc_fused_dense_launch(bool md, bool td, bool pc, long long D, long long C) {
+  return {std::string("aehmc::k_hmc_fused_dense<") + bool_arg(md) + ", " + bool_arg(td) + ", " + bool_arg(pc) + ">",
+          dim3((unsigned)((C + FUSED_DENSE_BLOCK / 64 - 1) / (FUSED_DENSE_BLOCK / 64))), dim3(FUSED_DENSE_BLOCK),
+          (size_t)((md && !pc ? 2 : 0) + (td ? 1 : 0)) * D * D * sizeof(double)};
+}
+// elements per thread of the AEHMC_T_JOINT instantiations of k_nuts_wide / k_hmc_wide (512 threads: the program runs as
+// aehmc_logp_grad_t<8> on all of them)
+inline int joint_wide_r(long long D) { return D <= 4096 ? 8 : D <= 8192 ? 16 : 20; }
+#endif  // __HIPCC_RTC__
 
 // ---- new_state / stand-alone building blocks --------------------------------------
 AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_new_state_elem(EngineArgs a) {

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <tuple>
 #include <type_traits>
 #include <vector>
 
@@ -43,6 +44,75 @@ constexpr int STEP_BATCH = 8;  // lock-step leapfrogs between two polls
 constexpr size_t PROF_POOL = 8192;
 }  // namespace
 
+// ---- run-time compiled programs (hipRTC; "user-defined targets" below).  One row per program: the target mode its
+// source is compiled in, the family headers included after engine.cuh, and the kernels compiled together -- or none:
+// one instantiation per program, named by the launch.  A new run-time compiled route registers here, and builds the
+// name of its instantiation beside the plan in its family header (KernelLaunch, engine.cuh).
+enum RtcProg { RTC_BASE, RTC_GLM, RTC_JBASE, RTC_JTWG, RTC_JWG, RTC_NUTS, RTC_JNUTS, RTC_WIDE, RTC_JWIDE, RTC_BLOCK, RTC_HMC,
+               RTC_JHMCF, RTC_JHMC, RTC_GLMK };
+struct RtcRow {
+  const char *mode;                  // "AEHMC_CUSTOM_TARGET" (engine.cuh: target_elem calls aehmc_custom_elem), "AEHMC_JOINT_TARGET"
+                                     // (leap_small_dense calls aehmc_logp through dual.cuh), or none: the GLM kernels
+  std::vector<const char *> headers;
+  std::vector<std::string> names;    // (a launch asks for one of them by the name written here: rtc_function fails otherwise)
+};
+static const RtcRow RTC_TABLE[] = {
+    // RTC_BASE: the lock-step engine's target-dependent kernels (+ new_state): what LAUNCH_T can ask for
+    {"AEHMC_CUSTOM_TARGET", {},
+     {"aehmc::k_new_state_elem", "aehmc::k_step<true, true, true, false, true>", "aehmc::k_step<true, true, true, false, false>",
+      "aehmc::k_step<false, true, true, true, false>", "aehmc::k_step_linear<12, false>", "aehmc::k_step_linear<15, true>"}},
+    /* RTC_GLM */ {nullptr, {"glm_rows.cuh"}, {"aehmc::k_glm_rows", "aehmc::k_glm_finish"}},
+    /* RTC_JBASE */ {"AEHMC_JOINT_TARGET", {},
+     {"aehmc::k_new_state_joint", "aehmc::k_target_joint_rows", "aehmc::k_nuts_joint_rows", "aehmc::k_hmc_joint_rows"}},
+    // RTC_JTWG: above JOINT_ROWS_MAX_D (a density with its reverse-mode program only): U and dU/dq a workgroup per chain --
+    // new_state and the lock-step path's target evaluation; RTC_JBASE's kernels would need four chains' rows in LDS
+    {"AEHMC_JOINT_TARGET", {}, {"aehmc::k_target_joint_wg<8>"}},
+    // RTC_JWG: a workgroup of 8 wavefronts per chain (engine.cuh: k_nuts_joint_wg): traced densities with long data sweeps, few chains
+    {"AEHMC_JOINT_TARGET", {}, {"aehmc::k_nuts_joint_wg<8>", "aehmc::k_hmc_joint_wg<8>"}},  // (this order: RTC_JWG_NUTS / _HMC below)
+    /* RTC_NUTS */ {"AEHMC_CUSTOM_TARGET", {"nuts_resident.cuh"}, {}},
+    /* RTC_JNUTS */ {"AEHMC_JOINT_TARGET", {"nuts_resident.cuh"}, {}},
+    /* RTC_WIDE */ {"AEHMC_CUSTOM_TARGET", {"nuts_wide.cuh"}, {}},
+    /* RTC_JWIDE */ {"AEHMC_JOINT_TARGET", {"nuts_wide.cuh", "hmc_fused.cuh"}, {}},
+    /* RTC_BLOCK */ {"AEHMC_CUSTOM_TARGET", {"nuts_block_reg.cuh"}, {}},
+    /* RTC_HMC */ {"AEHMC_CUSTOM_TARGET", {"hmc_fused.cuh"}, {}},
+    /* RTC_JHMCF */ {"AEHMC_JOINT_TARGET", {"hmc_fused.cuh"}, {}},
+    /* RTC_JHMC */ {"AEHMC_JOINT_TARGET", {}, {}},
+    /* RTC_GLMK */ {nullptr, {"glm_rows.cuh"}, {}},  // (one instantiation of the one-launch GLM kernels)
+};
+static_assert(sizeof(RTC_TABLE) / sizeof(RTC_TABLE[0]) == RTC_GLMK + 1, "one row per RtcProg, in its order");
+static const std::string &RTC_JWG_NUTS = RTC_TABLE[RTC_JWG].names[0], &RTC_JWG_HMC = RTC_TABLE[RTC_JWG].names[1];  // (nuts_run / hmc_run spell no template arguments)
+// a program and the wavefronts per SIMD its workgroup-per-chain kernels are compiled for (AEHMC_WG_MIN_WAVES 3 / 4:
+// RTC_GLMK and RTC_JWG, see wg_program; 0: not defined)
+struct RtcId {
+  RtcProg prog;
+  int waves;
+  RtcId(RtcProg p, int w = 0) : prog(p), waves(w) {}
+};
+struct RtcProgram {
+  hipModule_t mod = nullptr;
+  std::map<std::string, hipFunction_t> fn;
+};
+// What a bound user-defined target owns: its source, the kernels compiled against it (hipRTC code objects keyed by
+// program, waves and -- one instantiation per program -- kernel, kept while the source is bound), wg_program's picks
+// among them, the device array of its parameter arrays, and what the source says about itself (read once, at bind)
+struct CustomBinding {
+  std::string src, inc;
+  std::map<std::tuple<int, int, std::string>, RtcProgram> rtc;
+  std::map<std::pair<int, std::string>, int> wg_choice;  // (wg_program: program, kernel -> the waves that were picked)
+  const double **d_cparams = nullptr;
+  int n_cparams = 0;
+  bool has_grad = false, grad_small = false;  // "#define AEHMC_JOINT_GRAD" (a prefix of the next), "#define AEHMC_JOINT_GRAD_SMALL"
+  bool has_sweep = false;  // "#define AEHMC_JOINT_SWEEP_TERMS n" (the tracer writes it, also with n = 0)
+  long long sweep_terms = 0;
+};
+static void custom_release(CustomBinding &b) {
+  for (auto &kv : b.rtc)
+    if (kv.second.mod) (void)hipModuleUnload(kv.second.mod);
+  b.rtc.clear();
+  if (b.d_cparams) (void)hipFree(b.d_cparams);
+  b.d_cparams = nullptr;
+}
+
 struct aehmc_ctx {
   int device = 0;
   std::string err;
@@ -70,7 +140,6 @@ struct aehmc_ctx {
   int opt_block_roll = 0;        // block-resident NUTS: waiting chains that trigger a begin round (0: kernel default)
   int opt_joint_wg = 1;          // traced joint densities with long sweeps: a workgroup per chain (0 never, 1 when it pays, 2 always)
   int opt_wg_waves = 0;          // wavefronts per SIMD the workgroup-per-chain kernels are compiled for (0: four unless the program then spills, see wg_program; 3; 4)
-  std::map<std::string, std::string> wg_choice;  // (wg_program: kernel -> the program variant that was picked)
   int opt_joint_wide = 1;      // traced joint densities, scalar / diagonal metric: the workgroup-per-chain kernels (0 never, 1 above 2048 coordinates, 2 also from 513 on)
   int opt_joint_resident = 1;  // joint densities with a reverse-mode program, D <= 512: the register-resident NUTS kernel (0 never, 1 from 17 coordinates on or with long reductions, 2 always)
   bool opt_pc_dense = true;      // per-chain dense metrics, 64 < D <= 512: NUTS in one launch, a wavefront per chain streams its matrix
@@ -111,23 +180,14 @@ struct aehmc_ctx {
   size_t syrk_work_bytes = 0;
   double *blk_pack = nullptr;  // block-resident dense kernels: the launch's matrices zero-padded to [Dp][Dp] (kept, grown)
   size_t blk_pack_bytes = 0;
-  // user-defined target (aehmc_set_custom_target): its source, the kernels compiled against it (hipRTC code objects
-  // keyed by program + source, kept for the life of the ctx) and the device array of its parameter arrays
-  std::string custom_src, custom_inc;
+  CustomBinding bound;  // the user-defined target (aehmc_set_custom_target and its kin)
   std::string rtc_cache_dir;  // compiled code objects of user-defined targets, kept across processes (aehmc_set_rtc_cache)
   int64_t rtc_compiled = 0, rtc_loaded = 0;  // programs compiled by hipRTC / taken from rtc_cache_dir (aehmc_rtc_stats)
-  const double **d_cparams = nullptr;
-  int n_cparams = 0;
   // user-defined row-reduction target: data matrix X [N,D], its transpose (owned), responses, [C,N] / [C] work arrays (owned)
   const double *glm_X = nullptr, *glm_y = nullptr;
   double *glm_XT = nullptr, *glm_z = nullptr, *glm_lsum = nullptr;
   int64_t glm_N = 0;
   size_t glm_z_bytes = 0, glm_lsum_bytes = 0;
-  struct RtcProgram {
-    hipModule_t mod = nullptr;
-    std::map<std::string, hipFunction_t> fn;
-  };
-  std::map<std::string, RtcProgram> rtc;
   // whitened dense MVN (white_prepare): imm = L L^T, z = L^-1 (q - mu), r = L^T p; the problem is then a Gaussian of
   // precision H = L^T P L under the identity metric.  Formed from the bound arrays on first use, dropped on every
   // aehmc_set_target / aehmc_set_metric
@@ -171,6 +231,16 @@ struct aehmc_ctx {
     return -2;           \
   } while (0)
 
+// a buffer kept with the ctx and grown on demand (hipFree waits for earlier launches that use it)
+static int grow(aehmc_ctx *ctx, double **buf, size_t *have, size_t need) {
+  if (*have >= need) return 0;
+  if (*buf) HIPCHK(hipFree(*buf));
+  *buf = nullptr;
+  *have = 0;
+  HIPCHK(hipMalloc((void **)buf, need));
+  *have = need;
+  return 0;
+}
 static inline dim3 chain_grid(int64_t C) { return dim3((unsigned)((C + 3) / 4)); }
 static void carry_free_old(aehmc_ctx *ctx) {
   for (double **p : {&ctx->carry.old_L, &ctx->carry.old_Linv, &ctx->carry.old_H, &ctx->carry.old_mu}) {
@@ -273,13 +343,11 @@ extern "C" int aehmc_destroy(aehmc_ctx *ctx) {
   if (ctx->pool_work) (void)hipFree(ctx->pool_work);
   if (ctx->chees_work) (void)hipFree(ctx->chees_work);
   if (ctx->syrk_work) (void)hipFree(ctx->syrk_work);
-  if (ctx->d_cparams) (void)hipFree(ctx->d_cparams);
   if (ctx->glm_XT) (void)hipFree(ctx->glm_XT);
   if (ctx->glm_z) (void)hipFree(ctx->glm_z);
   if (ctx->glm_lsum) (void)hipFree(ctx->glm_lsum);
   white_release(ctx);
-  for (auto &kv : ctx->rtc)
-    if (kv.second.mod) (void)hipModuleUnload(kv.second.mod);
+  custom_release(ctx->bound);
   for (int i = 0; i < NRING; i++)
     if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
   for (auto e : ctx->prof_ev) (void)hipEventDestroy(e);
@@ -328,11 +396,9 @@ extern "C" int aehmc_set_target(aehmc_ctx *ctx, const aehmc_target *t) {
 }
 
 // ------------------------------------------------------------------ user-defined targets (hipRTC)
-// The kernels that evaluate the target are templates / inline functions of engine.cuh, nuts_resident.cuh and
-// hmc_fused.cuh; for a user-defined coordinate-wise target they are compiled at run time against the user's
-// aehmc_custom_elem (engine.cuh: target_elem's AEHMC_T_CUSTOM case).  One hipRTC program per kernel family, compiled
-// on first use: `which` = "base" (the lock-step engine's target-dependent kernels + new_state), "nuts" (one
-// k_nuts_resident instantiation), "hmc" (one k_hmc_fused instantiation).
+// The kernels that evaluate the target are templates / inline functions of engine.cuh and the family headers; for a
+// user-defined target they are compiled at run time against the user's aehmc_custom_elem (engine.cuh: target_elem's
+// AEHMC_T_CUSTOM case) or joint density.  One hipRTC program per RTC_TABLE row (and instantiation), compiled on first use.
 static const char *RTC_PROLOGUE =
     "typedef signed int int32_t; typedef unsigned int uint32_t; typedef long long int64_t;\n"
     "typedef unsigned long long uint64_t; typedef unsigned long long uintptr_t; typedef unsigned long size_t;\n"
@@ -397,30 +463,21 @@ extern "C" int aehmc_rtc_stats(const aehmc_ctx *ctx, int64_t *compiled, int64_t 
   return 0;
 }
 
-static int rtc_function(aehmc_ctx *ctx, const std::string &which_full, const std::vector<std::string> &names,
-                        const std::string &want, hipFunction_t *out) {
-  // "j*": the programs of a joint target (engine.cuh: AEHMC_JOINT_TARGET) -- "jbase" new_state, "jnuts" / "jhmc" one
-  // instantiation of the small-problem kernels each
-  // (a trailing digit -- "jwg4", "glmk3" -- is the occupancy the workgroup-per-chain kernels are compiled for: wg_program)
-  const std::string key = which_full + "|" + ((which_full == "base" || which_full == "glm" || which_full == "jbase") ? std::string() : want);
-  const int wg_waves = isdigit((unsigned char)which_full.back()) ? which_full.back() - '0' : 0;
-  const std::string which = wg_waves ? which_full.substr(0, which_full.size() - 1) : which_full;
-  const bool joint = which[0] == 'j';
-  auto it = ctx->rtc.find(key);
-  if (it == ctx->rtc.end()) {
-    if (ctx->custom_src.empty()) FAIL("internal: no user-defined target source");
+static int rtc_function(aehmc_ctx *ctx, RtcId id, const std::string &want, hipFunction_t *out) {
+  const RtcRow &row = RTC_TABLE[id.prog];
+  const bool one = row.names.empty();  // one instantiation per program
+  const std::tuple<int, int, std::string> key(id.prog, id.waves, one ? want : std::string());
+  auto it = ctx->bound.rtc.find(key);
+  if (it == ctx->bound.rtc.end()) {
+    const std::vector<std::string> names = one ? std::vector<std::string>{want} : row.names;
+    if (ctx->bound.src.empty()) FAIL("internal: no user-defined target source");
     std::string src = RTC_PROLOGUE;
-    if (wg_waves) src += "#define AEHMC_WG_MIN_WAVES " + std::to_string(wg_waves) + "\n";
-    if (joint) src += "#define AEHMC_JOINT_TARGET 1\n";  // (engine.cuh: leap_small_dense calls aehmc_logp through dual.cuh)
-    else if (which != "glm" && which != "glmk") src += "#define AEHMC_CUSTOM_TARGET 1\n";  // (engine.cuh: target_elem calls aehmc_custom_elem)
-    src += "#line 1 \"custom_target\"\n" + ctx->custom_src + "\n";
+    if (id.waves) src += "#define AEHMC_WG_MIN_WAVES " + std::to_string(id.waves) + "\n";
+    if (row.mode) src += std::string("#define ") + row.mode + " 1\n";
+    src += "#line 1 \"custom_target\"\n" + ctx->bound.src + "\n";
     src += "#include \"engine.cuh\"\n";
-    if (which == "nuts" || which == "jnuts") src += "#include \"nuts_resident.cuh\"\n";
-    if (which == "wide" || which == "jwide") src += "#include \"nuts_wide.cuh\"\n";
-    if (which == "block") src += "#include \"nuts_block_reg.cuh\"\n";
-    if (which == "hmc" || which == "jhmcf" || which == "jwide") src += "#include \"hmc_fused.cuh\"\n";
-    if (which == "glm" || which == "glmk") src += "#include \"glm_rows.cuh\"\n";  // ("glmk": one instantiation of the one-launch kernels)
-    const std::string inc = "-I" + ctx->custom_inc;
+    for (const char *h : row.headers) src += std::string("#include \"") + h + "\"\n";
+    const std::string inc = "-I" + ctx->bound.inc;
     const char *opts[] = {"--offload-arch=" AEHMC_GPU_ARCH, "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
                           "-mllvm", "-disable-machine-licm"};  // (the flags of csrc/Makefile)
     std::vector<char> code;
@@ -470,7 +527,7 @@ static int rtc_function(aehmc_ctx *ctx, const std::string &which_full, const std
     } else {
       ctx->rtc_loaded++;
     }
-    aehmc_ctx::RtcProgram rp;
+    RtcProgram rp;
     if (hipModuleLoadData(&rp.mod, code.data()) != hipSuccess) {
       if (cached) remove(cache_path.c_str());  // (a damaged file: compiled afresh by the next call)
       FAIL("user-defined target: hipModuleLoadData failed");
@@ -484,22 +541,18 @@ static int rtc_function(aehmc_ctx *ctx, const std::string &which_full, const std
       }
       rp.fn[names[k]] = f;
     }
-    it = ctx->rtc.emplace(key, rp).first;
+    it = ctx->bound.rtc.emplace(key, rp).first;
   }
   auto f = it->second.fn.find(want);
   if (f == it->second.fn.end()) FAIL("internal: kernel " + want + " was not compiled");
   *out = f->second;
   return 0;
 }
-// the lock-step engine's target-dependent kernels (+ new_state), compiled together
-static const std::vector<std::string> RTC_BASE = {
-    "aehmc::k_new_state_elem", "aehmc::k_step<true, true, true, false, true>", "aehmc::k_step<true, true, true, false, false>",
-    "aehmc::k_step<false, true, true, true, false>", "aehmc::k_step_linear<12, false>", "aehmc::k_step_linear<15, true>"};
 template <class... Args>
-static int rtc_launch(aehmc_ctx *ctx, const std::string &which, const std::vector<std::string> &names,
-                      const std::string &want, dim3 grid, dim3 block, size_t dyn, hipStream_t st, Args... args) {
+static int rtc_launch(aehmc_ctx *ctx, RtcId id, const std::string &want, dim3 grid, dim3 block, size_t dyn, hipStream_t st,
+                      Args... args) {
   hipFunction_t f = nullptr;
-  if (int rc = rtc_function(ctx, which, names, want, &f)) return rc;
+  if (int rc = rtc_function(ctx, id, want, &f)) return rc;
   void *params[] = {(void *)&args...};
   {  // a code object whose register count does not fit the workgroup aborts the PROCESS when it is launched
      // (HSA_STATUS_ERROR_INVALID_ISA): an error return instead
@@ -523,6 +576,10 @@ static int rtc_launch(aehmc_ctx *ctx, const std::string &which, const std::vecto
   HIPCHK(hipModuleLaunchKernel(f, grid.x, grid.y, grid.z, block.x, block.y, block.z, (unsigned)dyn, st, params, nullptr));
   return 0;
 }
+template <class... Args>  // (a launch as its family header describes it)
+static int rtc_launch(aehmc_ctx *ctx, RtcId id, const KernelLaunch &k, hipStream_t st, Args... args) {
+  return rtc_launch(ctx, id, k.name, k.grid, k.block, k.dyn, st, args...);
+}
 
 // The workgroup-per-chain kernels (512 threads) are compiled for FOUR wavefronts per SIMD -- 128 registers per lane, two
 // workgroups per CU -- unless the program then keeps more than WG_SCRATCH_MAX bytes per lane in scratch (a density with
@@ -530,26 +587,23 @@ static int rtc_launch(aehmc_ctx *ctx, const std::string &which, const std::vecto
 // regression N = 1e5, D = 8, 1024 chains, NUTS: 28.8 -> 22.9 ms per transition (profiles/r6/INDEX.md).  "wg_waves" option:
 // 3 / 4 force one.
 constexpr int WG_SCRATCH_MAX = 320;
-static int wg_program(aehmc_ctx *ctx, const std::string &base, const std::vector<std::string> &names, const std::string &want,
-                      std::string *which) {
+static int wg_program(aehmc_ctx *ctx, RtcProg prog, const std::string &want, int *waves) {
   if (ctx->opt_wg_waves == 3 || ctx->opt_wg_waves == 4) {
-    *which = base + std::to_string(ctx->opt_wg_waves);
+    *waves = ctx->opt_wg_waves;
     return 0;
   }
-  const std::string key = base + "|" + want;
-  auto it = ctx->wg_choice.find(key);
-  if (it == ctx->wg_choice.end()) {
+  auto it = ctx->bound.wg_choice.find({prog, want});
+  if (it == ctx->bound.wg_choice.end()) {
     hipFunction_t f = nullptr;
-    if (int rc = rtc_function(ctx, base + "4", names, want, &f)) return rc;
+    if (int rc = rtc_function(ctx, {prog, 4}, want, &f)) return rc;
     int scratch = 0;
     (void)hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, f);
-    it = ctx->wg_choice.emplace(key, base + (scratch > WG_SCRATCH_MAX ? "3" : "4")).first;
+    it = ctx->bound.wg_choice.emplace(std::make_pair((int)prog, want), scratch > WG_SCRATCH_MAX ? 3 : 4).first;
   }
-  *which = it->second;
+  *waves = it->second;
   return 0;
 }
 
-static const std::vector<std::string> RTC_GLM = {"aehmc::k_glm_rows", "aehmc::k_glm_finish"};
 __global__ void k_transpose_rect(const double *src, double *dst, long long rows, long long cols) {  // dst [cols, rows]
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < rows * cols) dst[(e % cols) * rows + e / cols] = src[e];
@@ -558,33 +612,23 @@ __global__ void k_transpose_rect(const double *src, double *dst, long long rows,
 // BESIDE what is bound, and only when every step has succeeded do they replace it (round 5; until then a failed compile
 // left the new source and parameter table in place under the old target: the next step of the old target then
 // recompiled the bad source, or read freed parameter arrays).
-struct CustomBinding {
-  std::string src, inc;
-  std::map<std::string, aehmc_ctx::RtcProgram> rtc;
-  const double **d_cparams = nullptr;
-  int n_cparams = 0;
-};
-static void custom_swap(aehmc_ctx *ctx, CustomBinding &b) {
-  std::swap(ctx->custom_src, b.src);
-  std::swap(ctx->custom_inc, b.inc);
-  std::swap(ctx->rtc, b.rtc);
-  std::swap(ctx->d_cparams, b.d_cparams);
-  std::swap(ctx->n_cparams, b.n_cparams);
-}
-static void custom_release(CustomBinding &b) {
-  for (auto &kv : b.rtc)
-    if (kv.second.mod) (void)hipModuleUnload(kv.second.mod);
-  b.rtc.clear();
-  if (b.d_cparams) (void)hipFree(b.d_cparams);
-  b.d_cparams = nullptr;
-}
-// installs (source, params) in the ctx and compiles program `which`; on failure the previous binding is back in place
-static int custom_bind(aehmc_ctx *ctx, const char *source, const char *include_dir, const double *const *params,
-                       int32_t n_params, const std::string &which, const std::vector<std::string> &names) {
-  if (n_params < 0 || (n_params > 0 && !params)) FAIL("custom target: bad parameter list");
+// the first step of a bind: the new binding's source, and the markers in it, read here and nowhere else
+static CustomBinding custom_source(const char *source, const char *include_dir) {
   CustomBinding nb;
   nb.src = source;
   nb.inc = include_dir;
+  nb.has_grad = nb.src.find("#define AEHMC_JOINT_GRAD") != std::string::npos;
+  nb.grad_small = nb.src.find("#define AEHMC_JOINT_GRAD_SMALL") != std::string::npos;
+  static const char sweep_key[] = "#define AEHMC_JOINT_SWEEP_TERMS ";
+  const size_t at = nb.src.find(sweep_key);
+  nb.has_sweep = at != std::string::npos;
+  nb.sweep_terms = nb.has_sweep ? atoll(nb.src.c_str() + at + sizeof(sweep_key) - 1) : 0;
+  return nb;
+}
+// installs `nb` (custom_source) with `params` in the ctx and compiles program `prog`; on failure the previous binding is
+// back in place
+static int custom_bind(aehmc_ctx *ctx, CustomBinding nb, const double *const *params, int32_t n_params, RtcProg prog) {
+  if (n_params < 0 || (n_params > 0 && !params)) FAIL("custom target: bad parameter list");
   nb.n_cparams = n_params;
   HIPCHK(hipMalloc((void **)&nb.d_cparams, (size_t)(n_params > 0 ? n_params : 1) * sizeof(double *)));
   if (n_params > 0 &&
@@ -592,20 +636,35 @@ static int custom_bind(aehmc_ctx *ctx, const char *source, const char *include_d
     custom_release(nb);
     FAIL("custom target: parameter table upload failed");
   }
-  const bool same_source = ctx->custom_src == nb.src && ctx->custom_inc == nb.inc;
-  if (same_source) std::swap(nb.rtc, ctx->rtc);  // the same function: its code objects stay
-  custom_swap(ctx, nb);                            // ctx: new binding; nb: the previous one
+  // the same function: its code objects and wg_program's picks among them stay
+  const bool same_source = ctx->bound.src == nb.src && ctx->bound.inc == nb.inc;
+  const auto keep_programs = [&] {
+    if (!same_source) return;
+    std::swap(nb.rtc, ctx->bound.rtc);
+    std::swap(nb.wg_choice, ctx->bound.wg_choice);
+  };
+  keep_programs();
+  std::swap(ctx->bound, nb);  // ctx: new binding; nb: the previous one
   hipFunction_t f = nullptr;  // compile now: errors in the user's source surface here, not in the first step
-  if (int rc = rtc_function(ctx, which, names, names[0], &f)) {
+  if (int rc = rtc_function(ctx, prog, RTC_TABLE[prog].names[0], &f)) {
     const std::string err = ctx->err;
-    custom_swap(ctx, nb);  // ctx: the previous binding again; nb: the failed one
-    if (same_source) std::swap(nb.rtc, ctx->rtc);
+    std::swap(ctx->bound, nb);  // ctx: the previous binding again; nb: the failed one
+    keep_programs();
     custom_release(nb);
     ctx->err = err;
     return rc;
   }
   custom_release(nb);
-  if (!same_source) ctx->wg_choice.clear();  // (wg_program's picks belong to the previous function's programs)
+  return 0;
+}
+// the bound source becomes the target: a record of its kind and D alone
+static int custom_target(aehmc_ctx *ctx, aehmc_target_kind kind, int64_t D) {
+  aehmc_target t{};
+  t.kind = kind;
+  t.D = D;
+  white_release(ctx);
+  ctx->tgt = t;
+  ctx->has_tgt = true;
   return 0;
 }
 extern "C" int aehmc_set_custom_glm_target(aehmc_ctx *ctx, const char *source, int64_t D, int64_t N, const double *X,
@@ -616,7 +675,7 @@ extern "C" int aehmc_set_custom_glm_target(aehmc_ctx *ctx, const char *source, i
   if (D <= 0 || N <= 0 || !X || !y) FAIL("GLM target needs D, N, X [N,D] and y [N]");
   double *XT = nullptr;  // (allocated before anything is replaced)
   HIPCHK(hipMalloc((void **)&XT, (size_t)N * D * sizeof(double)));
-  if (int rc = custom_bind(ctx, source, include_dir, params, n_params, "glm", RTC_GLM)) {
+  if (int rc = custom_bind(ctx, custom_source(source, include_dir), params, n_params, RTC_GLM)) {
     (void)hipFree(XT);
     return rc;
   }
@@ -627,65 +686,41 @@ extern "C" int aehmc_set_custom_glm_target(aehmc_ctx *ctx, const char *source, i
   HIPCHK(hipGetLastError());
   HIPCHK(hipDeviceSynchronize());
   ctx->glm_X = X; ctx->glm_y = y; ctx->glm_N = N;
-  aehmc_target t{};
-  t.kind = AEHMC_T_GLM;
-  t.D = D;
-  white_release(ctx);
-  ctx->tgt = t;
-  ctx->has_tgt = true;
-  return 0;
+  return custom_target(ctx, AEHMC_T_GLM, D);
 }
 
-// a workgroup of 8 wavefronts per chain (engine.cuh: k_nuts_joint_wg): traced densities with long data sweeps, few chains
-static const std::vector<std::string> RTC_JWG = {"aehmc::k_nuts_joint_wg<8>", "aehmc::k_hmc_joint_wg<8>"};
+// a traced joint density with long data sweeps and few chains on a workgroup of 8 wavefronts per chain (RTC_JWG)
 static bool joint_wg_wanted(const aehmc_ctx *ctx, int64_t C) {
-  if (!ctx->opt_joint_wg) return false;
-  static const char key[] = "#define AEHMC_JOINT_SWEEP_TERMS ";
-  const size_t at = ctx->custom_src.find(key);
-  if (at == std::string::npos) return false;
-  const long long terms = atoll(ctx->custom_src.c_str() + at + sizeof(key) - 1);
+  if (!ctx->opt_joint_wg || !ctx->bound.has_sweep) return false;
   // (a wavefront per chain fills the GPU's 1024 SIMDs twice over at 2048 chains; a sweep of < 8192 terms is < 128 trips of a wavefront)
-  return ctx->opt_joint_wg > 1 || (terms >= 8192 && C <= 2048);
+  return ctx->opt_joint_wg > 1 || (ctx->bound.sweep_terms >= 8192 && C <= 2048);
 }
-static const std::vector<std::string> RTC_JBASE = {"aehmc::k_new_state_joint", "aehmc::k_target_joint_rows", "aehmc::k_nuts_joint_rows",
-                                                   "aehmc::k_hmc_joint_rows"};
-// above JOINT_ROWS_MAX_D (a density with its reverse-mode program only): U and dU/dq a workgroup per chain -- new_state and
-// the lock-step path's target evaluation; the kernels above would need four chains' rows in LDS
-static const std::vector<std::string> RTC_JTWG = {"aehmc::k_target_joint_wg<8>"};
-static bool joint_has_grad(const aehmc_ctx *ctx) { return ctx->custom_src.find("#define AEHMC_JOINT_GRAD") != std::string::npos; }
 // a traced joint density on the workgroup-per-chain NUTS / HMC kernels (k_nuts_wide / k_hmc_wide, AEHMC_T_JOINT): above
 // JOINT_ROWS_MAX_D by default ("joint_wide" 1), also from 513 coordinates on with "joint_wide" 2 (cross-checks), never with 0
 static bool joint_wide_wanted(const aehmc_ctx *ctx) {
   const int64_t D = ctx->tgt.D;
-  if (ctx->tgt.kind != AEHMC_T_JOINT || !ctx->opt_joint_wide || ctx->met.ndim >= 2 || D > JOINT_WIDE_MAX_D || !joint_has_grad(ctx))
+  if (ctx->tgt.kind != AEHMC_T_JOINT || !ctx->opt_joint_wide || ctx->met.ndim >= 2 || D > JOINT_WIDE_MAX_D || !ctx->bound.has_grad)
     return false;
   // (option 2 only where the workspace rows are padded for k_nuts_wide: ws_layout, wide_rows_padded)
   return D > JOINT_ROWS_MAX_D || (ctx->opt_joint_wide == 2 && wide_rows_padded(D));
 }
-// the elements per thread of those instantiations (512 threads: the program runs as aehmc_logp_grad_t<8> on all of them)
-static int joint_wide_r(int64_t D) { return D <= 4096 ? 8 : D <= 8192 ? 16 : 20; }
 // LDS of a workgroup that holds ONE chain's position and gradient rows (`row` doubles each: D + 1 for the wide kernels,
 // D for k_target_joint_wg) next to the kernel's static arrays (`f`: the compiled kernel), against the CU's 160 KiB
 constexpr size_t CU_LDS_BYTES = 163840;
-static int joint_rows_lds(aehmc_ctx *ctx, hipFunction_t f, int64_t row, size_t *dyn) {
+// rtc_launch of such a kernel, after that budget check
+template <class... Args>
+static int joint_rows_launch(aehmc_ctx *ctx, RtcProg prog, const std::string &want, int64_t row, dim3 grid, dim3 block,
+                             hipStream_t st, Args... args) {
+  hipFunction_t f = nullptr;
+  if (int rc = rtc_function(ctx, prog, want, &f)) return rc;
   int stat = 0;
   if (hipFuncGetAttribute(&stat, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, f) != hipSuccess || stat < 0)
     FAIL("joint target: the static LDS size of the compiled kernel could not be read");
-  *dyn = (size_t)2 * row * sizeof(double);
-  if (*dyn + (size_t)stat > CU_LDS_BYTES)
-    FAIL("joint target: D = " + std::to_string(ctx->tgt.D) + " needs " + std::to_string(*dyn + stat) +
+  const size_t dyn = (size_t)2 * row * sizeof(double);
+  if (dyn + (size_t)stat > CU_LDS_BYTES)
+    FAIL("joint target: D = " + std::to_string(ctx->tgt.D) + " needs " + std::to_string(dyn + stat) +
          " bytes of LDS for one chain's position and gradient rows, the CU has " + std::to_string(CU_LDS_BYTES));
-  return 0;
-}
-// rtc_launch of a kernel that keeps one chain's rows in LDS, after the budget check above
-template <class... Args>
-static int joint_rows_launch(aehmc_ctx *ctx, const std::string &which, const std::vector<std::string> &names, const std::string &want,
-                             int64_t row, dim3 grid, dim3 block, hipStream_t st, Args... args) {
-  hipFunction_t f = nullptr;
-  if (int rc = rtc_function(ctx, which, names, want, &f)) return rc;
-  size_t dyn = 0;
-  if (int rc = joint_rows_lds(ctx, f, row, &dyn)) return rc;
-  return rtc_launch(ctx, which, names, want, grid, block, dyn, st, args...);
+  return rtc_launch(ctx, prog, want, grid, block, dyn, st, args...);
 }
 extern "C" int aehmc_set_custom_joint_target(aehmc_ctx *ctx, const char *source, int64_t D, const double *const *params,
                                              int32_t n_params, const char *include_dir) {
@@ -693,20 +728,14 @@ extern "C" int aehmc_set_custom_joint_target(aehmc_ctx *ctx, const char *source,
   HIPCHK(hipSetDevice(ctx->device));
   // (D <= 64: one coordinate per lane, the single-launch kernels; above: the position row in LDS -- four chains' rows per
   //  workgroup up to JOINT_ROWS_MAX_D, one chain's above, which takes the density's reverse-mode program)
-  const bool grad = strstr(source, "#define AEHMC_JOINT_GRAD") != nullptr;
+  CustomBinding nb = custom_source(source, include_dir);
+  const bool grad = nb.has_grad;
   const int64_t dmax = grad ? JOINT_WIDE_MAX_D : JOINT_ROWS_MAX_D;
   if (D <= 0 || D > dmax)
     FAIL("joint target: D must be in [1, " + std::to_string(dmax) + "]" +
          (grad ? std::string() : " without a reverse-mode program (AEHMC_JOINT_GRAD: up to " + std::to_string(JOINT_WIDE_MAX_D) + ")"));
-  const bool big = D > JOINT_ROWS_MAX_D;
-  if (int rc = custom_bind(ctx, source, include_dir, params, n_params, big ? "jtwg" : "jbase", big ? RTC_JTWG : RTC_JBASE)) return rc;
-  aehmc_target t{};
-  t.kind = AEHMC_T_JOINT;
-  t.D = D;
-  white_release(ctx);
-  ctx->tgt = t;
-  ctx->has_tgt = true;
-  return 0;
+  if (int rc = custom_bind(ctx, std::move(nb), params, n_params, D > JOINT_ROWS_MAX_D ? RTC_JTWG : RTC_JBASE)) return rc;
+  return custom_target(ctx, AEHMC_T_JOINT, D);
 }
 
 extern "C" int aehmc_set_custom_target(aehmc_ctx *ctx, const char *source, int64_t D, const double *const *params,
@@ -714,14 +743,8 @@ extern "C" int aehmc_set_custom_target(aehmc_ctx *ctx, const char *source, int64
   if (!ctx || !source || !include_dir) return -2;
   HIPCHK(hipSetDevice(ctx->device));
   if (D <= 0) FAIL("target: D must be positive");
-  if (int rc = custom_bind(ctx, source, include_dir, params, n_params, "base", RTC_BASE)) return rc;
-  aehmc_target t{};
-  t.kind = AEHMC_T_CUSTOM;
-  t.D = D;
-  white_release(ctx);
-  ctx->tgt = t;
-  ctx->has_tgt = true;
-  return 0;
+  if (int rc = custom_bind(ctx, custom_source(source, include_dir), params, n_params, RTC_BASE)) return rc;
+  return custom_target(ctx, AEHMC_T_CUSTOM, D);
 }
 
 static int gemm(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K, const double *A, int64_t lda,
@@ -883,14 +906,7 @@ extern "C" int aehmc_metric_sqrt_per_chain(aehmc_ctx *ctx, int64_t C, int64_t D,
   const size_t dyn = in_lds ? (size_t)2 * D * D * sizeof(double) : 0;
   double *work = nullptr;
   if (!in_lds) {  // the factor is formed in a scratch copy: kept with the ctx, not allocated per call
-    const size_t need = (size_t)C * D * D * sizeof(double);
-    if (ctx->pc_work_bytes < need) {
-      if (ctx->pc_work) HIPCHK(hipFree(ctx->pc_work));
-      ctx->pc_work = nullptr;
-      ctx->pc_work_bytes = 0;
-      HIPCHK(hipMalloc((void **)&ctx->pc_work, need));
-      ctx->pc_work_bytes = need;
-    }
+    if (int rc = grow(ctx, &ctx->pc_work, &ctx->pc_work_bytes, (size_t)C * D * D * sizeof(double))) return rc;
     work = ctx->pc_work;
   }
   if (dyn)
@@ -964,15 +980,6 @@ extern "C" int aehmc_adapt_update(aehmc_ctx *ctx, int64_t C, int64_t D, int32_t 
 }
 
 // ---- pooled window adaptation (pooled_adapt.cuh, syrk_f64.cuh) ----
-static int grow(aehmc_ctx *ctx, double **buf, size_t *have, size_t need) {
-  if (*have >= need) return 0;
-  if (*buf) HIPCHK(hipFree(*buf));
-  *buf = nullptr;
-  *have = 0;
-  HIPCHK(hipMalloc((void **)buf, need));
-  *have = need;
-  return 0;
-}
 static int pool_args(aehmc_ctx *ctx, int64_t C, int64_t D, const aehmc_pooled_adapt_state *s, PoolArgs &a) {
   if (!s || C <= 0 || D <= 0) FAIL("pooled adaptation: bad arguments");
   if (!s->da_step || !s->da_x || !s->da_x_avg || !s->da_g_avg || !s->da_mu || !s->wc_mean || !s->wc_m2 || !s->wc_n ||
@@ -1522,7 +1529,7 @@ static int fill_args(aehmc_ctx *ctx, int64_t C, int64_t E, EngineArgs &a, bool u
   a.sigma = ctx->tgt.sigma;
   a.log_sigma = ctx->log_sigma;
   a.X = ctx->tgt.X; a.y = ctx->tgt.y; a.N = ctx->tgt.N;
-  a.cparams = ctx->d_cparams;
+  a.cparams = ctx->bound.d_cparams;
   a.linear = (a.met_ndim == 2 && ctx->opt_dense_linear) ? 1 : 0;
   return 0;
 }
@@ -1673,27 +1680,14 @@ extern "C" int aehmc_gemm_nt_tri(aehmc_ctx *ctx, int64_t M, int64_t N, int64_t K
 static int launch_glm(aehmc_ctx *ctx, const EngineArgs &a, const double *q, double *g, double *U, int to_ctl,
                       hipStream_t st, const int *ri, const int *nr) {
   const int64_t C = a.C, D = a.D, N = ctx->glm_N;
-  const size_t zb = (size_t)C * N * sizeof(double), lb = (size_t)C * sizeof(double);
-  if (ctx->glm_z_bytes < zb) {
-    if (ctx->glm_z) HIPCHK(hipFree(ctx->glm_z));
-    ctx->glm_z = nullptr;
-    ctx->glm_z_bytes = 0;
-    HIPCHK(hipMalloc((void **)&ctx->glm_z, zb));
-    ctx->glm_z_bytes = zb;
-  }
-  if (ctx->glm_lsum_bytes < lb) {
-    if (ctx->glm_lsum) HIPCHK(hipFree(ctx->glm_lsum));
-    ctx->glm_lsum = nullptr;
-    ctx->glm_lsum_bytes = 0;
-    HIPCHK(hipMalloc((void **)&ctx->glm_lsum, lb));
-    ctx->glm_lsum_bytes = lb;
-  }
+  if (int rc = grow(ctx, &ctx->glm_z, &ctx->glm_z_bytes, (size_t)C * N * sizeof(double))) return rc;
+  if (int rc = grow(ctx, &ctx->glm_lsum, &ctx->glm_lsum_bytes, (size_t)C * sizeof(double))) return rc;
   if (int rc = gemm(ctx, C, N, D, q, D, ctx->glm_X, D, ctx->glm_z, N, st, ri, nr)) return rc;
-  if (int rc = rtc_launch(ctx, "glm", RTC_GLM, "aehmc::k_glm_rows", chain_grid(C), dim3(256), 0, st, (long long)C,
-                          (long long)N, ctx->glm_y, (const double *const *)ctx->d_cparams, ctx->glm_z, ctx->glm_lsum, ri, nr))
+  if (int rc = rtc_launch(ctx, RTC_GLM, "aehmc::k_glm_rows", chain_grid(C), dim3(256), 0, st, (long long)C,
+                          (long long)N, ctx->glm_y, (const double *const *)ctx->bound.d_cparams, ctx->glm_z, ctx->glm_lsum, ri, nr))
     return rc;
   if (int rc = gemm(ctx, C, D, N, ctx->glm_z, N, ctx->glm_XT, N, g, D, st, ri, nr)) return rc;
-  return rtc_launch(ctx, "glm", RTC_GLM, "aehmc::k_glm_finish", chain_grid(C), dim3(256), 0, st, a, q, g, U,
+  return rtc_launch(ctx, RTC_GLM, "aehmc::k_glm_finish", chain_grid(C), dim3(256), 0, st, a, q, g, U,
                     (const double *)ctx->glm_lsum, to_ctl);
 }
 
@@ -1708,19 +1702,20 @@ static int launch_glm(aehmc_ctx *ctx, const EngineArgs &a, const double *q, doub
 static int launch_joint_rows(aehmc_ctx *ctx, const EngineArgs &a, const double *q, double *g, double *U, int to_ctl,
                              hipStream_t st, const int *ri, const int *nr) {
   if (a.D > JOINT_ROWS_MAX_D)  // a workgroup per chain (k_target_joint_wg)
-    return joint_rows_launch(ctx, "jtwg", RTC_JTWG, RTC_JTWG[0], a.D, dim3((unsigned)a.C), dim3(512), st, a, q, g, U, to_ctl, ri, nr);
-  return rtc_launch(ctx, "jbase", RTC_JBASE, RTC_JBASE[1], chain_grid(a.C), dim3(256), (size_t)8 * a.D * sizeof(double), st, a, q, g, U,
+    return joint_rows_launch(ctx, RTC_JTWG, "aehmc::k_target_joint_wg<8>", a.D, dim3((unsigned)a.C), dim3(512), st, a, q, g, U, to_ctl, ri, nr);
+  return rtc_launch(ctx, RTC_JBASE, "aehmc::k_target_joint_rows", chain_grid(a.C), dim3(256), (size_t)8 * a.D * sizeof(double), st, a, q, g, U,
                     to_ctl, ri, nr);
 }
 
 // kernels that evaluate a coordinate-wise target: the library's own instantiation, or -- user-defined target -- the
 // run-time compiled one of the same name
-#define LAUNCH_T(name, kern, C, st, a)                                                                  \
+// (the kernel token as it is written is the name hipRTC is asked for: RTC_BASE's list holds every one written below)
+#define LAUNCH_T(C, st, a, ...)                                                                         \
   do {                                                                                                  \
     if (ctx->tgt.kind == AEHMC_T_CUSTOM) {                                                              \
-      if (int rc_ = rtc_launch(ctx, "base", RTC_BASE, name, chain_grid(C), dim3(256), 0, st, a)) return rc_; \
+      if (int rc_ = rtc_launch(ctx, RTC_BASE, "aehmc::" #__VA_ARGS__, chain_grid(C), dim3(256), 0, st, a)) return rc_; \
     } else {                                                                                            \
-      LAUNCH(kern, C, st, a);                                                                           \
+      LAUNCH((__VA_ARGS__), C, st, a);                                                                  \
     }                                                                                                   \
   } while (0)
 
@@ -1901,8 +1896,8 @@ static int launch_leapfrog(aehmc_ctx *ctx, const EngineArgs &a, bool book, bool 
   };
   const bool text = tdense || tlin || tglm || tjoint;
   if (!md && !text) {
-    if (book) LAUNCH_T("aehmc::k_step<true, true, true, false, true>", (k_step<true, true, true, false, true>), C, st, a);
-    else LAUNCH_T("aehmc::k_step<true, true, true, false, false>", (k_step<true, true, true, false, false>), C, st, a);
+    if (book) LAUNCH_T(C, st, a, k_step<true, true, true, false, true>);
+    else LAUNCH_T(C, st, a, k_step<true, true, true, false, false>);
     return 0;
   }
   if (!md && text) {
@@ -1920,12 +1915,12 @@ static int launch_leapfrog(aehmc_ctx *ctx, const EngineArgs &a, bool book, bool 
   if (a.linear) {  // dense metric, v carried by linearity: one metric GEMM (w' = imm g')
     // (NUTS lock-step loop: the first stages of every leapfrog but the first ride in the previous
     //  step's bookkeeping launch -- k_step_linear<15, true>)
-    if (!(book && ctx->pre_done)) LAUNCH_T("aehmc::k_step_linear<12, false>", (k_step_linear<12, false>), C, st, a);
+    if (!(book && ctx->pre_done)) LAUNCH_T(C, st, a, k_step_linear<12, false>);
     if (text)
       if (target_ext()) return -1;
     if (metric_mul(ctx, C, a.cur_g, ctx->met.imm, a.cur_w, st, ri, nr)) return -1;
     if (book && ctx->fuse_pre) {
-      LAUNCH_T("aehmc::k_step_linear<15, true>", (k_step_linear<15, true>), C, st, a);
+      LAUNCH_T(C, st, a, k_step_linear<15, true>);
       ctx->pre_done = true;
     } else if (book) LAUNCH((k_step_linear<3, true>), C, st, a);
     else LAUNCH((k_step_linear<3, false>), C, st, a);
@@ -1935,7 +1930,7 @@ static int launch_leapfrog(aehmc_ctx *ctx, const EngineArgs &a, bool book, bool 
   LAUNCH((k_step<true, false, false, true, false>), C, st, a);
   if (metric_mul(ctx, C, a.cur_p, ctx->met.imm, a.vhalf, st, ri, nr)) return -1;
   if (!text) {
-    LAUNCH_T("aehmc::k_step<false, true, true, true, false>", (k_step<false, true, true, true, false>), C, st, a);
+    LAUNCH_T(C, st, a, k_step<false, true, true, true, false>);
   } else {
     LAUNCH((k_step<false, true, false, true, false>), C, st, a);
     if (target_ext()) return -1;
@@ -1994,18 +1989,18 @@ extern "C" int aehmc_new_state(aehmc_ctx *ctx, int64_t C, const double *q, doubl
     memset(&a, 0, sizeof(a));
     a.C = C; a.D = ctx->tgt.D; a.tkind = ctx->tgt.kind;
     a.mu = ctx->tgt.mu; a.sigma = ctx->tgt.sigma; a.log_sigma = ctx->log_sigma;
-    a.cparams = ctx->d_cparams;
+    a.cparams = ctx->bound.d_cparams;
     a.q = const_cast<double *>(q); a.U = U; a.g = g;
-    LAUNCH_T("aehmc::k_new_state_elem", k_new_state_elem, C, st, a);
+    LAUNCH_T(C, st, a, k_new_state_elem);
     return 0;
   }
   if (ctx->has_tgt && ctx->tgt.kind == AEHMC_T_JOINT) {
     memset(&a, 0, sizeof(a));
     a.C = C; a.D = ctx->tgt.D; a.tkind = ctx->tgt.kind;
-    a.cparams = ctx->d_cparams;
+    a.cparams = ctx->bound.d_cparams;
     a.q = const_cast<double *>(q); a.U = U; a.g = g;
     if (a.D > FUSED_DENSE_MAX_D) return launch_joint_rows(ctx, a, q, g, U, 0, st, nullptr, nullptr);
-    return rtc_launch(ctx, "jbase", RTC_JBASE, RTC_JBASE[0], chain_grid(C), dim3(256), 0, st, a);
+    return rtc_launch(ctx, RTC_JBASE, "aehmc::k_new_state_joint", chain_grid(C), dim3(256), 0, st, a);
   }
   if (int rc = fill_args(ctx, C, 1, a, false)) return rc;
   if (a.tkind == AEHMC_T_DENSE_MVN) {
@@ -2037,35 +2032,8 @@ static bool glm_wg_wanted(const aehmc_ctx *ctx, int64_t D, int64_t C) {
   if (!ctx->opt_joint_wg || D > GLM_ROWS_MAX_D) return false;
   return ctx->opt_joint_wg > 1 || (ctx->glm_N >= 8192 && C <= 2048);
 }
-static std::string glm_wg_name(const char *kernel, int64_t D) {
-  return std::string("aehmc::") + kernel + "<" + std::to_string(D) + ", 8>";  // (the kernel for the target's own D)
-}
-static std::string glm_rows_name(const char *kernel, int64_t D) {
-  return std::string("aehmc::") + kernel + "<" + std::to_string(D) + ">";
-}
-// workspace of the small-dense kernels with per-chain metrics (hipFree waits for earlier launches that use it)
-static int fused_dense_workspace(aehmc_ctx *ctx, size_t need, double **out) {
-  if (ctx->fd_ws_bytes < need) {
-    if (ctx->fd_ws) HIPCHK(hipFree(ctx->fd_ws));
-    ctx->fd_ws = nullptr;
-    ctx->fd_ws_bytes = 0;
-    HIPCHK(hipMalloc((void **)&ctx->fd_ws, need));
-    ctx->fd_ws_bytes = need;
-  }
-  *out = ctx->fd_ws;
-  return 0;
-}
-static int block_pack_workspace(aehmc_ctx *ctx, int64_t D, double **out) {
-  const size_t need = blk_pack_bytes(D);
-  if (ctx->blk_pack_bytes < need) {
-    if (ctx->blk_pack) HIPCHK(hipFree(ctx->blk_pack));
-    ctx->blk_pack = nullptr;
-    ctx->blk_pack_bytes = 0;
-    HIPCHK(hipMalloc((void **)&ctx->blk_pack, need));
-    ctx->blk_pack_bytes = need;
-  }
-  *out = ctx->blk_pack;
-  return 0;
+static std::string glm_name(const char *kernel, int64_t D, bool wg) {
+  return std::string("aehmc::") + kernel + "<" + std::to_string(D) + (wg ? ", 8>" : ">");  // (the kernel for the target's own D)
 }
 static int nuts_path(const aehmc_ctx *ctx, int64_t C, int64_t max_num_expansions) {
   const int tkind = ctx->tgt.kind, nd = ctx->met.ndim;
@@ -2075,7 +2043,6 @@ static int nuts_path(const aehmc_ctx *ctx, int64_t C, int64_t max_num_expansions
   // kernels, they beat the lock-step path at EVERY chain count -- 1.6x to 3x between 2048 and 16384 chains, where
   // the old rule still picked lock-step (tools/debug/resident_vs_lockstep.py, profiles/r3/INDEX.md)
   const bool want_resident = ctx->opt_resident_nuts != 0;
-  (void)C;
   if (want_resident && nuts_resident_supported(tkind, nd, D)) return NUTS_PATH_TEAMS;  // D <= 512
   if (want_resident && tkind == AEHMC_T_CUSTOM && nd < 2 && D <= 512) return NUTS_PATH_TEAMS;  // (run-time compiled)
   if (want_resident && tkind == AEHMC_T_CUSTOM && nd < 2 && D <= 10176) return NUTS_PATH_WIDE;  // (run-time compiled)
@@ -2093,9 +2060,9 @@ static int nuts_path(const aehmc_ctx *ctx, int64_t C, int64_t max_num_expansions
   // kernel with the program's rows in LDS -- from 17 coordinates on, or when its reductions are long, it beats the 64
   // forward passes side by side of the dense-path kernel below (funnel, 4096 chains: D = 32 2.5 -> 3.5e8 leapfrog/s, D = 64
   // 1.6 -> 3.4e8; D = 4 / 10: 4.7 / 4.0e8 forward against 4.3 / 3.9e8)
-  if (want_resident && tkind == AEHMC_T_JOINT && nd < 2 && D <= FUSED_DENSE_MAX_D && joint_has_grad(ctx) &&
+  if (want_resident && tkind == AEHMC_T_JOINT && nd < 2 && D <= FUSED_DENSE_MAX_D && ctx->bound.has_grad &&
       (ctx->opt_joint_resident == 2 ||
-       (ctx->opt_joint_resident == 1 && (D > 16 || ctx->custom_src.find("#define AEHMC_JOINT_GRAD_SMALL") != std::string::npos))))
+       (ctx->opt_joint_resident == 1 && (D > 16 || ctx->bound.grad_small))))
     return NUTS_PATH_TEAMS;
   if (want_resident && tkind == AEHMC_T_JOINT && D <= FUSED_DENSE_MAX_D) return NUTS_PATH_FUSED_DENSE;  // (run-time compiled)
   if (want_resident && tkind == AEHMC_T_GLM && nd < 2 && (glm_rows_wanted(D, C) || glm_wg_wanted(ctx, D, C))) return NUTS_PATH_GLM_ROWS;  // (run-time compiled)
@@ -2106,12 +2073,11 @@ static int nuts_path(const aehmc_ctx *ctx, int64_t C, int64_t max_num_expansions
   // chains (funnel, 4096 chains: D = 100 3.1 -> 4.9e7 leapfrog/s in one launch, D = 256 1.41 -> 1.35e7: profiles/r5/INDEX.md)
   // a density with a reverse-mode program (AEHMC_JOINT_GRAD, a traced Python logprob_fn) up to D = 512: the register-resident
   // kernel, the position handed to the program through LDS rows (nuts_resident.cuh)
-  if (want_resident && tkind == AEHMC_T_JOINT && nd < 2 && D <= 512 && ctx->opt_joint_resident &&
-      ctx->custom_src.find("#define AEHMC_JOINT_GRAD") != std::string::npos)
+  if (want_resident && tkind == AEHMC_T_JOINT && nd < 2 && D <= 512 && ctx->opt_joint_resident && ctx->bound.has_grad)
     return NUTS_PATH_TEAMS;
   // (... costs O(D / 64) per gradient: one launch whatever D)
   if (want_resident && tkind == AEHMC_T_JOINT && nd < 2 && D <= JOINT_ROWS_MAX_D &&
-      (D <= 192 || ctx->custom_src.find("#define AEHMC_JOINT_GRAD") != std::string::npos))
+      (D <= 192 || ctx->bound.has_grad))
     return NUTS_PATH_JOINT_ROWS;
   if (want_resident && nuts_resident_dense_supported(tkind, nd, D))
     return NUTS_PATH_FUSED_DENSE;  // (per-chain dense metrics included: each wavefront reads its own matrices)
@@ -2178,15 +2144,11 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
                          (long long)a.D, a.sqrt_mass, (long long)a.imm_cs, a.met_ndim, a.zbuf, a.ldw, 1);
       HIPCHK(hipGetLastError());
       if (a.tkind == AEHMC_T_CUSTOM) {  // the same instantiation (plan_nuts_wide), compiled against the user's function
-        const NutsWidePlan pl = plan_nuts_wide(a.D);
-        const std::string name = "aehmc::k_nuts_wide<" + std::to_string(pl.T) + ", " + std::to_string(pl.R) + ", " +
-                                 (pl.qgl ? "true" : "false") + ", " + std::to_string((int)AEHMC_T_CUSTOM) + ">";
-        return rtc_launch(ctx, "wide", {name}, name, dim3((unsigned)C), dim3(pl.T), pl.dyn, st, a);
+        return rtc_launch(ctx, RTC_WIDE, nuts_wide_launch(plan_nuts_wide(a.D), AEHMC_T_CUSTOM, C), st, a);
       }
       if (a.tkind == AEHMC_T_JOINT) {  // traced joint density: the rows of its program (q, dU/dq) in LDS at every D
-        const std::string name = "aehmc::k_nuts_wide<512, " + std::to_string(joint_wide_r(a.D)) + ", true, " +
-                                 std::to_string((int)AEHMC_T_JOINT) + ">";
-        return joint_rows_launch(ctx, "jwide", {name}, name, a.D + 1, dim3((unsigned)C), dim3(512), st, a);
+        const KernelLaunch k = nuts_wide_launch(plan_nuts_wide_joint(a.D), AEHMC_T_JOINT, C);
+        return joint_rows_launch(ctx, RTC_JWIDE, k.name, a.D + 1, k.grid, k.block, st, a);
       }
       HIPCHK(tu::nuts_wide(a, st));
       return 0;
@@ -2196,18 +2158,10 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
     const NutsSampleArgs m = take_multi(multi, multi_done, [] { return true; });
     return profiled(ctx, st, [&](bool) -> int {
       if (a.tkind == AEHMC_T_CUSTOM) {  // the same instantiation, compiled against the user's function
-        const ResidentPlan pl = plan_nuts_resident(a, m, ctx->opt_resident_min_team);
-        const std::string name = "aehmc::k_nuts_resident<" + std::to_string(pl.T) + ", " + std::to_string(pl.R) + ", " +
-                                 (pl.multi ? "true" : "false") + ", 0, " + (pl.ckl ? "true" : "false") + ">";
-        return rtc_launch(ctx, "nuts", {name}, name, dim3(pl.grid), dim3(256), pl.dyn, st, a, m);
+        return rtc_launch(ctx, RTC_NUTS, nuts_resident_launch(plan_nuts_resident(a, m, ctx->opt_resident_min_team)), st, a, m);
       }
       if (a.tkind == AEHMC_T_JOINT) {  // joint density with a reverse-mode program: one wavefront per chain, rows in LDS
-        ResidentPlan pl = plan_nuts_resident(a, m, 0);
-        pl.T = 64;
-        pl.R = a.D <= 64 ? 1 : a.D <= 128 ? 2 : a.D <= 256 ? 4 : 8;
-        const std::string name = "aehmc::k_nuts_resident<64, " + std::to_string(pl.R) + ", " + (pl.multi ? "true" : "false") + ", 0, false>";
-        return rtc_launch(ctx, "jnuts", {name}, name, dim3((unsigned)((C + 3) / 4)), dim3(256),
-                          (size_t)4 * 2 * a.D * sizeof(double), st, a, m);
+        return rtc_launch(ctx, RTC_JNUTS, nuts_resident_launch(plan_nuts_resident_joint(a, m)), st, a, m);
       }
       HIPCHK(tu::nuts_resident(a, m, st, ctx->opt_resident_min_team));
       return 0;
@@ -2219,17 +2173,14 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
     // (adaptation in the launch: per-chain dense)
     NutsSampleArgs m = take_multi(multi, multi_done, [&] { return (!multi->adapt || (pc && multi->ad.full)); });
     m.prec = ctx->tgt.prec;
-    if (pc)
-      if (int rc = fused_dense_workspace(ctx, (size_t)C * a.D * a.D * sizeof(double), &m.imm_ws)) return rc;
+    if (pc) {  // the chains' transposed matrices
+      if (int rc = grow(ctx, &ctx->fd_ws, &ctx->fd_ws_bytes, (size_t)C * a.D * a.D * sizeof(double))) return rc;
+      m.imm_ws = ctx->fd_ws;
+    }
     return profiled(ctx, st, [&](bool) -> int {
       if (a.tkind == AEHMC_T_JOINT) {  // the same kernel, compiled against the user's density (DENSE bit 8: joint target)
         const int dense = (md ? RES_DENSE_METRIC : 0) | (pc ? RES_DENSE_PER_CHAIN : 0) | RES_DENSE_JOINT;
-        const bool mlt = m.T > 1 || m.samples || m.acc_hist || m.div_hist || m.nleap_total || m.adapt;
-        const std::string name = "aehmc::k_nuts_resident<64, 1, " + std::string(mlt ? "true" : "false") + ", " +
-                                 std::to_string(dense) + ", false>";
-        const size_t dyn = (size_t)(md && !pc ? 2 : 0) * a.D * a.D * sizeof(double);
-        const unsigned grid = (unsigned)((C + RES_DENSE_BLOCK / 64 - 1) / (RES_DENSE_BLOCK / 64));
-        return rtc_launch(ctx, "jnuts", {name}, name, dim3(grid), dim3(RES_DENSE_BLOCK), dyn, st, a, m);
+        return rtc_launch(ctx, RTC_JNUTS, nuts_resident_dense_launch(a, m, dense), st, a, m);
       }
       HIPCHK(tu::nuts_resident_dense(a, m, st, md, td, pc));
       return 0;
@@ -2239,20 +2190,15 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
     NutsSampleArgs m = take_multi(multi, multi_done, [&] { return !multi->adapt; });
     m.prec = ctx->tgt.prec;
     m.roll = ctx->opt_block_roll;
-    double *bp = nullptr;
-    if (int rc = block_pack_workspace(ctx, a.D, &bp)) return rc;
+    if (int rc = grow(ctx, &ctx->blk_pack, &ctx->blk_pack_bytes, blk_pack_bytes(a.D))) return rc;
+    double *bp = ctx->blk_pack;
     return profiled(ctx, st, [&](bool) -> int {
       if (a.tkind == AEHMC_T_CUSTOM) {  // the transition-by-transition kernels, compiled against the user's function
         BlkMats mats;
         HIPCHK(blk_pack_matrices(a, nullptr, bp, mats, st));
         EngineArgs b = a;
         b.imm = mats.imm; b.sqrt_mass = mats.sqrt_mass;
-        const bool reg = ctx->opt_block_dense != 2 && block_reg_supported(a.D);
-        const std::string name = reg ? "aehmc::k_nuts_block_reg<" + std::string(a.D <= 128 ? "2" : "4") + ", false>"
-                                     : std::string("aehmc::k_nuts_block_dense<false>");
-        const size_t dyn = reg ? blk_reg_lds_bytes(a.D) : blk_lds_bytes(a.D);
-        return rtc_launch(ctx, "block", {name}, name, dim3((unsigned)((C + BLK_CHAINS - 1) / BLK_CHAINS)),
-                          dim3(BLK_THREADS), dyn, st, b, m);
+        return rtc_launch(ctx, RTC_BLOCK, block_launch(/*nuts*/ true, ctx->opt_block_dense != 2, a.D, C), st, b, m);
       }
       if (ctx->opt_block_dense != 2 && block_roll_wanted(a.D, m.T, ctx->opt_block_roll)) HIPCHK(tu::nuts_block_roll(a, m, bp, st));
       else if (ctx->opt_block_dense != 2 && block_reg_supported(a.D)) HIPCHK(tu::nuts_block_reg(a, m, bp, st));
@@ -2263,26 +2209,26 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
   if (path == NUTS_PATH_GLM_ROWS) {  // row-reduction target, D <= 32, scalar / diagonal metric: every transition of the call in one launch
     const NutsSampleArgs m = take_multi(multi, multi_done, [&] { return !multi->adapt; });
     const bool wg = glm_wg_wanted(ctx, a.D, C);
-    const std::string name = wg ? glm_wg_name("k_nuts_glm_wg", a.D) : glm_rows_name("k_nuts_glm_rows", a.D);
+    const std::string name = glm_name(wg ? "k_nuts_glm_wg" : "k_nuts_glm_rows", a.D, wg);
     return profiled(ctx, st, [&](bool) -> int {
-      std::string prog = "glmk";
+      int waves = 0;
       if (wg)
-        if (int rc = wg_program(ctx, "glmk", {name}, name, &prog)) return rc;
-      return rtc_launch(ctx, prog, {name}, name, wg ? dim3((unsigned)C) : chain_grid(C), dim3(wg ? 512 : 256), 0, st, a, m,
+        if (int rc = wg_program(ctx, RTC_GLMK, name, &waves)) return rc;
+      return rtc_launch(ctx, {RTC_GLMK, waves}, name, wg ? dim3((unsigned)C) : chain_grid(C), dim3(wg ? 512 : 256), 0, st, a, m,
                         (const double *)ctx->glm_XT, ctx->glm_y, (long long)ctx->glm_N);
     });
   }
   if (path == NUTS_PATH_JOINT_WG) {  // traced joint density, long sweeps, few chains: a workgroup per chain, one launch per call
     const NutsSampleArgs m = take_multi(multi, multi_done, [&] { return !multi->adapt; });
     return profiled(ctx, st, [&](bool) -> int {
-      std::string prog;
-      if (int rc = wg_program(ctx, "jwg", RTC_JWG, RTC_JWG[0], &prog)) return rc;
-      return rtc_launch(ctx, prog, RTC_JWG, RTC_JWG[0], dim3((unsigned)C), dim3(512), (size_t)2 * a.D * sizeof(double), st, a, m);
+      int waves = 0;
+      if (int rc = wg_program(ctx, RTC_JWG, RTC_JWG_NUTS, &waves)) return rc;
+      return rtc_launch(ctx, {RTC_JWG, waves}, RTC_JWG_NUTS, dim3((unsigned)C), dim3(512), (size_t)2 * a.D * sizeof(double), st, a, m);
     });
   }
   if (path == NUTS_PATH_JOINT_ROWS) {  // joint target, D > 64, scalar / diagonal metric: every transition of the call in one launch
     const NutsSampleArgs m = take_multi(multi, multi_done, [&] { return !multi->adapt; });
-    return profiled(ctx, st, [&](bool) -> int { return rtc_launch(ctx, "jbase", RTC_JBASE, RTC_JBASE[2], chain_grid(C), dim3(256), (size_t)8 * a.D * sizeof(double), st, a, m); });
+    return profiled(ctx, st, [&](bool) -> int { return rtc_launch(ctx, RTC_JBASE, "aehmc::k_nuts_joint_rows", chain_grid(C), dim3(256), (size_t)8 * a.D * sizeof(double), st, a, m); });
   }
   if (path == NUTS_PATH_PC_DENSE) {  // per-chain dense metrics, 64 < D <= 512: every transition of the call in one launch
     const NutsSampleArgs m = take_multi(multi, multi_done, [&] { return !multi->adapt; });
@@ -2520,7 +2466,7 @@ static int hmc_path(const aehmc_ctx *ctx, int64_t C) {
   if (ctx->opt_fused_hmc && ctx->tgt.kind == AEHMC_T_CUSTOM && ctx->met.ndim < 2 && D <= 1024) return HMC_PATH_CUSTOM_FUSED;
   // traced joint density with its reverse-mode program, 64 < D <= 1024: the same fused kernel ("joint_resident" option;
   // D <= 64 stays on k_hmc_fused_dense)
-  if (ctx->opt_fused_hmc && ctx->opt_joint_resident && ctx->tgt.kind == AEHMC_T_JOINT && joint_has_grad(ctx) && ctx->met.ndim < 2 &&
+  if (ctx->opt_fused_hmc && ctx->opt_joint_resident && ctx->tgt.kind == AEHMC_T_JOINT && ctx->bound.has_grad && ctx->met.ndim < 2 &&
       D > FUSED_DENSE_MAX_D && D <= 1024 && !joint_wg_wanted(ctx, C) && !joint_wide_wanted(ctx))
     return HMC_PATH_JOINT_FUSED;
   // regression target (hmc_linreg.cuh)
@@ -2601,20 +2547,16 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
       return profiled(ctx, st, [&](bool) -> int { HIPCHK(tu::hmc_linreg(f, st)); return 0; });
     }
     if (path == HMC_PATH_CUSTOM_FUSED) {  // user-defined coordinate-wise target: the same fused kernel, compiled against the user's function at run time
-      f.tkind = AEHMC_T_CUSTOM; f.cparams = ctx->d_cparams;
+      f.tkind = AEHMC_T_CUSTOM; f.cparams = ctx->bound.d_cparams;
       f.fc = ctx->opt_fp_contract;
-      const int R = hmc_fused_r(D);
-      const std::string name = "aehmc::k_hmc_fused<" + std::to_string(R) + ", 5, " + (f.fc ? "true" : "false") + ">";
       return profiled(ctx, st, [&](bool) -> int {
-        return rtc_launch(ctx, "hmc", {name}, name, dim3((unsigned)((C + 3) / 4)), dim3(256), (size_t)4 * R * 64 * sizeof(double), st, f);
+        return rtc_launch(ctx, RTC_HMC, hmc_fused_launch(D, AEHMC_T_CUSTOM, f.fc, C), st, f);
       });
     }
     // traced joint density (round 6): the same fused kernel with the position and gradient rows of the generated program in LDS
-    f.tkind = AEHMC_T_JOINT; f.cparams = ctx->d_cparams;
-    const int R = hmc_fused_r(D);
-    const std::string name = "aehmc::k_hmc_fused<" + std::to_string(R) + ", " + std::to_string((int)AEHMC_T_JOINT) + ", false>";
+    f.tkind = AEHMC_T_JOINT; f.cparams = ctx->bound.d_cparams;
     return profiled(ctx, st, [&](bool) -> int {
-      return rtc_launch(ctx, "jhmcf", {name}, name, dim3((unsigned)((C + 3) / 4)), dim3(256), (size_t)4 * 2 * R * 64 * sizeof(double), st, f);
+      return rtc_launch(ctx, RTC_JHMCF, hmc_fused_launch(D, AEHMC_T_JOINT, false, C), st, f);
     });
   }
   EngineArgs a;
@@ -2624,7 +2566,7 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
   if (path == HMC_PATH_WIDE) {  // a workgroup per chain (k_hmc_wide), coordinate-wise target or traced joint density
     HmcFusedArgs f = hmc_fused_args(ctx, C, rng, step_size, L, divergence_threshold, q, U, g, out);
     f.tkind = ctx->tgt.kind; f.mu = ctx->tgt.mu; f.sigma = ctx->tgt.sigma; f.log_sigma = ctx->log_sigma;
-    f.cparams = ctx->d_cparams;
+    f.cparams = ctx->bound.d_cparams;
     f.fc = ctx->opt_fp_contract;
     // A launch pair per CHUNK of transitions: the momenta of the chunk are drawn first, at one wavefront per
     // chain (k_draw_momentum), into [nt][C][D]; the workgroup-per-chain kernel then runs the nt transitions
@@ -2653,15 +2595,11 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
         f.div_hist = div_hist ? div_hist + (size_t)t0 * C : nullptr;
         f.out.momentum = t0 + nt == T ? out->momentum : nullptr;  // only the last transition's is observable
         if (f.tkind == AEHMC_T_CUSTOM) {  // the same instantiation (plan_hmc_wide), compiled against the user's function (round 5)
-          const HmcWidePlan pl = plan_hmc_wide(D, AEHMC_T_CUSTOM);
-          const std::string name = "aehmc::k_hmc_wide<" + std::to_string(pl.T) + ", " + std::to_string(pl.R) + ", " +
-                                   std::to_string((int)AEHMC_T_CUSTOM) + ", " + (f.fc ? "true" : "false") + ">";
-          if (int rc = rtc_launch(ctx, "hmc", {name}, name, dim3((unsigned)C), dim3(pl.T), pl.dyn, st, f, (const double *)zall, nt))
-            return rc;
+          const KernelLaunch k = hmc_wide_launch(plan_hmc_wide(D, AEHMC_T_CUSTOM), AEHMC_T_CUSTOM, f.fc, C);
+          if (int rc = rtc_launch(ctx, RTC_HMC, k, st, f, (const double *)zall, nt)) return rc;
         } else if (f.tkind == AEHMC_T_JOINT) {  // k_nuts_wide's rule: 512 threads (the program's workgroup), q and dU/dq in LDS only
-          const std::string name = "aehmc::k_hmc_wide<512, " + std::to_string(joint_wide_r(D)) + ", " +
-                                   std::to_string((int)AEHMC_T_JOINT) + ", false>";
-          if (int rc = joint_rows_launch(ctx, "jwide", {name}, name, D + 1, dim3((unsigned)C), dim3(512), st, f, (const double *)zall, nt))
+          const KernelLaunch k = hmc_wide_launch(plan_hmc_wide_joint(D), AEHMC_T_JOINT, false, C);
+          if (int rc = joint_rows_launch(ctx, RTC_JWIDE, k.name, D + 1, k.grid, k.block, st, f, (const double *)zall, nt))
             return rc;
         } else {
           HIPCHK(tu::hmc_resident(f, zall, nt, st));
@@ -2678,24 +2616,23 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
     const bool md = a.met_ndim == 2, td = a.tkind == AEHMC_T_DENSE_MVN, pc = md && ctx->met.per_chain;
     EngineArgs b = a;
     b.linear = 0;  // literal products (metrics.py:71)
-    const size_t dyn = (size_t)((md && !pc ? 2 : 0) + (td ? 1 : 0)) * D * D * sizeof(double);
+    const KernelLaunch k = hmc_fused_dense_launch(md, td, pc, D, C);
     double *imm_ws = nullptr;
-    if (pc)
-      if (int rc = fused_dense_workspace(ctx, (size_t)C * D * D * sizeof(double), &imm_ws)) return rc;
-    const dim3 grid((unsigned)((C + FUSED_DENSE_BLOCK / 64 - 1) / (FUSED_DENSE_BLOCK / 64))), block(FUSED_DENSE_BLOCK);
+    if (pc) {  // the chains' transposed matrices
+      if (int rc = grow(ctx, &ctx->fd_ws, &ctx->fd_ws_bytes, (size_t)C * D * D * sizeof(double))) return rc;
+      imm_ws = ctx->fd_ws;
+    }
 #define AEHMC_FD_LAUNCH(MDV, TDV, PCV)                                                                         \
   do {                                                                                                         \
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_fused_dense<MDV, TDV, PCV>),               \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));                         \
-    hipLaunchKernelGGL((k_hmc_fused_dense<MDV, TDV, PCV>), grid, block, dyn, st, b, ctx->tgt.prec, imm_ws,      \
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.dyn));                       \
+    hipLaunchKernelGGL((k_hmc_fused_dense<MDV, TDV, PCV>), k.grid, k.block, k.dyn, st, b, ctx->tgt.prec, imm_ws, \
                        (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);                        \
   } while (0)
     const auto launch = [&](bool) -> int {
       if (tjoint) {  // the same kernel, compiled against the user's density
-        const std::string name = "aehmc::k_hmc_fused_dense<" + std::string(md ? "true" : "false") + ", false, " +
-                                 (pc ? "true" : "false") + ">";
         const double *noprec = nullptr;
-        if (int rc = rtc_launch(ctx, "jhmc", {name}, name, grid, block, dyn, st, b, noprec, imm_ws, (long long)L, (long long)T,
+        if (int rc = rtc_launch(ctx, RTC_JHMC, k, st, b, noprec, imm_ws, (long long)L, (long long)T,
                                 samples, acc_hist, (int *)div_hist))
           return rc;
       } else if (md && td && pc) AEHMC_FD_LAUNCH(true, true, true);
@@ -2712,12 +2649,12 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
   }
   if (path == HMC_PATH_GLM_ROWS) {  // row-reduction target with D <= 32, scalar / diagonal metric: all T transitions in one launch (glm_rows.cuh)
     const bool wg = glm_wg_wanted(ctx, D, C);
-    const std::string name = wg ? glm_wg_name("k_hmc_glm_wg", D) : glm_rows_name("k_hmc_glm_rows", D);
+    const std::string name = glm_name(wg ? "k_hmc_glm_wg" : "k_hmc_glm_rows", D, wg);
     const auto launch = [&](bool) -> int {
-      std::string prog = "glmk";
+      int waves = 0;
       if (wg)
-        if (int rc = wg_program(ctx, "glmk", {name}, name, &prog)) return rc;
-      return rtc_launch(ctx, prog, {name}, name, wg ? dim3((unsigned)C) : chain_grid(C), dim3(wg ? 512 : 256), 0, st, a,
+        if (int rc = wg_program(ctx, RTC_GLMK, name, &waves)) return rc;
+      return rtc_launch(ctx, {RTC_GLMK, waves}, name, wg ? dim3((unsigned)C) : chain_grid(C), dim3(wg ? 512 : 256), 0, st, a,
                         (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, (const double *)ctx->glm_XT,
                         ctx->glm_y, (long long)ctx->glm_N);
     };
@@ -2726,9 +2663,9 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
   }
   if (path == HMC_PATH_JOINT_WG) {  // traced joint density with long data sweeps, few chains: a workgroup per chain (k_hmc_joint_wg)
     const auto launch = [&](bool) -> int {
-      std::string prog;
-      if (int rc = wg_program(ctx, "jwg", RTC_JWG, RTC_JWG[1], &prog)) return rc;
-      return rtc_launch(ctx, prog, RTC_JWG, RTC_JWG[1], dim3((unsigned)C), dim3(512), (size_t)2 * D * sizeof(double), st, a,
+      int waves = 0;
+      if (int rc = wg_program(ctx, RTC_JWG, RTC_JWG_HMC, &waves)) return rc;
+      return rtc_launch(ctx, {RTC_JWG, waves}, RTC_JWG_HMC, dim3((unsigned)C), dim3(512), (size_t)2 * D * sizeof(double), st, a,
                         (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);
     };
     if (int rc = profiled(ctx, st, launch)) return rc;
@@ -2736,7 +2673,7 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
   }
   if (path == HMC_PATH_JOINT_ROWS) {  // all T transitions in one launch, the lock-step loop of a chain in one wavefront (k_hmc_joint_rows)
     const auto launch = [&](bool) -> int {
-      return rtc_launch(ctx, "jbase", RTC_JBASE, RTC_JBASE[3], chain_grid(C), dim3(256), (size_t)8 * D * sizeof(double), st, a,
+      return rtc_launch(ctx, RTC_JBASE, "aehmc::k_hmc_joint_rows", chain_grid(C), dim3(256), (size_t)8 * D * sizeof(double), st, a,
                         (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);
     };
     if (int rc = profiled(ctx, st, launch)) return rc;
@@ -2748,20 +2685,16 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
     return fill_n_leapfrog(ctx, C, L, T, out, false, st);
   }
   if (path == HMC_PATH_BLOCK_DENSE) {  // all T transitions in one launch, a workgroup per 16 chains, products on MFMA (nuts_block.cuh)
-    double *bp = nullptr;
-    if (int rc = block_pack_workspace(ctx, D, &bp)) return rc;
+    if (int rc = grow(ctx, &ctx->blk_pack, &ctx->blk_pack_bytes, blk_pack_bytes(D))) return rc;
+    double *bp = ctx->blk_pack;
     const auto launch = [&](bool) -> int {
       if (a.tkind == AEHMC_T_CUSTOM) {  // user-defined coordinate-wise target: the same kernels, compiled against the user's function (round 5)
         BlkMats mats;
         HIPCHK(blk_pack_matrices(a, nullptr, bp, mats, st));
         EngineArgs b = a;
         b.imm = mats.imm; b.sqrt_mass = mats.sqrt_mass;
-        const bool reg = ctx->opt_block_dense != 2 && block_reg_supported(D);
-        const std::string name = reg ? "aehmc::k_hmc_block_reg<" + std::string(D <= 128 ? "2" : "4") + ", false>"
-                                     : std::string("aehmc::k_hmc_block_dense<false>");
-        const size_t dyn = reg ? blk_reg_lds_bytes(D) : blk_lds_bytes(D);
-        return rtc_launch(ctx, "block", {name}, name, dim3((unsigned)((C + BLK_CHAINS - 1) / BLK_CHAINS)), dim3(BLK_THREADS),
-                          dyn, st, b, (const double *)nullptr, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);
+        return rtc_launch(ctx, RTC_BLOCK, block_launch(/*nuts*/ false, ctx->opt_block_dense != 2, D, C), st, b,
+                          (const double *)nullptr, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);
       }
       if (ctx->opt_block_dense != 2 && block_reg_supported(D))
         HIPCHK(tu::hmc_block_reg(a, ctx->tgt.prec, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, bp, st));

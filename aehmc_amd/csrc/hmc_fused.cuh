@@ -660,6 +660,13 @@ inline HmcWidePlan plan_hmc_wide(long long D, int tkind) {
   p.dyn = tkind == AEHMC_T_CUSTOM ? 0 : (size_t)D * sizeof(double) * (tkind == AEHMC_T_DIAG_GAUSSIAN ? 2 : 1);
   return p;
 }
+// a traced joint density (run-time compiled only): k_nuts_wide's rule -- 512 threads, q and dU/dq rows in LDS only
+inline HmcWidePlan plan_hmc_wide_joint(long long D) { return {512, joint_wide_r(D), (size_t)2 * (D + 1) * sizeof(double)}; }
+// the run-time compiled copy of a plan's instantiation for target kind `tkind` (AEHMC_T_CUSTOM, AEHMC_T_JOINT)
+inline KernelLaunch hmc_wide_launch(const HmcWidePlan &p, aehmc_target_kind tkind, bool fc, long long C) {
+  return {"aehmc::k_hmc_wide<" + std::to_string(p.T) + ", " + std::to_string(p.R) + ", " + std::to_string((int)tkind) + ", " + bool_arg(fc) + ">",
+          dim3((unsigned)C), dim3(p.T), p.dyn};
+}
 template <int T, int R>
 inline hipError_t launch_hmc_wide_r(const HmcFusedArgs &a, const HmcWidePlan &p, const double *zbuf, int nt, hipStream_t st) {
   if (p.T != T || p.R != R) return hipErrorInvalidValue;
@@ -735,5 +742,14 @@ inline int hmc_fused_r(long long D) {
   const long long r = (D + 63) / 64;
   return r <= 1 ? 1 : r <= 2 ? 2 : r <= 4 ? 4 : r <= 8 ? 8 : 16;
 }
+#ifndef __HIPCC_RTC__
+// the run-time compiled copy of that instantiation (AEHMC_T_CUSTOM; AEHMC_T_JOINT: the gradient rows of the program in
+// LDS beside the position rows)
+inline KernelLaunch hmc_fused_launch(long long D, aehmc_target_kind tkind, bool fc, long long C) {
+  const int R = hmc_fused_r(D);
+  return {"aehmc::k_hmc_fused<" + std::to_string(R) + ", " + std::to_string((int)tkind) + ", " + bool_arg(fc) + ">",
+          dim3((unsigned)((C + 3) / 4)), dim3(256), (size_t)4 * (tkind == AEHMC_T_JOINT ? 2 : 1) * R * 64 * sizeof(double)};
+}
+#endif  // __HIPCC_RTC__
 
 }  // namespace aehmc

@@ -549,6 +549,13 @@ inline hipError_t launch_hmc_block_reg(EngineArgs a, const double *prec, long lo
   return a.D <= 128 ? launch_hmc_block_reg_r<2>(a, mats.prec, L, nt, samples, acc_hist, div_hist, st)
                     : launch_hmc_block_reg_r<4>(a, mats.prec, L, nt, samples, acc_hist, div_hist, st);
 }
+// The run-time compiled block kernel of a coordinate-wise user-defined target, for NUTS or for HMC: the register
+// kernel where it exists (`reg_allowed`: the "block_dense" option is not 2), the work-row kernel otherwise
+inline KernelLaunch block_launch(bool nuts, bool reg_allowed, long long D, long long C) {
+  const bool reg = reg_allowed && block_reg_supported(D);
+  return {std::string(nuts ? "aehmc::k_nuts" : "aehmc::k_hmc") + (reg ? (D <= 128 ? "_block_reg<2, false>" : "_block_reg<4, false>") : "_block_dense<false>"),
+          dim3((unsigned)((C + BLK_CHAINS - 1) / BLK_CHAINS)), dim3(BLK_THREADS), reg ? blk_reg_lds_bytes(D) : blk_lds_bytes(D)};
+}
 #endif  // __HIPCC_RTC__
 
 }  // namespace aehmc

@@ -659,25 +659,30 @@ inline bool nuts_resident_dense_supported(int tkind, int met_ndim, long long D) 
   const bool elem = tkind == AEHMC_T_STD_NORMAL || tkind == AEHMC_T_ISO_GAUSSIAN || tkind == AEHMC_T_DIAG_GAUSSIAN;
   return D <= FUSED_DENSE_MAX_D && (met_ndim == 2 || tkind == AEHMC_T_DENSE_MVN) && (elem || tkind == AEHMC_T_DENSE_MVN);
 }
+// the MULTI instantiations: more than one transition, per-transition outputs or adaptation in the launch
+inline bool nuts_multi(const NutsSampleArgs &m) { return m.T > 1 || m.samples || m.acc_hist || m.div_hist || m.nleap_total || m.adapt; }
 #ifndef __HIPCC_RTC__
+// the small-dense instantiation of DENSE flags `dense`: its launch geometry, and its name for the run-time compiled copy
+inline KernelLaunch nuts_resident_dense_launch(const EngineArgs &a, const NutsSampleArgs &m, int dense) {
+  const int nmat = ((dense & RES_DENSE_METRIC) && !(dense & RES_DENSE_PER_CHAIN) ? 2 : 0) + ((dense & RES_DENSE_TARGET) ? 1 : 0);
+  return {"aehmc::k_nuts_resident<64, 1, " + std::string(bool_arg(nuts_multi(m))) + ", " + std::to_string(dense) + ", false>",
+          dim3((unsigned)((a.C + RES_DENSE_BLOCK / 64 - 1) / (RES_DENSE_BLOCK / 64))), dim3(RES_DENSE_BLOCK),
+          (size_t)nmat * a.D * a.D * sizeof(double)};
+}
 template <int DENSE>
 inline hipError_t launch_nuts_resident_dense_v(const EngineArgs &a, const NutsSampleArgs &m, hipStream_t st) {
-  constexpr int nmat = ((DENSE & RES_DENSE_METRIC) && !(DENSE & RES_DENSE_PER_CHAIN) ? 2 : 0) +
-                       ((DENSE & RES_DENSE_TARGET) ? 1 : 0);
-  const size_t dyn = (size_t)nmat * a.D * a.D * sizeof(double);
-  const unsigned grid = (unsigned)((a.C + RES_DENSE_BLOCK / 64 - 1) / (RES_DENSE_BLOCK / 64));
-  const bool multi = m.T > 1 || m.samples || m.acc_hist || m.div_hist || m.nleap_total || m.adapt;
+  const KernelLaunch k = nuts_resident_dense_launch(a, m, DENSE);  // (grid, block and LDS; the name is not used here)
   // in-launch adaptation of dense matrices: one per chain, with the transposed-copy workspace as factorisation scratch
   if (m.adapt && !((DENSE & RES_DENSE_METRIC) && (DENSE & RES_DENSE_PER_CHAIN) && m.ad.full && m.imm_ws))
     return hipErrorInvalidValue;
 #define AEHMC_RD(MULTI)                                                                                      \
   do {                                                                                                       \
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_nuts_resident<64, 1, MULTI, DENSE>), \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);                \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.dyn);              \
     if (e != hipSuccess) return e;                                                                           \
-    hipLaunchKernelGGL((k_nuts_resident<64, 1, MULTI, DENSE>), dim3(grid), dim3(RES_DENSE_BLOCK), dyn, st, a, m); \
+    hipLaunchKernelGGL((k_nuts_resident<64, 1, MULTI, DENSE>), k.grid, k.block, k.dyn, st, a, m);             \
   } while (0)
-  if (multi) AEHMC_RD(true);
+  if (nuts_multi(m)) AEHMC_RD(true);
   else AEHMC_RD(false);
 #undef AEHMC_RD
   return hipGetLastError();
@@ -715,14 +720,25 @@ inline ResidentPlan plan_nuts_resident(const EngineArgs &a, const NutsSampleArgs
   if (p.T == 1) p.R = D <= 1 ? 1 : D <= 2 ? 2 : 4;
   else if (p.T < 64) p.R = 4;
   else p.R = D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : 8;
-  p.multi = m.T > 1 || m.samples || m.acc_hist || m.div_hist || m.nleap_total || m.adapt;
+  p.multi = nuts_multi(m);
   p.ckl = p.T == 64 && p.R == 1 && a.C <= 2048 && a.max_exp <= 16;
   p.grid = p.T < 64 ? (unsigned)((a.C * p.T + 255) / 256) : (unsigned)((a.C + 3) / 4);
   p.dyn = p.ckl ? (size_t)4 * a.max_exp * 2 * 64 * sizeof(double) : 0;
   return p;
 }
+// a joint density with a reverse-mode program (run-time compiled only): one wavefront per chain whatever C, the rows of
+// the program (q, dU/dq) of the workgroup's four chains in LDS, no LDS checkpoints beside them
+inline ResidentPlan plan_nuts_resident_joint(const EngineArgs &a, const NutsSampleArgs &m) {
+  return {64, a.D <= 64 ? 1 : a.D <= 128 ? 2 : a.D <= 256 ? 4 : 8, nuts_multi(m), false, (unsigned)((a.C + 3) / 4),
+          (size_t)4 * 2 * a.D * sizeof(double)};
+}
 
 #ifndef __HIPCC_RTC__
+// the run-time compiled copy of a plan's team instantiation
+inline KernelLaunch nuts_resident_launch(const ResidentPlan &p) {
+  return {"aehmc::k_nuts_resident<" + std::to_string(p.T) + ", " + std::to_string(p.R) + ", " + bool_arg(p.multi) + ", 0, " + bool_arg(p.ckl) + ">",
+          dim3(p.grid), dim3(Team<64>::BLOCK), p.dyn};
+}
 template <int T, int R>
 inline hipError_t launch_nuts_resident_tr(const EngineArgs &a, const NutsSampleArgs &m, const ResidentPlan &p,
                                           hipStream_t st) {

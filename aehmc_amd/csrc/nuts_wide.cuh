@@ -651,6 +651,14 @@ inline NutsWidePlan plan_nuts_wide(long long D) {
   p.dyn = p.qgl ? (size_t)2 * (D + 1) * sizeof(double) : 0;
   return p;
 }
+// a traced joint density (run-time compiled only): 512 threads, the program's workgroup, and the rows of its program
+// (q, dU/dq) in LDS at every D
+inline NutsWidePlan plan_nuts_wide_joint(long long D) { return {512, joint_wide_r(D), true, (size_t)2 * (D + 1) * sizeof(double)}; }
+// the run-time compiled copy of a plan's instantiation for target kind `tkind` (AEHMC_T_CUSTOM, AEHMC_T_JOINT)
+inline KernelLaunch nuts_wide_launch(const NutsWidePlan &p, aehmc_target_kind tkind, long long C) {
+  return {"aehmc::k_nuts_wide<" + std::to_string(p.T) + ", " + std::to_string(p.R) + ", " + bool_arg(p.qgl) + ", " + std::to_string((int)tkind) + ">",
+          dim3((unsigned)C), dim3(p.T), p.dyn};
+}
 
 template <int T, int R, bool QGL>
 inline hipError_t launch_nuts_wide_tr(const EngineArgs &a, const NutsWidePlan &p, hipStream_t st) {

@@ -252,6 +252,32 @@ def test_custom_target_compile_error_is_reported(eng):
     np.testing.assert_allclose(st.potential_energy.cpu().numpy(), [StudentT(np.full(3, 4.0), np.ones(3))(np.ones(3))[0]] * 2, rtol=1e-12)
 
 
+def test_custom_target_same_source_keeps_its_programs(eng):
+    """binding the same source with other parameter arrays keeps the compiled programs (no further program compiled or
+    loaded from the disk cache) and samples from the NEW parameters; a source that differs by one constant brings
+    programs of its own"""
+    from aehmc_amd import RandomStream, nuts, targets
+    D, C, max_exp, eps = 8, 4, 5, 0.35
+    r = np.random.default_rng(81)
+    q0, imm, seeds = r.normal(size=(C, D)), 0.5 + r.random(D), [70 + c for c in range(C)]
+
+    def step(source, nu, s):
+        tgt = targets.Custom(source, params=[nu, s])
+        kern = nuts.new_kernel(RandomStream(seeds=seeds), tgt, max_num_expansions=max_exp)
+        info, _ = kern(nuts.new_state(dev(q0), tgt), eps, imm)
+        return info, sum(eng.rtc_stats())
+
+    _, n1 = step(STUDENT_T, 3.0 + 5 * r.random(D), 0.5 + r.random(D))
+    nu, s = 4.0 + 3 * r.random(D), 0.7 + r.random(D)
+    info, n2 = step(STUDENT_T, nu, s)
+    assert n2 == n1, (n1, n2)
+    ref = oracle_nuts(StudentT(nu, s), seeds, q0, eps, imm, max_exp, 1)
+    for c in range(C):
+        np.testing.assert_allclose(info.state.position[c].cpu().numpy(), ref[c][0].state.position, rtol=RTOL, atol=1e-12)
+    _, n3 = step(STUDENT_T.replace("(nu + 1.0)", "(nu + 2.0)"), nu, s)  # (in u and in g: the engine checks one against the other)
+    assert n3 > n2, (n2, n3)
+
+
 def test_custom_target_fp_contract_hmc(eng):
     """the fast-arithmetic mode of the fused HMC kernel with a user-defined target: within 1e-6 of the default mode"""
     from aehmc_amd import RandomStream, hmc, targets
