@@ -1354,6 +1354,63 @@ extern "C" int aehmc_summary_rank(aehmc_ctx *ctx, int64_t R, int64_t D, const do
   return 0;
 }
 
+// Highest-density intervals and the MCSE of quantiles (posterior.cuh): consumers of the same sorted columns, with the
+// scratch, the tiles and the refusals of aehmc_summary_rank.  tile: the coordinates a tile holds, or the refusal.
+static int posterior_shape(aehmc_ctx *ctx, const char *what, int64_t R, int64_t D, const void *work, int64_t work_bytes,
+                           int64_t *tile) {
+  if ((uintptr_t)work % 256) FAIL(std::string(what) + ": work must be 256-byte aligned");
+  if (R >= (int64_t)1 << 31) FAIL(std::string(what) + ": the counts are 32-bit, R must be below 2^31");
+  if (D >= (int64_t)1 << 31) FAIL(std::string(what) + ": D is too large");
+  *tile = work_bytes > 0 ? tu::rank_tile_width(R, D, (size_t)work_bytes) : 0;
+  if (*tile < 1)
+    FAIL(std::string(what) + ": work holds " + std::to_string(work_bytes) + " bytes, one coordinate needs " +
+         std::to_string(tu::rank_work_bytes(R, 1)) + " (aehmc_summary_rank_work gives " +
+         std::to_string(aehmc_summary_rank_work(R, D)) + ")");
+  return 0;
+}
+extern "C" int aehmc_summary_hdi(aehmc_ctx *ctx, int64_t R, int64_t D, const double *samples, double prob,
+                                 double *lower, double *upper, int64_t *index, void *work, int64_t work_bytes,
+                                 void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (R < 1 || D < 1 || !samples || !lower || !upper || !work) FAIL("summary_hdi: bad arguments");
+  if (!(prob > 0.0 && prob <= 1.0)) FAIL("summary_hdi: prob must be within (0, 1], got " + std::to_string(prob));
+  int64_t T = 0;
+  if (int rc = posterior_shape(ctx, "summary_hdi", R, D, work, work_bytes, &T)) return rc;
+  // the window in order statistics, numpy's floor(prob * n), held to R - 1 so that prob = 1 is (min, max)
+  int64_t m = (int64_t)std::floor(prob * (double)R);
+  if (m > R - 1) m = R - 1;
+  static_assert(sizeof(long long) == sizeof(int64_t), "index is written as long long");
+  HIPCHK(tu::hdi(samples, R, D, m, lower, upper, (long long *)index, work, T, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int aehmc_summary_quantile_mcse(aehmc_ctx *ctx, int64_t R, int64_t D, int64_t Q, const double *samples,
+                                           const double *probs, const double *ess, double *out, int64_t *ranks,
+                                           void *work, int64_t work_bytes, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (R < 1 || D < 1 || Q < 1 || !samples || !probs || !ess || !out || !work)
+    FAIL("summary_quantile_mcse: bad arguments");
+  if (Q > AEHMC_SUMMARY_QUANTILE_MAX)
+    FAIL("summary_quantile_mcse: at most " + std::to_string(AEHMC_SUMMARY_QUANTILE_MAX) + " probabilities a call");
+  for (int64_t i = 0; i < Q; ++i)
+    if (!(probs[i] >= 0.0 && probs[i] <= 1.0))
+      FAIL("summary_quantile_mcse: probability " + std::to_string(probs[i]) + " is outside [0, 1]");
+  int64_t T = 0;
+  if (int rc = posterior_shape(ctx, "summary_quantile_mcse", R, D, work, work_bytes, &T)) return rc;
+  HIPCHK(tu::quantile_mcse(samples, R, D, (int)Q, probs, ess, out, (long long *)ranks, work, T, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int aehmc_beta_quantile(aehmc_ctx *ctx, int64_t n, const double *p, const double *a, const double *b,
+                                   double *out, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (n < 1 || !p || !a || !b || !out) FAIL("beta_quantile: bad arguments");
+  if (n >= (int64_t)1 << 37) FAIL("beta_quantile: n is too large");
+  HIPCHK(tu::beta_quantile(n, p, a, b, out, (hipStream_t)stream));
+  return 0;
+}
+
 extern "C" int aehmc_set_option(aehmc_ctx *ctx, const char *name, int64_t value) {
   if (!ctx || !name) return -2;
   if (!strcmp(name, "fused_hmc")) {

@@ -18,6 +18,7 @@
 //  (3) k_rank_out: the row segments are read again, a draw's key is recomputed and its lower and upper bound are
 //      searched in its sorted column: r = (lo + hi + 1) / 2, exact in fp64.  Ties need no pass of their own.  A
 //      coordinate with a NaN answers NaN for every draw.
+// Steps (1) and (2) are launch_rank_sort; posterior.cuh (HDI, MCSE of a quantile) reads the sorted columns it leaves.
 //
 // Cost of the 8-bit digit: 8 passes, each reading the keys twice and writing them once (24 R T bytes); the scatter
 // holds 2 x 16 x 257 counters (32 896 B of LDS) and its 256 offsets, the count 256 counters; registers stay far below
@@ -47,6 +48,10 @@ constexpr size_t RANK_DEFAULT_WORK = (size_t)256 << 20;         // the default s
 __device__ inline unsigned long long rank_key(double v) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(v);
   return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
+}
+// its inverse: the value whose key this is
+__device__ inline double rank_unkey(unsigned long long k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffULL) : ~k));
 }
 // the value that is ranked: folded about the centre if there is one, and -0.0 made +0.0 so that the zeros tie
 __device__ inline double rank_value(double v, const double *centre, long long d) {
@@ -248,7 +253,7 @@ __global__ __launch_bounds__(RANK_THREADS) void k_rank_scatter(const unsigned lo
 // rational function of 0.180625 - q^2 for |q| = |p - 1/2| <= 0.425, of sqrt(-log(min(p, 1 - p))) - 1.6 beyond.  The
 // far-tail branch of the algorithm (sqrt(-log p) > 5, p < 1.4e-11) is left out: the argument (r - 3/8) / (R + 1/4) of
 // a rank is never below 0.625 / 2^31 = 2.9e-10, where sqrt(-log p) = 4.69.
-__device__ inline double rank_ndtri(double p) {
+__host__ __device__ inline double rank_ndtri(double p) {
   const double q = p - 0.5;
   if (fabs(q) <= 0.425) {
     const double r = 0.180625 - q * q;
@@ -322,45 +327,64 @@ __global__ __launch_bounds__(RANK_THREADS) void k_rank_out(RankTileArgs a, const
   }
 }
 
+// the launch geometry of a tile's row kernels (1) and (3)
+struct RankTileGeom {
+  RankTileArgs a;
+  long long subs, rc;  // workgroups across the tile's coordinates, chunks of rows
+};
+inline RankTileGeom rank_tile_geom(const double *x, const double *centre, long long R, long long D, long long d0,
+                                   long long Tc) {
+  RankTileGeom g;
+  int twl = 4;  // workgroups of 16 coordinates, or of the power of two that holds the tile
+  while (twl > 0 && (1LL << (twl - 1)) >= Tc) --twl;
+  const int tw = 1 << twl;
+  g.subs = (Tc + tw - 1) / tw;
+  // about 2048 workgroups in all, each at least one block of 256 rows
+  long long rc = (2048 + g.subs - 1) / g.subs;
+  const long long most = (R + RANK_THREADS - 1) / RANK_THREADS;
+  if (rc > most) rc = most;
+  if (rc > 65535) rc = 65535;
+  long long rows_per_chunk = (R + rc - 1) / rc;
+  rows_per_chunk = (rows_per_chunk + RANK_THREADS - 1) / RANK_THREADS * RANK_THREADS;
+  g.rc = (R + rows_per_chunk - 1) / rows_per_chunk;
+  g.a.x = x; g.a.centre = centre; g.a.R = R; g.a.D = D; g.a.d0 = d0; g.a.T = Tc; g.a.rows_per_chunk = rows_per_chunk;
+  g.a.tw_log2 = twl;
+  return g;
+}
+
+// Steps (1) and (2) for the tile of `g`: afterwards w.keys[RANK_PASSES & 1] (the first buffer) holds the tile's sorted
+// key columns [Tc][R] and w.nan its NaN counts; w.counts is free again.  Shared by launch_rank and posterior.cuh.
+inline hipError_t launch_rank_sort(const RankTileGeom &g, const RankWork &w, hipStream_t st) {
+  const long long R = g.a.R, Tc = g.a.T;
+  const long long chunk = rank_chunk(R), chunks = rank_chunks(R);
+  if (hipError_t e = hipMemsetAsync(w.nan, 0, (size_t)Tc * sizeof(unsigned), st); e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_rank_keys, dim3((unsigned)g.subs, (unsigned)g.rc), dim3(RANK_THREADS), 0, st, g.a, w.keys[0],
+                     w.nan);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  const dim3 grid((unsigned)chunks, (unsigned)Tc);
+  for (int p = 0; p < RANK_PASSES; ++p) {
+    const unsigned long long *src = w.keys[p & 1];
+    unsigned long long *dst = w.keys[(p & 1) ^ 1];
+    hipLaunchKernelGGL(k_rank_count, grid, dim3(RANK_THREADS), 0, st, src, w.counts, R, chunk, 8 * p);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rank_scan, dim3((unsigned)Tc), dim3(RANK_THREADS), 0, st, w.counts, (int)chunks);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rank_scatter, grid, dim3(RANK_THREADS), 0, st, src, dst, (const unsigned *)w.counts, R,
+                       chunk, 8 * p);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 // out [R][D] from x [R][D]: tiles of T coordinates, T >= 1 what `w` (laid out by rank_work(base, R, T)) holds
 inline hipError_t launch_rank(const double *x, const double *centre, long long R, long long D, int mode, double *out,
                               void *work, long long T, hipStream_t st) {
   const RankWork w = rank_work(work, R, T);
-  const long long chunk = rank_chunk(R), chunks = rank_chunks(R);
   for (long long d0 = 0; d0 < D; d0 += T) {
-    const long long Tc = D - d0 < T ? D - d0 : T;
-    int twl = 4;  // workgroups of 16 coordinates, or of the power of two that holds the tile
-    while (twl > 0 && (1LL << (twl - 1)) >= Tc) --twl;
-    const int tw = 1 << twl;
-    const long long subs = (Tc + tw - 1) / tw;
-    // about 2048 workgroups in all, each at least one block of 256 rows
-    long long rc = (2048 + subs - 1) / subs;
-    const long long most = (R + RANK_THREADS - 1) / RANK_THREADS;
-    if (rc > most) rc = most;
-    if (rc > 65535) rc = 65535;
-    long long rows_per_chunk = (R + rc - 1) / rc;
-    rows_per_chunk = (rows_per_chunk + RANK_THREADS - 1) / RANK_THREADS * RANK_THREADS;
-    rc = (R + rows_per_chunk - 1) / rows_per_chunk;
-    RankTileArgs a;
-    a.x = x; a.centre = centre; a.R = R; a.D = D; a.d0 = d0; a.T = Tc; a.rows_per_chunk = rows_per_chunk;
-    a.tw_log2 = twl;
-    if (hipError_t e = hipMemsetAsync(w.nan, 0, (size_t)Tc * sizeof(unsigned), st); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_rank_keys, dim3((unsigned)subs, (unsigned)rc), dim3(RANK_THREADS), 0, st, a, w.keys[0], w.nan);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    const dim3 grid((unsigned)chunks, (unsigned)Tc);
-    for (int p = 0; p < RANK_PASSES; ++p) {
-      const unsigned long long *src = w.keys[p & 1];
-      unsigned long long *dst = w.keys[(p & 1) ^ 1];
-      hipLaunchKernelGGL(k_rank_count, grid, dim3(RANK_THREADS), 0, st, src, w.counts, R, chunk, 8 * p);
-      if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-      hipLaunchKernelGGL(k_rank_scan, dim3((unsigned)Tc), dim3(RANK_THREADS), 0, st, w.counts, (int)chunks);
-      if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-      hipLaunchKernelGGL(k_rank_scatter, grid, dim3(RANK_THREADS), 0, st, src, dst, (const unsigned *)w.counts, R,
-                         chunk, 8 * p);
-      if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
+    const RankTileGeom g = rank_tile_geom(x, centre, R, D, d0, D - d0 < T ? D - d0 : T);
+    if (hipError_t e = launch_rank_sort(g, w, st); e != hipSuccess) return e;
     // (an even number of passes: the sorted columns are back in the first buffer)
-    hipLaunchKernelGGL(k_rank_out, dim3((unsigned)subs, (unsigned)rc), dim3(RANK_THREADS), 0, st, a,
+    hipLaunchKernelGGL(k_rank_out, dim3((unsigned)g.subs, (unsigned)g.rc), dim3(RANK_THREADS), 0, st, g.a,
                        (const unsigned long long *)w.keys[RANK_PASSES & 1], (const unsigned *)w.nan, mode, out);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   }

@@ -74,6 +74,13 @@ long long rank_tile_width(long long R, long long D, size_t bytes);
 long long rank_default_tile(long long R, long long D);
 hipError_t rank(const double *x, const double *centre, long long R, long long D, int mode, double *out, void *work,
                 long long T, hipStream_t st);
+// posterior.cuh (on rank.cuh's sorted columns, the same scratch and tiles; m: the HDI's window in order statistics;
+// probs [Q] host, ess [Q][D] device; beta_quantile: device arrays of n)
+hipError_t hdi(const double *x, long long R, long long D, long long m, double *lower, double *upper, long long *index,
+               void *work, long long T, hipStream_t st);
+hipError_t quantile_mcse(const double *x, long long R, long long D, int Q, const double *probs, const double *ess,
+                         double *out, long long *ranks, void *work, long long T, hipStream_t st);
+hipError_t beta_quantile(long long n, const double *p, const double *a, const double *b, double *out, hipStream_t st);
 // syrk_f64.cuh, pooled_adapt.cuh
 hipError_t syrk_tn(long long C, long long D, const double *X, long long ldx, const double *centre, double w,
                    const double *w_dev, const double *delta, double *S, long long lds, double *partial, hipStream_t st);

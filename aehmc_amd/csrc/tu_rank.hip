@@ -1,6 +1,7 @@
 // One translation unit of libaehmc_hip.so (see tu.h): instantiates the kernels behind the functions below.
 #include "tu.h"
 #include "rank.cuh"
+#include "posterior.cuh"
 
 namespace aehmc {
 namespace tu {
@@ -13,6 +14,17 @@ long long rank_default_tile(long long R, long long D) {
 hipError_t rank(const double *x, const double *centre, long long R, long long D, int mode, double *out, void *work,
                 long long T, hipStream_t st) {
   return launch_rank(x, centre, R, D, mode, out, work, T, st);
+}
+hipError_t hdi(const double *x, long long R, long long D, long long m, double *lower, double *upper, long long *index,
+               void *work, long long T, hipStream_t st) {
+  return launch_hdi(x, R, D, m, lower, upper, index, work, T, st);
+}
+hipError_t quantile_mcse(const double *x, long long R, long long D, int Q, const double *probs, const double *ess,
+                         double *out, long long *ranks, void *work, long long T, hipStream_t st) {
+  return launch_quantile_mcse(x, R, D, Q, probs, ess, out, ranks, work, T, st);
+}
+hipError_t beta_quantile(long long n, const double *p, const double *a, const double *b, double *out, hipStream_t st) {
+  return launch_beta_quantile(n, p, a, b, out, st);
 }
 }  // namespace tu
 }  // namespace aehmc

@@ -796,15 +796,55 @@ class Engine:
         draws of its coordinate; with center [D], of the folded draws |samples - center|.  ``_work_bytes``: scratch
         other than the default (the tile of coordinates sorted at a time follows it; the result does not)."""
         R, D = samples.shape
-        nbytes = int(self.lib.aehmc_summary_rank_work(int(R), int(D))) if _work_bytes is None else int(_work_bytes)
-        if nbytes <= 0:
-            raise EngineError(f"aehmc_summary_rank_work: no scratch size for R = {R}, D = {D} (1 <= R < 2^31)")
-        work = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        work = self._rank_work(R, D, _work_bytes)
         out = torch.empty(R, D, dtype=torch.float64, device=self.device)
         self._check(self.lib.aehmc_summary_rank(self.ctx, R, D, samples.data_ptr(),
                                                 center.data_ptr() if center is not None else None, int(mode),
                                                 out.data_ptr(), work.data_ptr(), work.numel(), self.stream),
                     "aehmc_summary_rank")
+        return out
+
+    def _rank_work(self, R, D, _work_bytes):
+        """The scratch of the calls that sort: the default size, or ``_work_bytes``."""
+        nbytes = int(self.lib.aehmc_summary_rank_work(int(R), int(D))) if _work_bytes is None else int(_work_bytes)
+        if nbytes <= 0:
+            raise EngineError(f"aehmc_summary_rank_work: no scratch size for R = {R}, D = {D} (1 <= R < 2^31)")
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
+    def summary_hdi(self, samples, prob, _work_bytes=None):
+        """(lower [D], upper [D], index [D] int64): the narrowest window of min(floor(prob R), R - 1) + 1 consecutive
+        order statistics of every coordinate of samples [R, D], and where it starts.  ``_work_bytes`` as in
+        ``summary_rank``."""
+        R, D = samples.shape
+        work = self._rank_work(R, D, _work_bytes)
+        lower, upper = (torch.empty(D, dtype=torch.float64, device=self.device) for _ in range(2))
+        index = torch.empty(D, dtype=torch.int64, device=self.device)
+        self._check(self.lib.aehmc_summary_hdi(self.ctx, R, D, samples.data_ptr(), float(prob), lower.data_ptr(),
+                                               upper.data_ptr(), index.data_ptr(), work.data_ptr(), work.numel(),
+                                               self.stream),
+                    "aehmc_summary_hdi")
+        return lower, upper, index
+
+    def summary_quantile_mcse(self, samples, probs, ess, _work_bytes=None):
+        """(out [Q, D], ranks [2, Q, D] int64): the MCSE of the quantiles of samples [R, D] at probs, from the
+        effective sample sizes ess [Q, D] (device) of the indicators, and the two order statistics behind each."""
+        R, D = samples.shape
+        Q = len(probs)
+        work = self._rank_work(R, D, _work_bytes)
+        out = torch.empty(Q, D, dtype=torch.float64, device=self.device)
+        ranks = torch.empty(2, Q, D, dtype=torch.int64, device=self.device)
+        self._check(self.lib.aehmc_summary_quantile_mcse(self.ctx, R, D, Q, samples.data_ptr(),
+                                                         (ct.c_double * Q)(*probs), ess.data_ptr(), out.data_ptr(),
+                                                         ranks.data_ptr(), work.data_ptr(), work.numel(), self.stream),
+                    "aehmc_summary_quantile_mcse")
+        return out, ranks
+
+    def beta_quantile(self, p, a, b):
+        """out shaped like p: the x with I_x(a, b) = p, elementwise over float64 device tensors of one shape."""
+        out = torch.empty_like(p)
+        self._check(self.lib.aehmc_beta_quantile(self.ctx, p.numel(), p.data_ptr(), a.data_ptr(), b.data_ptr(),
+                                                 out.data_ptr(), self.stream),
+                    "aehmc_beta_quantile")
         return out
 
     def profile_enable(self, on=True):

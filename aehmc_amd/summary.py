@@ -28,6 +28,11 @@ classical ``rhat`` cannot -- chains that agree in location but not in scale, tar
 normal scores z = Phi^-1((r - 3/8) / (S + 1/4))), ``bulk_ess`` and ``rank_rhat``, and ``rank_summarize`` for all of
 them at once.  The kernels produce ranks and scores only; every estimator after that is ``summarize`` run on z.
 
+From the same sorted columns, the columns of an ArviZ-style table that were still missing: ``hdi`` (the narrowest window
+of consecutive order statistics), ``mcse_quantile`` / ``mcse_median`` (two order statistics per coordinate, at ranks
+that a beta quantile of the coordinate's own ESS gives; csrc/posterior.cuh), ``mcse_sd``, and ``table`` for the
+``az.summary`` columns at once.
+
 Without the stored draws: ``QuantileSketch``, a fixed-grid histogram per coordinate that ``run`` can feed next to its
 ``Accumulator`` (csrc/sketch.cuh) -- ``quantiles``, ``median`` and ``interval`` of the pooled draws to within one bin
 width, with ``resolved`` to say where that bound holds.
@@ -402,6 +407,104 @@ def rank_summarize(samples, *, batched: bool = True, max_lag: Optional[int] = No
     return RankSummary(rhat=torch.maximum(bulk.rhat, folded), rhat_bulk=bulk.rhat, rhat_folded=folded,
                        ess_bulk=bulk.ess, ess_tail=tail_ess(samples, batched=batched, prob=prob, max_lag=max_lag),
                        lag_truncated=bulk.lag_truncated, num_draws=bulk.num_draws, num_chains=bulk.num_chains)
+
+
+def _check_hdi_prob(prob):
+    if not isinstance(prob, (int, float)) or isinstance(prob, bool):
+        raise ValueError(f"prob must be a float, got {prob!r}")
+    prob = float(prob)
+    if not (math.isfinite(prob) and 0.0 < prob <= 1.0):
+        raise ValueError(f"prob must be finite and within (0, 1], got {prob}")
+    return prob
+
+
+def hdi(samples, prob: float = 0.9, *, batched: bool = True):
+    """``(lower, upper)``: the highest-density interval of mass ``prob`` in (0, 1] of stored draws, per coordinate and
+    with the chains pooled, each shaped like one chain's position.  ``samples`` as ``summarize`` takes them.  Of the
+    windows of m + 1 consecutive order statistics, m = min(floor(prob S), S - 1) over the S pooled draws, the narrowest,
+    and of equally narrow ones the first: ArviZ's unimodal ``hdi`` (the ``hdi_3%`` / ``hdi_97%`` columns of
+    ``az.summary`` at prob = 0.94), exact, from the sorted columns of csrc/rank.cuh.  ``prob = 1`` gives (min, max);
+    zeros of both signs come back as +0.0; a coordinate with a NaN gives NaN."""
+    x, shape = _pooled(samples, batched)
+    prob = _check_hdi_prob(prob)
+    eng = get_engine()
+    _on_device(eng, x)
+    lower, upper, _ = eng.summary_hdi(x, prob)
+    return lower.reshape(shape), upper.reshape(shape)
+
+
+def mcse_quantile(samples, probs, *, batched: bool = True, max_lag: Optional[int] = None):
+    """Monte-Carlo standard error of ``quantiles(samples, probs)``: [Q, *shape], or ``shape`` for a scalar ``probs``
+    (``posterior::mcse_quantile``, ArviZ's ``mcse(method="quantile")``).  Per probability p the split-chain ``ess`` e of
+    the indicator ``x <= quantile(x, p)`` (what ``tail_ess`` forms per tail; ``max_lag`` and the length limit as in
+    ``summarize``), then half the distance between the order statistics at the 0.1586553 and the 0.8413447 quantile of
+    Beta(e p + 1, e (1 - p) + 1), scaled to the S pooled draws.  One indicator array the size of ``samples`` at a time,
+    one kernel call for all probabilities.  A coordinate with a NaN, or whose indicator has no ESS, gives NaN."""
+    x, shape = _pooled(samples, batched)
+    p, scalar = _check_probs(probs)
+    lo = 2 if batched else 1
+    _check_run(samples.shape[0], samples.shape[1] if batched else 1, samples.shape[lo:], True)
+    _check_acov_length(samples.shape[0], True, max_lag)
+    eng = get_engine()
+    _on_device(eng, x)
+    view = (len(p),) + (1,) * (lo - 1) + tuple(samples.shape[lo:])  # (a coordinate's quantile against all its draws)
+    q = eng.summary_quantiles(x, p).reshape(view)
+    e = torch.stack([summarize((samples <= q[i]).to(torch.float64), batched=batched, split=True, max_lag=max_lag)
+                     .ess.reshape(-1) for i in range(len(p))])
+    out, _ = eng.summary_quantile_mcse(x, p, e)
+    return out[0].reshape(shape) if scalar else out.reshape((len(p),) + shape)
+
+
+def mcse_median(samples, **kw):
+    return mcse_quantile(samples, 0.5, **kw)
+
+
+def mcse_sd(samples, *, batched: bool = True, max_lag: Optional[int] = None):
+    """Monte-Carlo standard error of the standard deviation (``posterior::mcse_sd``), shaped like one chain's position:
+    with c = x - the pooled mean, e the split-chain ``ess`` of c^2, Evar = mean(c^2) and
+    varvar = (mean(c^4) - Evar^2) / e, ``sqrt(varvar / Evar / 4)``.  Allocates two arrays the size of ``samples``.
+    ``summarize``'s length limit (``MAX_ACOV_ROWS``) applies."""
+    _check_rank_run(samples, batched, max_lag)
+    _on_device(get_engine(), samples)
+    pool = tuple(range(2 if batched else 1))
+    c = samples - samples.mean(dim=pool, keepdim=True)
+    c2 = c * c
+    del c
+    e = summarize(c2, batched=batched, split=True, max_lag=max_lag).ess
+    evar = c2.mean(dim=pool)
+    varvar = ((c2 * c2).mean(dim=pool) - evar * evar) / e
+    return torch.sqrt(varvar / evar / 4.0)
+
+
+class PosteriorTable(NamedTuple):
+    """The columns of ``az.summary`` per coordinate (device tensors shaped like one chain's position): ``mean``, ``sd``
+    and ``mcse_mean`` are ``summarize``'s mean, sd and mcse; ``hdi_lower`` / ``hdi_upper`` are ``hdi`` at the table's
+    ``prob``; ``mcse_sd``; ``ess_bulk``, ``ess_tail`` and ``rhat`` are ``rank_summarize``'s."""
+    mean: torch.Tensor
+    sd: torch.Tensor
+    hdi_lower: torch.Tensor
+    hdi_upper: torch.Tensor
+    mcse_mean: torch.Tensor
+    mcse_sd: torch.Tensor
+    ess_bulk: torch.Tensor
+    ess_tail: torch.Tensor
+    rhat: torch.Tensor
+    num_draws: int
+    num_chains: int
+
+
+def table(samples, prob: float = 0.9, *, batched: bool = True, max_lag: Optional[int] = None) -> PosteriorTable:
+    """``PosteriorTable`` of stored draws ``samples`` as ``summarize`` takes them: ``summarize``, ``rank_summarize``,
+    ``hdi(prob)`` and ``mcse_sd`` one after the other, every argument checked before any work is done.  Each of them
+    that sorts does its own sort."""
+    _check_rank_run(samples, batched, max_lag)
+    prob = _check_hdi_prob(prob)
+    s = summarize(samples, batched=batched, max_lag=max_lag)
+    r = rank_summarize(samples, batched=batched, max_lag=max_lag)
+    lower, upper = hdi(samples, prob, batched=batched)
+    return PosteriorTable(mean=s.mean, sd=s.sd, hdi_lower=lower, hdi_upper=upper, mcse_mean=s.mcse,
+                          mcse_sd=mcse_sd(samples, batched=batched, max_lag=max_lag), ess_bulk=r.ess_bulk,
+                          ess_tail=r.ess_tail, rhat=r.rhat, num_draws=s.num_draws, num_chains=s.num_chains)
 
 
 # aehmc_hip.h: AEHMC_SUMMARY_SKETCH_MIN_BINS / _MAX_BINS -- the grids of QuantileSketch (a power of two in between)

@@ -591,6 +591,37 @@ int64_t aehmc_summary_rank_work(int64_t R, int64_t D);
 int aehmc_summary_rank(aehmc_ctx *ctx, int64_t R, int64_t D, const double *samples, const double *center, int mode,
                        double *out, void *work, int64_t work_bytes, void *stream);
 
+/* ---- highest-density intervals and the MCSE of quantiles (aehmc_amd/summary.py) ----
+ * The remaining columns of a posterior table that need values at positions of the sorted pooled draws which differ from
+ * coordinate to coordinate: consumers of the sorted key columns of `rank` above (csrc/posterior.cuh).  samples [R, D]
+ * as above, the chains pooled; -0.0 and +0.0 tie and come back as +0.0, -inf and +inf and denormals are ordinary
+ * values, a coordinate that holds a NaN answers NaN.  `work` is that of aehmc_summary_rank_work(R, D): 256-byte
+ * aligned, anything from one coordinate's need upward, and the result does not depend on it; 1 <= R < 2^31.  No
+ * floating-point atomics: two calls on the same input are bit-equal.
+ *
+ * hdi: with s_0 <= ... <= s_{R-1} a coordinate's sorted draws and m = min(floor(prob R), R - 1) (the product in fp64),
+ * the windows w_i = s_{i+m} - s_i, i = 0 ... R - m - 1 (a NaN width, inf - inf, counts as +inf), i* the smallest i of
+ * minimal width: lower [D] = s_{i*}, upper [D] = s_{i*+m}, index [D] (or NULL) = i*; NaN, NaN and -1 for a coordinate
+ * with a NaN.  ArviZ's unimodal hdi with m held to R - 1, so that prob = 1 gives (min, max).  prob in (0, 1].
+ *
+ * quantile_mcse: out [Q, D], the Monte-Carlo standard error of the quantile at probs[q] (posterior::mcse_quantile,
+ * ArviZ's _mcse_quantile).  `probs` is a HOST array of Q values in [0, 1], Q <= AEHMC_SUMMARY_QUANTILE_MAX; ess [Q, D]
+ * (device) the effective sample size of the indicator x <= quantile per probability and coordinate.  With e = ess[q][d],
+ * p = probs[q]: a1 = beta_quantile(0.1586553, e p + 1, e (1 - p) + 1), a2 = beta_quantile(0.8413447, the same),
+ * lo = max(floor(a1 R), 1) - 1, hi = min(ceil(a2 R), R) - 1, out = (s_hi - s_lo) / 2; ranks [2, Q, D] (or NULL) = lo,
+ * hi.  An e that is NaN, infinite or <= 0 gives NaN (ranks -1), as does a coordinate with a NaN.
+ *
+ * beta_quantile: out[i] = the x with I_x(a[i], b[i]) = p[i] (the regularised incomplete beta function), for n
+ * elements of DEVICE arrays; fp64, a, b >= 1 and finite, 0 < p < 1, NaN otherwise.  The continued fraction of I_x with
+ * a bounded number of terms, Halley steps inside a bisection bracket; accuracy in DESIGN.md section 4. */
+int aehmc_summary_hdi(aehmc_ctx *ctx, int64_t R, int64_t D, const double *samples, double prob, double *lower,
+                      double *upper, int64_t *index, void *work, int64_t work_bytes, void *stream);
+int aehmc_summary_quantile_mcse(aehmc_ctx *ctx, int64_t R, int64_t D, int64_t Q, const double *samples,
+                                const double *probs, const double *ess, double *out, int64_t *ranks, void *work,
+                                int64_t work_bytes, void *stream);
+int aehmc_beta_quantile(aehmc_ctx *ctx, int64_t n, const double *p, const double *a, const double *b, double *out,
+                        void *stream);
+
 /* window_adaptation.run (window_adaptation.py:17-116) for a NUTS kernel: num_steps x (one transition
  * with the current per-chain parameters, then aehmc_adapt_update), enqueued in one call.  `stage` /
  * `is_window_end` [num_steps] are HOST arrays from build_schedule.  Before the call the caller binds
