@@ -96,6 +96,31 @@ def diagnostics(layout: Layout, q, U, g, out, tree: bool) -> Diagnostics:
         n_leapfrog=layout.per_chain(out["n_leapfrog"]))
 
 
+def trajectory_lengths(num_integration_steps, num_samples: int):
+    """``num_integration_steps`` of a ``sample`` call: None for a single integer (one L for every transition), or the
+    ``num_samples`` per-transition lengths as a list of ints -- from a sequence, a numpy array or an integer tensor.
+    A wrong count, a negative or a non-integer entry raise ``ValueError``."""
+    x = num_integration_steps
+    if isinstance(x, torch.Tensor):
+        if x.ndim == 0:
+            return None
+        if x.dtype.is_floating_point or x.dtype == torch.bool or x.is_complex():
+            raise ValueError("per-transition num_integration_steps must be an integer tensor")
+        x = x.detach().cpu().numpy()
+    if isinstance(x, (int, np.integer)) or np.ndim(x) == 0:
+        return None
+    arr = np.asarray(x)
+    if arr.ndim != 1 or arr.shape[0] != int(num_samples):
+        raise ValueError(f"per-transition num_integration_steps must hold num_samples = {int(num_samples)} lengths, got "
+                         f"shape {tuple(arr.shape)}")
+    if arr.dtype.kind not in "iu":
+        if arr.dtype.kind != "f" or not np.all(arr == np.floor(arr)):
+            raise ValueError("per-transition num_integration_steps must be integers")
+    if np.any(arr < 0):
+        raise ValueError("num_integration_steps must be >= 0 for every transition")
+    return [int(v) for v in arr]
+
+
 def histories(layout: Layout, out, n: int, keep_samples: bool):
     """(samples [N, ...], acceptance history, divergence history) of a sample() call."""
     samples = out["samples"].reshape((n,) + layout.user_shape) if keep_samples else None

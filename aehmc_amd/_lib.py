@@ -97,6 +97,10 @@ SYMBOLS = {
     "aehmc_hmc_step": (_I, [_P, _I64, _P, _D, _I64, _D, _P, _P, _P, ct.POINTER(CDiagnostics), _P]),
     "aehmc_hmc_sample": (_I, [_P, _I64, _P, _D, _I64, _D, _I64, _P, _P, _P, ct.POINTER(CDiagnostics),
                               _P, _P, _P, _P]),
+    "aehmc_hmc_sample_lengths": (_I, [_P, _I64, _P, _D, ct.POINTER(_I64), _D, _I64, _P, _P, _P, ct.POINTER(CDiagnostics),
+                                      _P, _P, _P, _P]),
+    "aehmc_chees_warmup": (_I, [_P, _I64, _P, _I64, _D, _D, _I64, _D, _D, _P, _P, _P, ct.POINTER(CDiagnostics),
+                                ct.POINTER(CCheesState), _P]),
     "aehmc_nuts_step": (_I, [_P, _I64, _P, _D, _I64, _D, _P, _P, _P, ct.POINTER(CDiagnostics), _P]),
     "aehmc_nuts_sample": (_I, [_P, _I64, _P, _D, _I64, _D, _I64, _P, _P, _P, ct.POINTER(CDiagnostics),
                                _P, _P, _P, _P, _P]),

@@ -4,7 +4,8 @@ Radul, Sountsov, "An adaptive MCMC scheme for setting trajectory lengths in Hami
 ``hmc.new_kernel`` takes ``num_integration_steps`` from the caller.  With many chains it can be adapted: ChEES maximises
 the squared change of ``|q - E q|^2`` per unit of trajectory length, a cross-chain criterion that every warm-up step
 estimates from all chains, and samples with jittered lengths ``L_i = ceil(halton(i) T / step_size)``.  The update is one
-launch sequence of ``aehmc_chees_update`` (csrc/chees.cuh); the transitions are the package's HMC kernels unchanged: they
+launch sequence of ``aehmc_chees_update`` (csrc/chees.cuh); the transitions are the package's HMC kernels, which read the
+length of a transition from device memory, so ``run`` is one engine call and ``sample`` another: they
 export the returned state and the accept flag rather than the proposal, and the accept flag weights the returned state
 (``E[1{accept} f(proposal)] = E[alpha f(proposal)]``; on accept the returned momentum is the flipped end momentum).
 
@@ -48,6 +49,14 @@ def num_integration_steps(step_size: float, trajectory_length: float, index: int
     ``max(1, ceil(T / step_size))``."""
     h = halton(index) if jitter else 1.0
     return max(1, math.ceil((h * float(trajectory_length)) / float(step_size)))
+
+
+def trajectory_lengths(step_size: float, trajectory_length: float, num_samples: int, *, jitter: bool = True,
+                       first: int = 1):
+    """The lengths ``chees.sample`` runs: ``num_integration_steps(step_size, T, first + i, jitter)`` for ``i`` in
+    ``range(num_samples)`` -- also what ``summary.run(..., num_integration_steps=...)`` takes for a jittered run that
+    is summarised without being stored."""
+    return [num_integration_steps(step_size, trajectory_length, int(first) + i, jitter) for i in range(int(num_samples))]
 
 
 class CheesState(NamedTuple):
@@ -196,10 +205,20 @@ def run(kernel, initial_state: IntegratorState, num_steps=1000, inverse_mass_mat
     ``window_adaptation.run(kernel, state, n, pooled=True, num_integration_steps=L0)``; a ``PerChain`` metric and any
     kernel but a static HMC one raise ``ValueError``.
 
-    The transitions run on whatever route ``aehmc_hmc_step`` picks for the target, with the step sizes bound to the
-    adaptation state's ``[C]`` array, which the update rewrites in place.  Per step the position is copied before the
-    transition, and the one int64 ``num_steps`` is read back afterwards: the HMC kernels take L from the host.  That
-    read-back is the only host synchronisation of a step."""
+    ONE engine call (``aehmc_chees_warmup``): per step the position is copied, the transition runs on whatever route
+    ``aehmc_hmc_step`` picks for the target with the step sizes bound to the adaptation state's ``[C]`` array, and the
+    update rewrites that array and ``num_steps`` in place.  On the routes whose kernels read the trajectory length from
+    device memory the transition takes ``num_steps`` from the state itself and the host waits for
+    nothing between the steps; on the others the engine reads the one int64 back per step.  Bit-equal to the
+    hand-driven ``chees.adaptation`` loop either way."""
+    return _run(kernel, initial_state, num_steps, inverse_mass_matrix, initial_step_size, initial_trajectory_length,
+                target_acceptance_rate, learning_rate, max_num_integration_steps)[:3]
+
+
+def _run(kernel, initial_state, num_steps, inverse_mass_matrix, initial_step_size, initial_trajectory_length,
+         target_acceptance_rate, learning_rate, max_num_integration_steps):
+    """``run``, returning also the final ``CheesState`` and the engine's record of the last transition (a dict with
+    ``n_leapfrog`` [C], ``acceptance_probability`` [C], ...; None for ``num_steps`` = 0)."""
     k = _hmc_settings(kernel)
     metric = _Metric(inverse_mass_matrix)
     eps0, T0, target, lr, max_steps = _options(initial_step_size, initial_trajectory_length, target_acceptance_rate,
@@ -214,20 +233,13 @@ def run(kernel, initial_state: IntegratorState, num_steps=1000, inverse_mass_mat
     q, U, g = bind_target(k, eng, initial_state, layout, layout.scalar)
     eng.set_metric(inverse_mass_matrix, D)
     rng, thr = k["holder"]["rng"], k["divergence_threshold"]
-    before = torch.empty_like(q)
-    L = min(int(st["num_steps"]), max_steps)
-    for i in range(n):
-        before.copy_(q)
-        eng._bind_step_sizes(st["step_size"])
-        out = eng.hmc_step(rng, 0.0, L, thr, q, U, g)
-        mom, diag, scalar = metric.velocity_args(eng, D, out["momentum"])
-        eng.chees_update(C, D, i == n - 1, target, lr, max_steps, before, q, mom, diag, scalar, out["flags"][0],
-                         out["acceptance_probability"], cst)
-        L = int(st["num_steps"])  # the read-back
+    # (a scalar metric: the update takes its value from the host, as chees.adaptation's does)
+    scalar = float(_dev_f64(inverse_mass_matrix, eng.device)) if metric.ndim == 0 else 0.0
+    out = eng.chees_warmup(rng, n, target, lr, max_steps, scalar, thr, q, U, g, st, cst) if n > 0 else None
     state = IntegratorState(position=layout.vec(q), momentum=None, potential_energy=layout.per_chain(U),
                             potential_energy_grad=layout.vec(g))
     step_size, T = float(st["step_size"][0]), math.exp(float(st["log_T"]))
-    return state, (step_size, inverse_mass_matrix, T), {k["srng"]: rng}
+    return state, (step_size, inverse_mass_matrix, T), {k["srng"]: rng}, _as_state(st, layout), out
 
 
 def sample(kernel, state: IntegratorState, step_size, inverse_mass_matrix, trajectory_length, num_samples: int, *,
@@ -237,9 +249,10 @@ def sample(kernel, state: IntegratorState, step_size, inverse_mass_matrix, traje
     every time.  Returns what ``kernel.sample`` returns: ``(samples [N, ...], Diagnostics of the last transition,
     acceptance history [N, ...], divergence history [N, ...])``.
 
-    One engine call per transition (the kernels take L per call); ``step_size`` and ``trajectory_length`` are host
-    floats, so nothing is read back.  The draws land in their slot of one ``[N, C, D]`` buffer.  ``first``: continue a
-    Halton sequence across calls (``first = 1 + draws so far``)."""
+    ONE engine call (``aehmc_hmc_sample_lengths``) with the lengths, which the host knows (``step_size`` and
+    ``trajectory_length`` are host floats): one launch on the routes whose kernels read them from device memory, a loop
+    of single transitions inside the engine on the others.  ``first``: continue a Halton sequence across calls
+    (``first = 1 + draws so far``)."""
     k = _hmc_settings(kernel)
     _Metric(inverse_mass_matrix)  # (a PerChain metric has no ONE trajectory length to go with)
     if isinstance(step_size, PerChain):
@@ -247,7 +260,7 @@ def sample(kernel, state: IntegratorState, step_size, inverse_mass_matrix, traje
     eps, T, n = float(step_size), float(trajectory_length), int(num_samples)
     if not eps > 0 or not T > 0 or n < 1 or int(first) < 1:
         raise ValueError("chees.sample needs step_size > 0, trajectory_length > 0, num_samples >= 1 and first >= 1")
-    lengths = [num_integration_steps(eps, T, int(first) + i, jitter) for i in range(n)]
+    lengths = trajectory_lengths(eps, T, n, jitter=jitter, first=first)
     eng = get_engine()
     pos = state.position
     layout, _ = _layout(pos, getattr(kernel, "num_chains", None) or None, getattr(kernel, "batched", pos.ndim == 2))
@@ -255,13 +268,7 @@ def sample(kernel, state: IntegratorState, step_size, inverse_mass_matrix, traje
     q, U, g = bind_target(k, eng, state, layout, layout.scalar)
     eng.set_metric(inverse_mass_matrix, D)
     rng, thr = k["holder"]["rng"], k["divergence_threshold"]
-    samples, acc, div = eng._history_buffers(n, C, D, keep_samples, None)
-    for i, L in enumerate(lengths):
-        out = eng.hmc_step(rng, eng.set_step_sizes(eps), L, thr, q, U, g)
-        if keep_samples:
-            samples[i].copy_(q)
-        acc[i].copy_(out["acceptance_probability"])
-        div[i].copy_(out["is_diverging"])
-    out["samples"], out["acceptance_history"], out["divergence_history"] = samples, acc, div
+    out = eng.hmc_sample_lengths(rng, eng.set_step_sizes(eps), lengths, thr, q, U, g, keep_samples)
+    out["n_leapfrog"].fill_(lengths[-1])  # (documented: of the last transition; the engine reports the call's total)
     samples, acc_hist, div_hist = histories(layout, out, n, keep_samples)
     return samples, diagnostics(layout, q, U, g, out, False), acc_hist, div_hist

@@ -1134,6 +1134,25 @@ AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_hmc_begin_diag(EngineArg
   rng_store(a, c, lane, rng, 0, 0);
   hmc_init_chain<false>(a, c, lane);
 }
+// Per-transition trajectory lengths from device memory (jittered HMC, the ChEES warm-up): transition t of a launch runs
+// min(max(Ls[t * ls], 0), Lmax) leapfrogs; ls = 1: one length per transition, ls = 0: one cell for the whole launch
+// (the warm-up's num_steps).  The clamp bounds the trajectory loop whatever the memory holds.  The EngineArgs kernels take
+// it as a trailing parameter pack `Len... len`, empty (the launch constant L, the kernel as it always was) or one
+// HmcLengths; HmcFusedArgs carries the three fields.  The value is the same for every lane; readfirstlane on both halves
+// says so to the compiler, which then keeps the trip count in scalar registers and the trajectory loop unmasked.
+struct HmcLengths {
+  const long long *Ls;
+  long long ls, Lmax;
+};
+__device__ __forceinline__ long long hmc_length(long long L, long long) { return L; }
+__device__ __forceinline__ long long hmc_length(long long L, long long t, const HmcLengths &n) {
+  if (!n.Ls) return L;
+  const long long v = n.Ls[t * n.ls];
+  const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+  const long long u = (long long)(((unsigned long long)(unsigned)hi << 32) | lo);
+  return u < 0 ? 0 : (u > n.Lmax ? n.Lmax : u);
+}
 // hmc.py:185-204 after the L leapfrogs: flip, energy difference, accept / reject, outputs.  The accept draw comes
 // from `g2` (site #2), which the caller owns (registers, for kernels that run several transitions per launch).
 struct HmcEnd {
@@ -1192,10 +1211,10 @@ __global__ __launch_bounds__(256) void k_hmc_end(EngineArgs a, long long L) {
 }
 // The HMC transition of a small dense problem in one launch (see above: same matrices in LDS, same
 // in-wavefront products, literal dense mode); the chain's scalars stay in registers between the stages.
-template <bool MD, bool TD, bool PC = false>
+template <bool MD, bool TD, bool PC = false, class... Len>
 __global__ __launch_bounds__(FUSED_DENSE_BLOCK) AEHMC_USER_DENSITY_512 void k_hmc_fused_dense(EngineArgs a, const double *prec, double *imm_ws, long long L,
                                                                          long long nt, double *samples, double *acc_hist,
-                                                                         int *div_hist) {
+                                                                         int *div_hist, Len... len) {
   extern __shared__ __attribute__((aligned(16))) double fd_lds[];
   const int D = (int)a.D, DD = D * D;
   constexpr bool MLDS = MD && !PC;
@@ -1215,6 +1234,7 @@ __global__ __launch_bounds__(FUSED_DENSE_BLOCK) AEHMC_USER_DENSITY_512 void k_hm
   if (PC) wave_transpose_to(a.imm + (size_t)c * DD, imm_ws + (size_t)c * DD, D, lane);
   // nt consecutive transitions of the chain in this launch (kernel.sample(nt)); per-transition records optional
   for (long long tt = 0; tt < nt; tt++) {
+  const long long Lt = hmc_length(L, tt, len...);
   {
     Pcg64 g1 = pcg_load(a.rng + (size_t)c * a.nsites * 4);
     draw_momentum<MD>(a, c, lane, g1);
@@ -1230,18 +1250,18 @@ __global__ __launch_bounds__(FUSED_DENSE_BLOCK) AEHMC_USER_DENSITY_512 void k_hm
   const size_t el = row + (on ? lane : 0);
   double q = a.cur_q[el], p = a.cur_p[el], g = a.cur_g[el];
   const double eps_c = 1.0 * (a.eps_c ? a.eps_c[c] : a.eps);
-  for (long long l = 0; l < L; l++)  // trajectory.py:86-95: the whole trajectory in registers
+  for (long long l = 0; l < Lt; l++)  // trajectory.py:86-95: the whole trajectory in registers
     ct.U_cur = leap_small_dense<MD, TD>(a, c, lane, eps_c, immW, PT, D, q, p, g);
   if (on) {
     a.cur_q[el] = q;
     a.cur_p[el] = p;
     a.cur_g[el] = g;
   }
-  if (MD && L > 0) {
+  if (MD && Lt > 0) {
     const double v = wave_matvec_reg(immW, p, D, lane);  // for the final kinetic energy
     if (on) a.cur_v[el] = v;
   }
-  hmc_end_chain<MD>(a, c, lane, ct, L);
+  hmc_end_chain<MD>(a, c, lane, ct, Lt);
   if (samples && on) samples[((size_t)tt * a.C + c) * a.D + lane] = a.q[el];  // (what this lane holds now)
   if (lane == 0) {
     if (acc_hist) acc_hist[(size_t)tt * a.C + c] = a.out.acceptance_probability[c];
@@ -1260,8 +1280,10 @@ struct KernelLaunch {
   size_t dyn;
 };
 inline const char *bool_arg(bool b) { return b ? "true" : "false"; }
-inline KernelLaunch hmc_fused_dense_launch(bool md, bool td, bool pc, long long D, long long C) {
-  return {std::string("aehmc::k_hmc_fused_dense<") + bool_arg(md) + ", " + bool_arg(td) + ", " + bool_arg(pc) + ">",
+// the trailing template argument of an instantiation that takes its trajectory lengths from device memory (HmcLengths)
+inline const char *lengths_arg(bool lengths) { return lengths ? ", aehmc::HmcLengths>" : ">"; }
+inline KernelLaunch hmc_fused_dense_launch(bool md, bool td, bool pc, long long D, long long C, bool lengths = false) {
+  return {std::string("aehmc::k_hmc_fused_dense<") + bool_arg(md) + ", " + bool_arg(td) + ", " + bool_arg(pc) + lengths_arg(lengths),
           dim3((unsigned)((C + FUSED_DENSE_BLOCK / 64 - 1) / (FUSED_DENSE_BLOCK / 64))), dim3(FUSED_DENSE_BLOCK),
           (size_t)((md && !pc ? 2 : 0) + (td ? 1 : 0)) * D * D * sizeof(double)};
 }

@@ -176,6 +176,10 @@ struct aehmc_ctx {
   size_t pool_work_bytes = 0;
   double *chees_work = nullptr;  // ChEES warm-up: partial column sums, the two means, the per-chain criterion (kept, grown)
   size_t chees_work_bytes = 0;
+  double *chees_loop = nullptr;  // aehmc_chees_warmup: the positions before a transition [C,D], momentum . imm [C,D] (kept, grown)
+  size_t chees_loop_bytes = 0;
+  double *hmc_lens = nullptr;  // aehmc_hmc_sample_lengths: the call's trajectory lengths, int64 [num_samples] (kept, grown)
+  size_t hmc_lens_bytes = 0;
   double *syrk_work = nullptr;  // symmetric rank-C update of a mid-size D: the parts of the chain range (kept, grown)
   size_t syrk_work_bytes = 0;
   double *blk_pack = nullptr;  // block-resident dense kernels: the launch's matrices zero-padded to [Dp][Dp] (kept, grown)
@@ -342,6 +346,8 @@ extern "C" int aehmc_destroy(aehmc_ctx *ctx) {
   if (ctx->blk_pack) (void)hipFree(ctx->blk_pack);
   if (ctx->pool_work) (void)hipFree(ctx->pool_work);
   if (ctx->chees_work) (void)hipFree(ctx->chees_work);
+  if (ctx->chees_loop) (void)hipFree(ctx->chees_loop);
+  if (ctx->hmc_lens) (void)hipFree(ctx->hmc_lens);
   if (ctx->syrk_work) (void)hipFree(ctx->syrk_work);
   if (ctx->glm_XT) (void)hipFree(ctx->glm_XT);
   if (ctx->glm_z) (void)hipFree(ctx->glm_z);
@@ -2567,12 +2573,27 @@ static HmcFusedArgs hmc_fused_args(const aehmc_ctx *ctx, int64_t C, uint64_t *rn
   f.rng = rng; f.q = q; f.U = U; f.g = g; f.out = *out;
   return f;
 }
-// n_leapfrog = L T of every chain behind a kernel that ran the whole call.  `only_multi`: the route's kernel writes it
-// itself when T == 1 (which routes do is kernel behaviour)
-static int fill_n_leapfrog(aehmc_ctx *ctx, int64_t C, int64_t L, int64_t T, const aehmc_diagnostics *out, bool only_multi,
+// The trajectory lengths of a call that does not run one L throughout: `dev`[t * stride] on the device (stride 1: one per
+// transition; 0: one cell for the whole call, the ChEES warm-up's num_steps), clamped to [0, max] by the kernels; `host`:
+// the same [T] entries where the caller knows them (nullptr: the warm-up's cell), `sum` their total.
+struct HmcLens {
+  const long long *dev;
+  long long stride;
+  const int64_t *host;
+  long long max, sum;
+};
+// The routes whose kernels read the lengths from device memory (DESIGN section 3 lists them); every other route runs a
+// call with lengths as single transitions, L from `host`.
+static bool hmc_path_reads_lengths(int path) {
+  return path == HMC_PATH_FUSED || path == HMC_PATH_CUSTOM_FUSED || path == HMC_PATH_JOINT_FUSED || path == HMC_PATH_LINREG ||
+         path == HMC_PATH_WIDE || path == HMC_PATH_FUSED_DENSE || path == HMC_PATH_BLOCK_DENSE;
+}
+// n_leapfrog = `total` (L T, or the sum of the call's lengths) of every chain behind a kernel that ran the whole call.
+// `only_multi`: the route's kernel writes it itself when T == 1 (which routes do is kernel behaviour)
+static int fill_n_leapfrog(aehmc_ctx *ctx, int64_t C, int64_t total, int64_t T, const aehmc_diagnostics *out, bool only_multi,
                            hipStream_t st) {
   if ((!only_multi || T > 1) && out->n_leapfrog)
-    LAUNCH(k_fill_i64, C, st, (long long *)out->n_leapfrog, (long long)C, (long long)(L * T));
+    LAUNCH(k_fill_i64, C, st, (long long *)out->n_leapfrog, (long long)C, (long long)total);
   return 0;
 }
 
@@ -2581,19 +2602,32 @@ static int fill_n_leapfrog(aehmc_ctx *ctx, int64_t C, int64_t L, int64_t T, cons
 static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, int64_t L,
                    double divergence_threshold, int64_t T, double *q, double *U, double *g,
                    const aehmc_diagnostics *out, double *samples, double *acc_hist,
-                   int32_t *div_hist, hipStream_t st) {
+                   int32_t *div_hist, hipStream_t st, const HmcLens *len = nullptr) {
   if (L < 0) FAIL("num_integration_steps must be >= 0");
   if (T < 1) FAIL("number of transitions must be >= 1");
   if (!out->acceptance_probability || !out->is_diverging) FAIL("diagnostics arrays missing");
   if (!ctx->has_tgt || !ctx->has_met) FAIL("set_target and set_metric must be called first");
   const int64_t D = ctx->tgt.D;
   const int path = hmc_path(ctx, C);
+  if (len && !hmc_path_reads_lengths(path)) {  // one single-transition pass per entry, as the caller's own loop would run them
+    if (!len->host) FAIL("internal: this route needs the trajectory lengths on the host");
+    for (int64_t t = 0; t < T; t++) {
+      if (int rc = hmc_run(ctx, C, rng, step_size, len->host[t], divergence_threshold, 1, q, U, g, out, nullptr, nullptr,
+                           nullptr, st))
+        return rc;
+      if (int rc = record_transition(ctx, C, D, t, q, out, samples, acc_hist, div_hist, st)) return rc;
+    }
+    return fill_n_leapfrog(ctx, C, len->sum, T, out, true, st);
+  }
+  const int64_t total = len ? len->sum : L * T;  // n_leapfrog of the whole call
+  const HmcLengths dl = len ? HmcLengths{len->dev, len->stride, len->max} : HmcLengths{nullptr, 0, 0};
   // The first four routes run the whole call in one launch on HmcFusedArgs alone: no workspace, so no fill_args (they
   // never report "workspace too small" or "dimensions differ").
   if (path == HMC_PATH_FUSED || path == HMC_PATH_CUSTOM_FUSED || path == HMC_PATH_JOINT_FUSED || path == HMC_PATH_LINREG) {
     if (int rc = check_per_chain(ctx, C)) return rc;
     HmcFusedArgs f = hmc_fused_args(ctx, C, rng, step_size, L, divergence_threshold, q, U, g, out);
     f.T = T; f.samples = samples; f.acc_hist = acc_hist; f.div_hist = div_hist;
+    f.Ls = dl.Ls; f.ls = dl.ls; f.Lmax = dl.Lmax;
     if (path == HMC_PATH_FUSED) {  // fused register-resident path (hmc_fused.cuh): diagonal/scalar metric, coordinate-wise target
       f.tkind = ctx->tgt.kind; f.mu = ctx->tgt.mu; f.sigma = ctx->tgt.sigma; f.log_sigma = ctx->log_sigma;
       f.fc = ctx->opt_fp_contract;
@@ -2607,13 +2641,13 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
       f.tkind = AEHMC_T_CUSTOM; f.cparams = ctx->bound.d_cparams;
       f.fc = ctx->opt_fp_contract;
       return profiled(ctx, st, [&](bool) -> int {
-        return rtc_launch(ctx, RTC_HMC, hmc_fused_launch(D, AEHMC_T_CUSTOM, f.fc, C), st, f);
+        return rtc_launch(ctx, RTC_HMC, hmc_fused_launch(D, AEHMC_T_CUSTOM, f.fc, C, len != nullptr), st, f);
       });
     }
     // traced joint density (round 6): the same fused kernel with the position and gradient rows of the generated program in LDS
     f.tkind = AEHMC_T_JOINT; f.cparams = ctx->bound.d_cparams;
     return profiled(ctx, st, [&](bool) -> int {
-      return rtc_launch(ctx, RTC_JHMCF, hmc_fused_launch(D, AEHMC_T_JOINT, false, C), st, f);
+      return rtc_launch(ctx, RTC_JHMCF, hmc_fused_launch(D, AEHMC_T_JOINT, false, C, len != nullptr), st, f);
     });
   }
   EngineArgs a;
@@ -2651,6 +2685,9 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
         f.acc_hist = acc_hist ? acc_hist + (size_t)t0 * C : nullptr;
         f.div_hist = div_hist ? div_hist + (size_t)t0 * C : nullptr;
         f.out.momentum = t0 + nt == T ? out->momentum : nullptr;  // only the last transition's is observable
+        if (dl.Ls) {  // the chunk's own slice of the lengths
+          f.Ls = dl.Ls + t0 * dl.ls; f.ls = dl.ls; f.Lmax = dl.Lmax;
+        }
         if (f.tkind == AEHMC_T_CUSTOM) {  // the same instantiation (plan_hmc_wide), compiled against the user's function (round 5)
           const KernelLaunch k = hmc_wide_launch(plan_hmc_wide(D, AEHMC_T_CUSTOM), AEHMC_T_CUSTOM, f.fc, C);
           if (int rc = rtc_launch(ctx, RTC_HMC, k, st, f, (const double *)zall, nt)) return rc;
@@ -2662,7 +2699,7 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
           HIPCHK(tu::hmc_resident(f, zall, nt, st));
         }
       }
-      return fill_n_leapfrog(ctx, C, L, T, out, true, st);
+      return fill_n_leapfrog(ctx, C, total, T, out, true, st);
     });
   }
   a.eps = step_size; a.thr = divergence_threshold;
@@ -2673,7 +2710,7 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
     const bool md = a.met_ndim == 2, td = a.tkind == AEHMC_T_DENSE_MVN, pc = md && ctx->met.per_chain;
     EngineArgs b = a;
     b.linear = 0;  // literal products (metrics.py:71)
-    const KernelLaunch k = hmc_fused_dense_launch(md, td, pc, D, C);
+    const KernelLaunch k = hmc_fused_dense_launch(md, td, pc, D, C, len != nullptr);
     double *imm_ws = nullptr;
     if (pc) {  // the chains' transposed matrices
       if (int rc = grow(ctx, &ctx->fd_ws, &ctx->fd_ws_bytes, (size_t)C * D * D * sizeof(double))) return rc;
@@ -2681,16 +2718,25 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
     }
 #define AEHMC_FD_LAUNCH(MDV, TDV, PCV)                                                                         \
   do {                                                                                                         \
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_fused_dense<MDV, TDV, PCV>),               \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.dyn));                       \
-    hipLaunchKernelGGL((k_hmc_fused_dense<MDV, TDV, PCV>), k.grid, k.block, k.dyn, st, b, ctx->tgt.prec, imm_ws, \
-                       (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);                        \
+    if (len) {                                                                                                 \
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_fused_dense<MDV, TDV, PCV, HmcLengths>), \
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.dyn));                     \
+      hipLaunchKernelGGL((k_hmc_fused_dense<MDV, TDV, PCV, HmcLengths>), k.grid, k.block, k.dyn, st, b, ctx->tgt.prec, \
+                         imm_ws, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, dl);          \
+    } else {                                                                                                   \
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_fused_dense<MDV, TDV, PCV>),             \
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.dyn));                     \
+      hipLaunchKernelGGL((k_hmc_fused_dense<MDV, TDV, PCV>), k.grid, k.block, k.dyn, st, b, ctx->tgt.prec, imm_ws, \
+                         (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);                      \
+    }                                                                                                          \
   } while (0)
     const auto launch = [&](bool) -> int {
       if (tjoint) {  // the same kernel, compiled against the user's density
         const double *noprec = nullptr;
-        if (int rc = rtc_launch(ctx, RTC_JHMC, k, st, b, noprec, imm_ws, (long long)L, (long long)T,
-                                samples, acc_hist, (int *)div_hist))
+        if (int rc = len ? rtc_launch(ctx, RTC_JHMC, k, st, b, noprec, imm_ws, (long long)L, (long long)T, samples, acc_hist,
+                                      (int *)div_hist, dl)
+                         : rtc_launch(ctx, RTC_JHMC, k, st, b, noprec, imm_ws, (long long)L, (long long)T, samples, acc_hist,
+                                      (int *)div_hist))
           return rc;
       } else if (md && td && pc) AEHMC_FD_LAUNCH(true, true, true);
       else if (md && td) AEHMC_FD_LAUNCH(true, true, false);
@@ -2702,7 +2748,7 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
     };
 #undef AEHMC_FD_LAUNCH
     if (int rc = profiled(ctx, st, launch)) return rc;
-    return fill_n_leapfrog(ctx, C, L, T, out, true, st);
+    return fill_n_leapfrog(ctx, C, total, T, out, true, st);
   }
   if (path == HMC_PATH_GLM_ROWS) {  // row-reduction target with D <= 32, scalar / diagonal metric: all T transitions in one launch (glm_rows.cuh)
     const bool wg = glm_wg_wanted(ctx, D, C);
@@ -2716,7 +2762,7 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
                         ctx->glm_y, (long long)ctx->glm_N);
     };
     if (int rc = profiled(ctx, st, launch)) return rc;
-    return fill_n_leapfrog(ctx, C, L, T, out, false, st);
+    return fill_n_leapfrog(ctx, C, L * T, T, out, false, st);
   }
   if (path == HMC_PATH_JOINT_WG) {  // traced joint density with long data sweeps, few chains: a workgroup per chain (k_hmc_joint_wg)
     const auto launch = [&](bool) -> int {
@@ -2726,7 +2772,7 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
                         (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);
     };
     if (int rc = profiled(ctx, st, launch)) return rc;
-    return fill_n_leapfrog(ctx, C, L, T, out, false, st);
+    return fill_n_leapfrog(ctx, C, L * T, T, out, false, st);
   }
   if (path == HMC_PATH_JOINT_ROWS) {  // all T transitions in one launch, the lock-step loop of a chain in one wavefront (k_hmc_joint_rows)
     const auto launch = [&](bool) -> int {
@@ -2734,12 +2780,12 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
                         (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);
     };
     if (int rc = profiled(ctx, st, launch)) return rc;
-    return fill_n_leapfrog(ctx, C, L, T, out, false, st);
+    return fill_n_leapfrog(ctx, C, L * T, T, out, false, st);
   }
   if (path == HMC_PATH_PC_DENSE) {  // all T transitions in one launch, the wavefront that owns a chain streaming its matrix (nuts_pc_dense.cuh)
     const auto launch = [&](bool) -> int { HIPCHK(tu::hmc_pc_dense(a, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, st)); return 0; };
     if (int rc = profiled(ctx, st, launch)) return rc;
-    return fill_n_leapfrog(ctx, C, L, T, out, false, st);
+    return fill_n_leapfrog(ctx, C, L * T, T, out, false, st);
   }
   if (path == HMC_PATH_BLOCK_DENSE) {  // all T transitions in one launch, a workgroup per 16 chains, products on MFMA (nuts_block.cuh)
     if (int rc = grow(ctx, &ctx->blk_pack, &ctx->blk_pack_bytes, blk_pack_bytes(D))) return rc;
@@ -2750,17 +2796,21 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
         HIPCHK(blk_pack_matrices(a, nullptr, bp, mats, st));
         EngineArgs b = a;
         b.imm = mats.imm; b.sqrt_mass = mats.sqrt_mass;
-        return rtc_launch(ctx, RTC_BLOCK, block_launch(/*nuts*/ false, ctx->opt_block_dense != 2, D, C), st, b,
-                          (const double *)nullptr, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);
+        const KernelLaunch k = block_launch(/*nuts*/ false, ctx->opt_block_dense != 2, D, C, len != nullptr);
+        return len ? rtc_launch(ctx, RTC_BLOCK, k, st, b, (const double *)nullptr, (long long)L, (long long)T, samples, acc_hist,
+                                (int *)div_hist, dl)
+                   : rtc_launch(ctx, RTC_BLOCK, k, st, b, (const double *)nullptr, (long long)L, (long long)T, samples, acc_hist,
+                                (int *)div_hist);
       }
+      const HmcLengths *dlp = len ? &dl : nullptr;
       if (ctx->opt_block_dense != 2 && block_reg_supported(D))
-        HIPCHK(tu::hmc_block_reg(a, ctx->tgt.prec, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, bp, st));
+        HIPCHK(tu::hmc_block_reg(a, ctx->tgt.prec, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, bp, st, dlp));
       else
-        HIPCHK(tu::hmc_block_dense(a, ctx->tgt.prec, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, bp, st));
+        HIPCHK(tu::hmc_block_dense(a, ctx->tgt.prec, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, bp, st, dlp));
       return 0;
     };
     if (int rc = profiled(ctx, st, launch)) return rc;
-    return fill_n_leapfrog(ctx, C, L, T, out, true, st);
+    return fill_n_leapfrog(ctx, C, total, T, out, true, st);
   }
   for (int64_t t = 0; t < T; t++) {
     EngineArgs wa;  // whitened mode: each transition mapped in and out on its own (white_begin / white_end)
@@ -2777,7 +2827,7 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
       if (int rc = white_end(ctx, a, wb, st)) return rc;
     if (int rc = record_transition(ctx, C, D, t, q, out, samples, acc_hist, div_hist, st)) return rc;
   }
-  return fill_n_leapfrog(ctx, C, L, T, out, true, st);
+  return fill_n_leapfrog(ctx, C, L * T, T, out, true, st);
 }
 
 extern "C" int aehmc_hmc_step(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
@@ -2798,6 +2848,82 @@ extern "C" int aehmc_hmc_sample(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double
   HIPCHK(hipSetDevice(ctx->device));
   return hmc_run(ctx, C, rng, step_size, L, divergence_threshold, num_samples, q, U, g, out, samples,
                  acceptance_history, divergence_history, (hipStream_t)stream);
+}
+
+// aehmc_hmc_sample with one trajectory length per transition: the lengths go into a ctx-owned device array on the
+// caller's stream, and the kernels of the one-launch routes read transition t's from there
+extern "C" int aehmc_hmc_sample_lengths(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, const int64_t *lengths,
+                                        double divergence_threshold, int64_t num_samples, double *q, double *U, double *g,
+                                        const aehmc_diagnostics *out, double *samples, double *acceptance_history,
+                                        int32_t *divergence_history, void *stream) {
+  if (!ctx || !out) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (num_samples < 1) FAIL("number of transitions must be >= 1");
+  if (!lengths) FAIL("lengths missing");
+  HmcLens len{nullptr, 1, lengths, 0, 0};
+  for (int64_t t = 0; t < num_samples; t++) {
+    if (lengths[t] < 0) FAIL("num_integration_steps must be >= 0");
+    if (lengths[t] > len.max) len.max = lengths[t];
+    len.sum += lengths[t];
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = grow(ctx, &ctx->hmc_lens, &ctx->hmc_lens_bytes, (size_t)num_samples * sizeof(int64_t))) return rc;
+  HIPCHK(hipMemcpyAsync(ctx->hmc_lens, lengths, (size_t)num_samples * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  len.dev = (const long long *)ctx->hmc_lens;
+  return hmc_run(ctx, C, rng, step_size, 0, divergence_threshold, num_samples, q, U, g, out, samples, acceptance_history,
+                 divergence_history, st, &len);
+}
+
+// chees.run: num_steps x (q -> before; one HMC transition of state->num_steps leapfrogs; momentum . imm for a dense
+// metric; aehmc_chees_update), enqueued in one call -- the same kernels in the same order as the caller's own loop
+extern "C" int aehmc_chees_warmup(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_t num_steps,
+                                  double target_acceptance_rate, double learning_rate, int64_t max_num_steps,
+                                  double inverse_mass_scalar, double divergence_threshold, double *q, double *U, double *g,
+                                  const aehmc_diagnostics *out, const aehmc_chees_state *state, void *stream) {
+  if (!ctx || !out || !state) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (!ctx->has_tgt || !ctx->has_met) FAIL("set_target and set_metric must be called first");
+  if (num_steps < 0) FAIL("chees: num_steps must be >= 0");
+  if (max_num_steps < 1) FAIL("chees: max_num_steps must be at least 1");
+  if (ctx->met.per_chain) FAIL("chees warm-up needs ONE shared metric bound");
+  if (!state->step_size || !state->num_steps || ctx->eps_c != state->step_size || ctx->eps_n != C)
+    FAIL("chees warm-up: the bound step sizes are not the adaptation state's own array (bind state->step_size with "
+         "aehmc_set_step_sizes)");
+  if (!out->momentum || !out->is_turning || !out->acceptance_probability)
+    FAIL("chees warm-up needs out->momentum, out->is_turning (the accept flag) and out->acceptance_probability");
+  const int64_t D = ctx->tgt.D;
+  const int nd = ctx->met.ndim;
+  const size_t vec = (size_t)C * D * sizeof(double);
+  if (int rc = grow(ctx, &ctx->chees_loop, &ctx->chees_loop_bytes, (nd == 2 ? 2 : 1) * vec)) return rc;
+  double *before = ctx->chees_loop, *prod = ctx->chees_loop + (size_t)C * D;
+  const bool on_device = hmc_path_reads_lengths(hmc_path(ctx, C));
+  const HmcLens len{(const long long *)state->num_steps, 0, nullptr, max_num_steps, 0};
+  for (int64_t i = 0; i < num_steps; i++) {
+    HIPCHK(hipMemcpyAsync(before, q, vec, hipMemcpyDeviceToDevice, st));
+    if (on_device) {  // the transition reads the cell itself (clamped to max_num_steps, which init does not apply)
+      if (int rc = hmc_run(ctx, C, rng, 0.0, 0, divergence_threshold, 1, q, U, g, out, nullptr, nullptr, nullptr, st, &len))
+        return rc;
+    } else {  // the route takes L from the host: the one int64 is read back, as chees.adaptation's caller does
+      int64_t L = 0;
+      HIPCHK(hipMemcpyAsync(&L, state->num_steps, sizeof(L), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      L = L < 0 ? 0 : (L > max_num_steps ? max_num_steps : L);
+      if (int rc = hmc_run(ctx, C, rng, 0.0, L, divergence_threshold, 1, q, U, g, out, nullptr, nullptr, nullptr, st))
+        return rc;
+    }
+    const double *mom = out->momentum;
+    if (nd == 2) {  // (imm is symmetric: momentum . imm^T)
+      if (int rc = gemm(ctx, C, D, D, out->momentum, D, ctx->met.imm, D, prod, D, st)) return rc;
+      mom = prod;
+    }
+    if (int rc = aehmc_chees_update(ctx, C, D, i == num_steps - 1, target_acceptance_rate, learning_rate, max_num_steps,
+                                    before, q, mom, nd == 1 ? ctx->met.imm : nullptr,
+                                    nd == 2 ? 1.0 : (nd == 1 ? 0.0 : inverse_mass_scalar), out->is_turning,
+                                    out->acceptance_probability, state, stream))
+      return rc;
+  }
+  return 0;
 }
 
 // window_adaptation.run around an HMC kernel (window_adaptation.py:66: `kernel(chain_state, *parameters)` with the

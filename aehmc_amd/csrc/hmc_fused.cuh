@@ -41,7 +41,13 @@ struct HmcFusedArgs {
   int32_t *div_hist; // [T,C] or null
   int fc;            // "fp_contract" option: fast arithmetic in the leapfrog bodies (1e-6 instead of bit parity)
   const double *const *cparams;  // user-defined target (AEHMC_T_CUSTOM, run-time compiled instantiations only)
+  // per-transition trajectory lengths from device memory (engine.cuh: HmcLengths); Ls == nullptr: L for every transition
+  const long long *Ls;
+  long long ls, Lmax;
 };
+__device__ __forceinline__ long long hmc_length(const HmcFusedArgs &a, long long t) {
+  return hmc_length(a.L, t, HmcLengths{a.Ls, a.ls, a.Lmax});
+}
 
 inline bool target_is_elem_host(int k) {
   return k == AEHMC_T_STD_NORMAL || k == AEHMC_T_ISO_GAUSSIAN || k == AEHMC_T_DIAG_GAUSSIAN;
@@ -73,7 +79,11 @@ constexpr int hmc_fused_min_waves(int R, int TK) {
   return TK == AEHMC_T_JOINT ? 1 : R <= 4 ? 4 : (R == 8 && TK != AEHMC_T_DIAG_GAUSSIAN ? 3 : 1);
 }
 
-template <int R, int TK, bool FC = false>
+// LS: the instantiation that reads the length of every transition from a.Ls.  It is one of its own because the kernel
+// runs at the limit of its scalar registers: the three fields and the running total, live across the trajectory loop,
+// would cost the launch-constant path one or two VGPRs of spilled scalars (and k_hmc_fused<4, diagonal Gaussian> 12 bytes
+// of scratch).  With LS = false the kernel never looks at a.Ls.
+template <int R, int TK, bool FC = false, bool LS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(hmc_fused_min_waves(R, TK)))) void k_hmc_fused(HmcFusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) double zlds[];  // [4 waves][R*64]
   __shared__ double ztab[ZIG_LDS_DOUBLES];
@@ -120,7 +130,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(hmc_fused_m
   }
 
   const PcgLaneJump jump1 = pcg_lane_jump(g1);
+  long long n_leap = 0;
   for (long long t = 0; t < a.T; t++) {
+    const long long Lt = LS ? hmc_length(a, t) : a.L;
+    if (LS) n_leap += Lt;
     wave_normals(g1, a.D, [=](long long i, double z) { zrow[i] = z; }, tab, jump1);  // metrics.py:65-68
     __threadfence_block();
     double kd = 0.0;
@@ -141,14 +154,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(hmc_fused_m
     if (FC && TK != AEHMC_T_JOINT) {
       constexpr bool DGT = TK == AEHMC_T_DIAG_GAUSSIAN || TK == AEHMC_T_CUSTOM;  // otherwise dU/dq == q
       constexpr bool CUS = TK == AEHMC_T_CUSTOM;
-      if (a.L > 0) {
+      if (Lt > 0) {
         // half kick | (drift, full kick) x (L - 1) | drift, half kick: no per-iteration select, four leapfrogs per
         // trip of the loop (the body is four instructions per element: loop overhead would otherwise match it)
         const double neg_eps = -eps;
 #pragma unroll
         for (int r = 0; r < R; r++) p[r] = __builtin_fma(-b, DGT ? g[r] : q[r], p[r]);
 #pragma unroll 4
-        for (long long l = 1; l < a.L; l++) {
+        for (long long l = 1; l < Lt; l++) {
 #pragma unroll
           for (int r = 0; r < R; r++) {
             q[r] = __builtin_fma(aim[FC ? r : 0], p[r], q[r]);
@@ -176,7 +189,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(hmc_fused_m
 #ifdef AEHMC_JOINT_GRAD
     } else if (TK == AEHMC_T_JOINT) {
       double *const grow = zrow + R * 64;
-      for (long long l = 0; l < a.L; l++) {  // leap_stages<1,1,0>, joint_rows_eval, leap_stages<0,0,1>
+      for (long long l = 0; l < Lt; l++) {  // leap_stages<1,1,0>, joint_rows_eval, leap_stages<0,0,1>
 #pragma unroll
         for (int r = 0; r < R; r++) {
           p[r] = p[r] - b * g[r];
@@ -199,7 +212,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(hmc_fused_m
       __threadfence_block();
 #endif
     } else if (TK == AEHMC_T_CUSTOM) {
-      for (long long l = 0; l < a.L; l++) {  // leap_stages<1,1,1> with the user's gradient
+      for (long long l = 0; l < Lt; l++) {  // leap_stages<1,1,1> with the user's gradient
 #pragma unroll
         for (int r = 0; r < R; r++) {
           p[r] = p[r] - b * g[r];
@@ -210,7 +223,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(hmc_fused_m
         }
       }
     } else if (TK == AEHMC_T_DIAG_GAUSSIAN) {
-      for (long long l = 0; l < a.L; l++) {  // trajectory.py:86-95, integrators.py:54-73
+      for (long long l = 0; l < Lt; l++) {  // trajectory.py:86-95, integrators.py:54-73
 #pragma unroll
         for (int r = 0; r < R; r++) {
           p[r] = p[r] - b * g[r];
@@ -225,7 +238,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(hmc_fused_m
       double bq[R];
 #pragma unroll
       for (int r = 0; r < R; r++) bq[r] = b * q[r];
-      for (long long l = 0; l < a.L; l++) {
+      for (long long l = 0; l < Lt; l++) {
 #pragma unroll
         for (int r = 0; r < R; r++) {
           p[r] = p[r] - bq[r];
@@ -261,7 +274,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(hmc_fused_m
     }
     usum = wave_sum(usum);
     kd = wave_sum(kd);
-    const double Unew = TK == AEHMC_T_JOINT ? U_joint : a.L > 0 ? (TK == AEHMC_T_ISO_GAUSSIAN ? 0.5 * usum : usum) : U;
+    const double Unew = TK == AEHMC_T_JOINT ? U_joint : Lt > 0 ? (TK == AEHMC_T_ISO_GAUSSIAN ? 0.5 * usum : usum) : U;
     double delta = H0 - (Unew + 0.5 * kd);
     if (isnan(delta)) delta = -INFINITY;
     is_div = fabs(delta) > a.thr;
@@ -305,7 +318,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(hmc_fused_m
     a.U[c] = U;
     a.out.acceptance_probability[c] = pa;
     a.out.is_diverging[c] = is_div;
-    if (a.out.n_leapfrog) a.out.n_leapfrog[c] = a.L * a.T;
+    if (a.out.n_leapfrog) a.out.n_leapfrog[c] = LS ? n_leap : a.L * a.T;
     if (a.out.is_turning) a.out.is_turning[c] = acc;  // HMC: reused as the accept flag
   }
 }
@@ -414,8 +427,11 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
   const double b = 0.5 * eps, aa = 1 * eps;
   double pa = 0.0, U_joint = 0.0;
   int is_div = 0, acc = 0, any_acc = 0;
+  long long n_leap = 0;
   for (int tt = 0; tt < nt; tt++) {
     const bool last_t = tt == nt - 1;
+    const long long Lt = hmc_length(a, tt);  // (the engine hands each launch the slice of its own transitions)
+    n_leap += Lt;
     double kd = 0.0, zero = 0.0;
     RENEW_TB();
 #pragma unroll
@@ -428,7 +444,7 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
     sum2(kd, zero);
     const double H0 = U + 0.5 * kd;  // hmc.py:187
     if (FC && !JT) {  // fast arithmetic (see k_hmc_fused): fused multiply-adds, eps * imm formed once, inner half kicks merged
-      if (a.L > 0) {
+      if (Lt > 0) {
         double aim[FC ? R : 1];
 #pragma unroll
         for (int r = 0; r < R; r++) {
@@ -437,7 +453,7 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
         }
         const double neg_eps = -eps;
 #pragma unroll 4
-        for (long long l = 1; l < a.L; l++) {  // (drift, full kick) x (L - 1)
+        for (long long l = 1; l < Lt; l++) {  // (drift, full kick) x (L - 1)
           if (DG) RENEW_TB();
 #pragma unroll
           for (int r = 0; r < R; r++) {
@@ -466,7 +482,7 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
       }
 #ifdef AEHMC_JOINT_GRAD
     } else if (JT) {
-      for (long long l = 0; l < a.L; l++) {  // trajectory.py:86-95, integrators.py:54-73
+      for (long long l = 0; l < Lt; l++) {  // trajectory.py:86-95, integrators.py:54-73
         RENEW_TB();
 #pragma unroll
         for (int r = 0; r < R; r++) {
@@ -492,7 +508,7 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
       }
 #endif
     } else if (DG) {
-      for (long long l = 0; l < a.L; l++) {  // trajectory.py:86-95, integrators.py:54-73
+      for (long long l = 0; l < Lt; l++) {  // trajectory.py:86-95, integrators.py:54-73
         RENEW_TB();
 #pragma unroll
         for (int r = 0; r < R; r++) {
@@ -516,7 +532,7 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
       double bq[R];
 #pragma unroll
       for (int r = 0; r < R; r++) bq[r] = b * q[QI(r)];
-      for (long long l = 0; l < a.L; l++) {
+      for (long long l = 0; l < Lt; l++) {
 #pragma unroll
         for (int r = 0; r < R; r++) {
           p[r] = p[r] - bq[r];
@@ -558,7 +574,7 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
       for (int r = 0; r < R; r++) p[r] = zn[EI(r)];
     }
     sum2(usum, kd);
-    const double Unew = a.L > 0 ? (JT ? U_joint : TK == AEHMC_T_ISO_GAUSSIAN ? 0.5 * usum : usum) : U;
+    const double Unew = Lt > 0 ? (JT ? U_joint : TK == AEHMC_T_ISO_GAUSSIAN ? 0.5 * usum : usum) : U;
     double delta = H0 - (Unew + 0.5 * kd);
     if (isnan(delta)) delta = -INFINITY;
     is_div = fabs(delta) > a.thr;
@@ -624,7 +640,7 @@ __global__ __launch_bounds__(T) void k_hmc_wide(HmcFusedArgs a, const double *zb
     if (any_acc) a.U[c] = U;
     a.out.acceptance_probability[c] = pa;
     a.out.is_diverging[c] = is_div;
-    if (a.out.n_leapfrog) a.out.n_leapfrog[c] = a.L * nt;
+    if (a.out.n_leapfrog) a.out.n_leapfrog[c] = n_leap;
     if (a.out.is_turning) a.out.is_turning[c] = acc;  // HMC: reused as the accept flag
   }
 #undef GR
@@ -708,33 +724,34 @@ inline hipError_t launch_hmc_resident(const HmcFusedArgs &a, const double *zbuf,
   }
 }
 
-template <int R, bool FC>
+template <int R, bool FC, bool LS>
 inline hipError_t launch_hmc_fused_r(const HmcFusedArgs &a, hipStream_t st) {
   dim3 grid((unsigned)((a.C + 3) / 4)), block(256);
   size_t lds = (size_t)4 * R * 64 * sizeof(double);
   switch (a.tkind) {
     case AEHMC_T_STD_NORMAL:
-      hipLaunchKernelGGL((k_hmc_fused<R, AEHMC_T_STD_NORMAL, FC>), grid, block, lds, st, a);
+      hipLaunchKernelGGL((k_hmc_fused<R, AEHMC_T_STD_NORMAL, FC, LS>), grid, block, lds, st, a);
       break;
     case AEHMC_T_ISO_GAUSSIAN:
-      hipLaunchKernelGGL((k_hmc_fused<R, AEHMC_T_ISO_GAUSSIAN, FC>), grid, block, lds, st, a);
+      hipLaunchKernelGGL((k_hmc_fused<R, AEHMC_T_ISO_GAUSSIAN, FC, LS>), grid, block, lds, st, a);
       break;
     default:
-      hipLaunchKernelGGL((k_hmc_fused<R, AEHMC_T_DIAG_GAUSSIAN, FC>), grid, block, lds, st, a);
+      hipLaunchKernelGGL((k_hmc_fused<R, AEHMC_T_DIAG_GAUSSIAN, FC, LS>), grid, block, lds, st, a);
   }
   return hipGetLastError();
 }
-template <bool FC>
+template <bool FC, bool LS>
 inline hipError_t launch_hmc_fused_fc(const HmcFusedArgs &a, hipStream_t st) {
   const long long r = (a.D + 63) / 64;
-  if (r <= 1) return launch_hmc_fused_r<1, FC>(a, st);
-  if (r <= 2) return launch_hmc_fused_r<2, FC>(a, st);
-  if (r <= 4) return launch_hmc_fused_r<4, FC>(a, st);
-  if (r <= 8) return launch_hmc_fused_r<8, FC>(a, st);
-  return launch_hmc_fused_r<16, FC>(a, st);
+  if (r <= 1) return launch_hmc_fused_r<1, FC, LS>(a, st);
+  if (r <= 2) return launch_hmc_fused_r<2, FC, LS>(a, st);
+  if (r <= 4) return launch_hmc_fused_r<4, FC, LS>(a, st);
+  if (r <= 8) return launch_hmc_fused_r<8, FC, LS>(a, st);
+  return launch_hmc_fused_r<16, FC, LS>(a, st);
 }
 inline hipError_t launch_hmc_fused(const HmcFusedArgs &a, hipStream_t st) {
-  return a.fc ? launch_hmc_fused_fc<true>(a, st) : launch_hmc_fused_fc<false>(a, st);
+  if (a.Ls) return a.fc ? launch_hmc_fused_fc<true, true>(a, st) : launch_hmc_fused_fc<false, true>(a, st);
+  return a.fc ? launch_hmc_fused_fc<true, false>(a, st) : launch_hmc_fused_fc<false, false>(a, st);
 }
 #endif  // __HIPCC_RTC__
 // elements per lane of the k_hmc_fused instantiation that holds a D-dimensional chain
@@ -745,9 +762,9 @@ inline int hmc_fused_r(long long D) {
 #ifndef __HIPCC_RTC__
 // the run-time compiled copy of that instantiation (AEHMC_T_CUSTOM; AEHMC_T_JOINT: the gradient rows of the program in
 // LDS beside the position rows)
-inline KernelLaunch hmc_fused_launch(long long D, aehmc_target_kind tkind, bool fc, long long C) {
+inline KernelLaunch hmc_fused_launch(long long D, aehmc_target_kind tkind, bool fc, long long C, bool lengths = false) {
   const int R = hmc_fused_r(D);
-  return {"aehmc::k_hmc_fused<" + std::to_string(R) + ", " + std::to_string((int)tkind) + ", " + bool_arg(fc) + ">",
+  return {"aehmc::k_hmc_fused<" + std::to_string(R) + ", " + std::to_string((int)tkind) + ", " + bool_arg(fc) + (lengths ? ", true>" : ">"),
           dim3((unsigned)((C + 3) / 4)), dim3(256), (size_t)4 * (tkind == AEHMC_T_JOINT ? 2 : 1) * R * 64 * sizeof(double)};
 }
 #endif  // __HIPCC_RTC__

@@ -78,7 +78,10 @@ __global__ __launch_bounds__(LR_BLOCK) void k_hmc_linreg(HmcFusedArgs a) {
   double p = 0.0, p0 = 0.0, pa = 0.0;
   int is_div = 0, acc = 0;
 
+  long long n_leap = 0;
   for (long long t = 0; t < a.T; t++) {
+    const long long Lt = hmc_length(a, t);  // (the same in every wavefront: the barriers of the row sums hold)
+    n_leap += Lt;
     double kd = 0.0, Unew = U;
     const double qs = q, gs = g;
     if (!ghost) {  // metrics.py:65-68: z ~ normal(size=2), two consecutive draws of site #1
@@ -89,7 +92,7 @@ __global__ __launch_bounds__(LR_BLOCK) void k_hmc_linreg(HmcFusedArgs a) {
       kd = wave_sum(ok ? v_init * p : 0.0);
     }
     const double H0 = U + 0.5 * kd;  // hmc.py:187
-    for (long long l = 0; l < a.L; l++) {  // trajectory.py:86-95, integrators.py:54-73
+    for (long long l = 0; l < Lt; l++) {  // trajectory.py:86-95, integrators.py:54-73
       if (dm) {
         const double ph = p - b * g;
         const double vh = vel(ph);  // (both elements of p_half: outside the lane mask)
@@ -158,7 +161,7 @@ __global__ __launch_bounds__(LR_BLOCK) void k_hmc_linreg(HmcFusedArgs a) {
       const double pf = -1.0 * p;  // hmc.py:185
       const double v_fin = vel(pf);
       kd = wave_sum(ok ? v_fin * pf : 0.0);
-      if (a.L == 0) Unew = U;
+      if (Lt == 0) Unew = U;
       double delta = H0 - (Unew + 0.5 * kd);
       if (isnan(delta)) delta = -INFINITY;
       is_div = fabs(delta) > a.thr;
@@ -191,7 +194,7 @@ __global__ __launch_bounds__(LR_BLOCK) void k_hmc_linreg(HmcFusedArgs a) {
     a.U[c] = U;
     a.out.acceptance_probability[c] = pa;
     a.out.is_diverging[c] = is_div;
-    if (a.out.n_leapfrog) a.out.n_leapfrog[c] = a.L * a.T;
+    if (a.out.n_leapfrog) a.out.n_leapfrog[c] = n_leap;
     if (a.out.is_turning) a.out.is_turning[c] = acc;  // HMC: reused as the accept flag
   }
 }

@@ -262,10 +262,10 @@ __global__ __launch_bounds__(BLK_THREADS) void k_nuts_block_dense(EngineArgs a, 
 }
 
 // HMC: hmc_run's lock-step loop (engine.hip) for 16 chains, nt transitions x L leapfrogs in one launch.
-template <bool TDENSE>
+template <bool TDENSE, class... Len>
 __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_dense(EngineArgs a, const double *prec, long long L,
                                                                   long long nt, double *samples, double *acc_hist,
-                                                                  int *div_hist) {
+                                                                  int *div_hist, Len... len) {
   extern __shared__ __attribute__((aligned(16))) double blk_lds[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -282,13 +282,14 @@ __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_dense(EngineArgs a, c
     U_state = a.U[c];
   }
   for (long long tt = 0; tt < nt; tt++) {
+    const long long Lt = hmc_length(L, tt, len...);  // (the same for every chain: the barriers inside the products hold)
     if (valid) draw_momentum<true>(a, c, lane, g1);
     blk_gemm(blk_lds, S, a.zbuf, a.sqrt_mass, a.cur_p, a.D, c0, a.C, wave, lane, tm);
     blk_gemm(blk_lds, S, a.cur_p, a.imm, a.cur_v, a.D, c0, a.C, wave, lane, tm);
     blk_gemm(blk_lds, S, a.g, a.imm, a.cur_w, a.D, c0, a.C, wave, lane, tm);
     ChainCtl ct = {};
     if (valid) ct = hmc_init_chain<true>(a, c, lane, &U_state);
-    for (long long l = 0; l < L; l++) {  // trajectory.py:86-95
+    for (long long l = 0; l < Lt; l++) {  // trajectory.py:86-95
       if (valid) {
         double U_new = 0.0;
         if (leap_linear<12>(a, c, lane, 1, U_new)) ct.U_cur = U_new;
@@ -302,7 +303,7 @@ __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_dense(EngineArgs a, c
     }
     if (valid) {
       __threadfence_block();
-      const HmcEnd e = hmc_end_chain_rng<true>(a, c, lane, ct, L, g2);
+      const HmcEnd e = hmc_end_chain_rng<true>(a, c, lane, ct, Lt, g2);
       if (e.acc) U_state = ct.U_cur;
       if (samples) {  // (a.q: what this lane has just written, or left untouched on rejection)
         double *dst = samples + ((size_t)tt * a.C + c) * a.D;
@@ -363,7 +364,8 @@ inline hipError_t launch_nuts_block_dense(EngineArgs a, NutsSampleArgs m, double
 }
 
 inline hipError_t launch_hmc_block_dense(EngineArgs a, const double *prec, long long L, long long nt,
-                                         double *samples, double *acc_hist, int *div_hist, double *bp, hipStream_t st) {
+                                         double *samples, double *acc_hist, int *div_hist, double *bp, hipStream_t st,
+                                         const HmcLengths *len = nullptr) {
   const bool td = a.tkind == AEHMC_T_DENSE_MVN;
   BlkMats mats;
   if (hipError_t e = blk_pack_matrices(a, prec, bp, mats, st)) return e;
@@ -374,9 +376,16 @@ inline hipError_t launch_hmc_block_dense(EngineArgs a, const double *prec, long 
   do {                                                                                                       \
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_block_dense<TDV>),              \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);                \
+    if (e == hipSuccess && len)                                                                              \
+      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_block_dense<TDV, HmcLengths>),           \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);                         \
     if (e != hipSuccess) return e;                                                                           \
-    hipLaunchKernelGGL((k_hmc_block_dense<TDV>), grid, block, dyn, st, a, mats.prec, L, nt, samples, acc_hist, \
-                       div_hist);                                                                            \
+    if (len)                                                                                                 \
+      hipLaunchKernelGGL((k_hmc_block_dense<TDV, HmcLengths>), grid, block, dyn, st, a, mats.prec, L, nt, samples, \
+                         acc_hist, div_hist, *len);                                                          \
+    else                                                                                                     \
+      hipLaunchKernelGGL((k_hmc_block_dense<TDV>), grid, block, dyn, st, a, mats.prec, L, nt, samples, acc_hist, \
+                         div_hist);                                                                          \
   } while (0)
   if (td) AEHMC_BLK(true);
   else AEHMC_BLK(false);

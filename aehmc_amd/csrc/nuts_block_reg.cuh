@@ -320,10 +320,10 @@ __global__ __launch_bounds__(BLK_THREADS) void k_nuts_block_reg(EngineArgs a, Nu
 // HMC: nt transitions x L leapfrogs, the chains' q, p, v in registers, dU/dq and w = imm dU/dq in the LDS rows the
 // products write (as above) -- hmc_run's lock-step loop: hmc_init_chain, leap_linear<12> / <3>, hmc_end_chain.  The
 // state a rejection falls back to is the caller's q / dU/dq, rewritten at every accepted transition.
-template <int R, bool TDENSE>
+template <int R, bool TDENSE, class... Len>
 __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_reg(EngineArgs a, const double *prec, long long L,
                                                                 long long nt, double *samples, double *acc_hist,
-                                                                int *div_hist) {
+                                                                int *div_hist, Len... len) {
   extern __shared__ __attribute__((aligned(16))) double blk_lds[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -356,6 +356,7 @@ __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_reg(EngineArgs a, con
   Pcg64 g1 = {}, g2 = {};
   double U = 0.0, eps = 0.0, pa = 0.0;
   int is_div = 0, acc = 0;
+  long long Lt = L;
   if (valid) {
     g1 = pcg_load(a.rng + (size_t)c * a.nsites * 4);
     g2 = pcg_load(a.rng + ((size_t)c * a.nsites + 1) * 4);
@@ -366,6 +367,7 @@ __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_reg(EngineArgs a, con
   blk_barrier_lds();
   for (long long tt = 0; tt < nt; tt++) {
     const bool last_t = tt == nt - 1;
+    Lt = hmc_length(L, tt, len...);  // (the same for every chain: the barriers between the products hold)
     if (valid) {
       wave_normals(g1, D, [=](long long i, double z) { xrow[i] = z; });
       __threadfence_block();
@@ -397,7 +399,7 @@ __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_reg(EngineArgs a, con
     kd = wave_sum(kd);
     const double H0 = U + 0.5 * kd;  // hmc.py:187
     double U_cur = U;
-    for (long long l = 0; l < L; l++) {  // trajectory.py:86-95: leap_linear<12> | P r | imm g' | leap_linear<3>
+    for (long long l = 0; l < Lt; l++) {  // trajectory.py:86-95: leap_linear<12> | P r | imm g' | leap_linear<3>
       double usum = 0.0;
 #pragma unroll
       for (int r = 0; r < R; r++) {
@@ -492,7 +494,7 @@ __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_reg(EngineArgs a, con
     a.U[c] = U;
     a.out.acceptance_probability[c] = pa;
     a.out.is_diverging[c] = is_div;
-    if (a.out.n_leapfrog) a.out.n_leapfrog[c] = L;
+    if (a.out.n_leapfrog) a.out.n_leapfrog[c] = Lt;  // (of the last transition; hmc_run fills a longer call's total)
     if (a.out.is_turning) a.out.is_turning[c] = acc;  // HMC: reused as the accept flag
   }
 #undef EI
@@ -525,16 +527,24 @@ inline hipError_t launch_nuts_block_reg(EngineArgs a, NutsSampleArgs m, double *
 
 template <int R>
 inline hipError_t launch_hmc_block_reg_r(const EngineArgs &a, const double *prec, long long L, long long nt,
-                                         double *samples, double *acc_hist, int *div_hist, hipStream_t st) {
+                                         double *samples, double *acc_hist, int *div_hist, hipStream_t st,
+                                         const HmcLengths *len) {
   const size_t dyn = blk_reg_lds_bytes(a.D);
   const dim3 grid((unsigned)((a.C + BLK_CHAINS - 1) / BLK_CHAINS)), block(BLK_THREADS);
 #define AEHMC_BLK(TDV)                                                                                       \
   do {                                                                                                       \
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_block_reg<R, TDV>),             \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);                \
+    if (e == hipSuccess && len)                                                                              \
+      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_block_reg<R, TDV, HmcLengths>),          \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);                         \
     if (e != hipSuccess) return e;                                                                           \
-    hipLaunchKernelGGL((k_hmc_block_reg<R, TDV>), grid, block, dyn, st, a, prec, L, nt, samples, acc_hist,   \
-                       div_hist);                                                                            \
+    if (len)                                                                                                 \
+      hipLaunchKernelGGL((k_hmc_block_reg<R, TDV, HmcLengths>), grid, block, dyn, st, a, prec, L, nt, samples, \
+                         acc_hist, div_hist, *len);                                                          \
+    else                                                                                                     \
+      hipLaunchKernelGGL((k_hmc_block_reg<R, TDV>), grid, block, dyn, st, a, prec, L, nt, samples, acc_hist, \
+                         div_hist);                                                                          \
   } while (0)
   if (a.tkind == AEHMC_T_DENSE_MVN) AEHMC_BLK(true);
   else AEHMC_BLK(false);
@@ -542,18 +552,20 @@ inline hipError_t launch_hmc_block_reg_r(const EngineArgs &a, const double *prec
   return hipGetLastError();
 }
 inline hipError_t launch_hmc_block_reg(EngineArgs a, const double *prec, long long L, long long nt, double *samples,
-                                       double *acc_hist, int *div_hist, double *bp, hipStream_t st) {
+                                       double *acc_hist, int *div_hist, double *bp, hipStream_t st,
+                                       const HmcLengths *len = nullptr) {
   BlkMats mats;
   if (hipError_t e = blk_pack_matrices(a, prec, bp, mats, st)) return e;
   a.imm = mats.imm; a.sqrt_mass = mats.sqrt_mass;
-  return a.D <= 128 ? launch_hmc_block_reg_r<2>(a, mats.prec, L, nt, samples, acc_hist, div_hist, st)
-                    : launch_hmc_block_reg_r<4>(a, mats.prec, L, nt, samples, acc_hist, div_hist, st);
+  return a.D <= 128 ? launch_hmc_block_reg_r<2>(a, mats.prec, L, nt, samples, acc_hist, div_hist, st, len)
+                    : launch_hmc_block_reg_r<4>(a, mats.prec, L, nt, samples, acc_hist, div_hist, st, len);
 }
 // The run-time compiled block kernel of a coordinate-wise user-defined target, for NUTS or for HMC: the register
 // kernel where it exists (`reg_allowed`: the "block_dense" option is not 2), the work-row kernel otherwise
-inline KernelLaunch block_launch(bool nuts, bool reg_allowed, long long D, long long C) {
+inline KernelLaunch block_launch(bool nuts, bool reg_allowed, long long D, long long C, bool lengths = false) {
   const bool reg = reg_allowed && block_reg_supported(D);
-  return {std::string(nuts ? "aehmc::k_nuts" : "aehmc::k_hmc") + (reg ? (D <= 128 ? "_block_reg<2, false>" : "_block_reg<4, false>") : "_block_dense<false>"),
+  return {std::string(nuts ? "aehmc::k_nuts" : "aehmc::k_hmc") + (reg ? (D <= 128 ? "_block_reg<2, false" : "_block_reg<4, false") : "_block_dense<false") +
+              lengths_arg(lengths),
           dim3((unsigned)((C + BLK_CHAINS - 1) / BLK_CHAINS)), dim3(BLK_THREADS), reg ? blk_reg_lds_bytes(D) : blk_lds_bytes(D)};
 }
 #endif  // __HIPCC_RTC__

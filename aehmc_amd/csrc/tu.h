@@ -10,6 +10,7 @@ namespace aehmc {
 struct EngineArgs;
 struct NutsSampleArgs;
 struct HmcFusedArgs;
+struct HmcLengths;
 struct GemmStreamK;
 struct PoolArgs;
 struct CheesArgs;
@@ -32,10 +33,11 @@ hipError_t nuts_resident_dense(const EngineArgs &a, const NutsSampleArgs &m, hip
 hipError_t nuts_block_roll(const EngineArgs &a, const NutsSampleArgs &m, double *bp, hipStream_t st);
 hipError_t nuts_block_reg(const EngineArgs &a, const NutsSampleArgs &m, double *bp, hipStream_t st);
 hipError_t nuts_block_dense(const EngineArgs &a, const NutsSampleArgs &m, double *bp, hipStream_t st);
+// (`len`: trajectory lengths from device memory, or nullptr -- the launch constant L)
 hipError_t hmc_block_reg(const EngineArgs &a, const double *prec, long long L, long long nt, double *samples,
-                         double *acc_hist, int *div_hist, double *bp, hipStream_t st);
+                         double *acc_hist, int *div_hist, double *bp, hipStream_t st, const HmcLengths *len);
 hipError_t hmc_block_dense(const EngineArgs &a, const double *prec, long long L, long long nt, double *samples,
-                           double *acc_hist, int *div_hist, double *bp, hipStream_t st);
+                           double *acc_hist, int *div_hist, double *bp, hipStream_t st, const HmcLengths *len);
 // nuts_pc_dense.cuh
 hipError_t nuts_pc_dense(const EngineArgs &a, const NutsSampleArgs &m, hipStream_t st);
 hipError_t hmc_pc_dense(const EngineArgs &a, long long L, long long nt, double *samples, double *acc_hist, int *div_hist,

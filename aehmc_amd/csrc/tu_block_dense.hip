@@ -9,8 +9,8 @@ hipError_t nuts_block_dense(const EngineArgs &a, const NutsSampleArgs &m, double
   return launch_nuts_block_dense(a, m, bp, st);
 }
 hipError_t hmc_block_dense(const EngineArgs &a, const double *prec, long long L, long long nt, double *samples,
-                           double *acc_hist, int *div_hist, double *bp, hipStream_t st) {
-  return launch_hmc_block_dense(a, prec, L, nt, samples, acc_hist, div_hist, bp, st);
+                           double *acc_hist, int *div_hist, double *bp, hipStream_t st, const HmcLengths *len) {
+  return launch_hmc_block_dense(a, prec, L, nt, samples, acc_hist, div_hist, bp, st, len);
 }
 }  // namespace tu
 }  // namespace aehmc

@@ -466,6 +466,22 @@ class Engine:
         out["samples"], out["acceptance_history"], out["divergence_history"] = samples, acc, div
         return out
 
+    def hmc_sample_lengths(self, rng, eps, lengths, thr, q, U, g, keep_samples=True, into=None):
+        """``hmc_sample`` with one trajectory length per transition (``lengths``: a list of ints >= 0): one engine
+        call -- one launch on the routes whose kernels read the lengths on the device; ``n_leapfrog`` is their sum."""
+        C, D = q.shape
+        n = len(lengths)
+        self.ensure_workspace(C, 1)
+        out, c = self._diag(C, D, False)
+        samples, acc, div = self._history_buffers(n, C, D, keep_samples, into)
+        self._step_call(
+            self.lib.aehmc_hmc_sample_lengths, "aehmc_hmc_sample_lengths",
+            self.ctx, C, rng.data_ptr(), float(eps), (ct.c_int64 * n)(*lengths), float(thr), n, q.data_ptr(),
+            U.data_ptr(), g.data_ptr(), ct.byref(c), samples.data_ptr() if keep_samples else None,
+            acc.data_ptr(), div.data_ptr(), self.stream)
+        out["samples"], out["acceptance_history"], out["divergence_history"] = samples, acc, div
+        return out
+
     def nuts_step(self, rng, eps, max_exp, thr, q, U, g):
         C, D = q.shape
         self.ensure_workspace(C, max_exp)
@@ -657,6 +673,18 @@ class Engine:
             position_before.data_ptr(), position_after.data_ptr(), momentum.data_ptr(),
             inverse_mass_diag.data_ptr() if inverse_mass_diag is not None else None, float(inverse_mass_scalar),
             accepted.data_ptr(), p_accept.data_ptr(), ct.byref(cstate), self.stream), "aehmc_chees_update")
+
+    def chees_warmup(self, rng, n, target, learning_rate, max_num_steps, inverse_mass_scalar, thr, q, U, g, st, cstate):
+        """The whole ChEES warm-up in one C-ABI call (``aehmc_chees_warmup``): ``n`` x (transition of the state's own
+        ``num_steps``, update).  The metric is bound by the caller; the state's ``step_size`` is bound here."""
+        C, D = q.shape
+        self.ensure_workspace(C, 1)
+        out, c = self._diag(C, D, False)
+        self._bind_step_sizes(st["step_size"])
+        self._step_call(self.lib.aehmc_chees_warmup, "aehmc_chees_warmup", self.ctx, C, rng.data_ptr(), int(n),
+                        float(target), float(learning_rate), int(max_num_steps), float(inverse_mass_scalar), float(thr),
+                        q.data_ptr(), U.data_ptr(), g.data_ptr(), ct.byref(c), ct.byref(cstate), self.stream)
+        return out
 
     def syrk_tn(self, X, S, centre=None, w=0.0, delta=None):
         """S[i, j] += sum_c (X[c, i] - centre[i]) (X[c, j] - centre[j]) + w delta[i] delta[j] for j <= i, in place

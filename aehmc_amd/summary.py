@@ -46,6 +46,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
+from ._common import trajectory_lengths
 from .engine import get_engine
 
 # aehmc_hip.h: AEHMC_SUMMARY_MAX_ROWS -- the autocovariance kernel keeps a coordinate's centred series (one segment)
@@ -684,14 +685,17 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
     median and intervals are there when the run ends (``sketch.quantiles`` / ``interval`` / ``resolved``).  What is
     returned does not change.
 
-    An HMC kernel needs ``num_integration_steps`` (as in ``window_adaptation.run``).  ``chunk=None``: the largest
+    An HMC kernel needs ``num_integration_steps`` (as in ``window_adaptation.run``): an int, or one length per
+    transition (a sequence of ``num_samples`` entries, as ``kernel.sample`` takes it -- the jittered lengths of
+    ``chees.trajectory_lengths`` for a run too large to store); every chunk gets its slice.  ``chunk=None``: the largest
     chunk whose buffer stays under ``CHUNK_BYTES`` (1 GiB), at least one draw."""
     is_hmc = getattr(kernel, "_hmc", None) is not None
     if is_hmc and num_integration_steps is None:
         raise ValueError("summary.run with an HMC kernel needs num_integration_steps")
     if not hasattr(kernel, "sample"):
         raise ValueError("summary.run needs a kernel of hmc.new_kernel / nuts.new_kernel (with .sample)")
-    extra = () if num_integration_steps is None else (int(num_integration_steps),)
+    lengths = None if num_integration_steps is None else trajectory_lengths(num_integration_steps, num_samples)
+    extra = () if num_integration_steps is None or lengths is not None else (int(num_integration_steps),)
     pos = state.position
     pshape = tuple(pos.shape) if hasattr(pos, "shape") else ()
     batched = bool(getattr(kernel, "batched", len(pshape) == 2))
@@ -714,6 +718,8 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
     done = 0
     while done < N:
         T = min(chunk, N - done)
+        if lengths is not None:
+            extra = (lengths[done:done + T],)
         samples, info, a, d = kernel.sample(state, step_size, inverse_mass_matrix, *extra, T, into=buf)
         acc.update(samples.reshape((T, C) + shape))
         if sketch is not None:

@@ -349,6 +349,19 @@ int aehmc_hmc_sample(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
                      const aehmc_diagnostics *out, double *samples, double *acceptance_history,
                      int32_t *divergence_history, void *stream);
 
+/* aehmc_hmc_sample with one trajectory length per transition (randomised-length HMC; chees.sample's jittered lengths):
+ * transition t runs lengths[t] leapfrogs.  `lengths` is a HOST array of num_samples entries, each >= 0 (a negative one is
+ * an error); the engine copies it into a device array of its own on `stream`.  On the routes whose kernels run a whole
+ * call in one launch with a coordinate-wise target or a shared dense metric (fused, workgroup per chain, small dense,
+ * block dense, regression; DESIGN.md section 3 lists every route) the call is still ONE launch: the kernels read
+ * transition t's length from that array, clamped to [0, max(lengths)].  On the other routes the call runs num_samples
+ * single transitions with L = lengths[t], as the caller's own loop of aehmc_hmc_step calls would, and records each.
+ * Either way the results are bit-equal to that loop.  out->n_leapfrog: the sum of the lengths. */
+int aehmc_hmc_sample_lengths(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, const int64_t *lengths,
+                             double divergence_threshold, int64_t num_samples, double *q, double *U, double *g,
+                             const aehmc_diagnostics *out, double *samples, double *acceptance_history,
+                             int32_t *divergence_history, void *stream);
+
 /* nuts.new_kernel(...)(state, step_size, imm) -- nuts.py:56-153, trajectory.py:154-374,428-714,
  * termination.py:19-235, proposals.py.  rng [C,4,4]: #1 momentum, #2 direction,
  * #3 uniform progressive, #4 biased progressive.  q,U,g updated in place. */
@@ -423,6 +436,22 @@ int aehmc_chees_update(aehmc_ctx *ctx, int64_t C, int64_t D, int32_t is_last, do
                        const double *position_after, const double *velocity_or_momentum,
                        const double *inverse_mass_diag, double inverse_mass_scalar, const int32_t *accepted,
                        const double *acceptance_probability, const aehmc_chees_state *state, void *stream);
+
+/* The whole ChEES warm-up in one call: num_steps x (copy q; one HMC transition of state->num_steps leapfrogs, at most
+ * max_num_steps; for a dense metric momentum . imm; aehmc_chees_update on the copy, q, the momentum, the accept flags
+ * out->is_turning and out->acceptance_probability, is_last at the last step) -- the kernels of the caller's own loop in
+ * its order, bit-equal to it.  Before the call: aehmc_chees_init on `state`, ONE shared metric bound (scalar: its value
+ * also in inverse_mass_scalar; diagonal and dense: taken from the binding), the step sizes bound to state->step_size
+ * (aehmc_set_step_sizes, n = C), and out->momentum, out->is_turning, out->acceptance_probability present.  On the routes
+ * that read trajectory lengths from device memory (see aehmc_hmc_sample_lengths) the transition takes its length from
+ * the state's own cell and nothing is read back: the call returns with all num_steps steps enqueued.  On the other
+ * routes the kernels take L from the host, and the call reads the one int64 back before every transition (a stream
+ * synchronisation per step, as the caller's loop has).  out->n_leapfrog afterwards: the length of the LAST transition
+ * (the kernels write what they ran).  The ctx keeps the two [C,D] work arrays. */
+int aehmc_chees_warmup(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_t num_steps, double target_acceptance_rate,
+                       double learning_rate, int64_t max_num_steps, double inverse_mass_scalar,
+                       double divergence_threshold, double *q, double *U, double *g, const aehmc_diagnostics *out,
+                       const aehmc_chees_state *state, void *stream);
 
 /* step_size.dual_averaging_adaptation(target, gamma, t0, kappa) -> update (step_size.py:9-100 over
  * algorithms.dual_averaging, algorithms.py:17-115) as a stand-alone building block around any kernel
