@@ -40,6 +40,10 @@ class CCheesState(ct.Structure):
                                            "da_step", "da_x", "da_x_avg", "da_g_avg", "da_mu", "step_size", "sums")]
 
 
+class CMeadsState(ct.Structure):
+    _fields_ = [(n, ct.c_void_p) for n in ("params", "scale", "count", "skipped", "sums")]
+
+
 class CDiagnostics(ct.Structure):
     _fields_ = [("momentum", ct.c_void_p), ("acceptance_probability", ct.c_void_p),
                 ("num_doublings", ct.c_void_p), ("is_turning", ct.c_void_p),
@@ -101,6 +105,11 @@ SYMBOLS = {
                                       _P, _P, _P, _P]),
     "aehmc_chees_warmup": (_I, [_P, _I64, _P, _I64, _D, _D, _I64, _D, _D, _P, _P, _P, ct.POINTER(CDiagnostics),
                                 ct.POINTER(CCheesState), _P]),
+    "aehmc_ghmc_sample": (_I, [_P, _I64, _P, _P, _D, _D, _D, _P, _I64, _D, _I64, _P, _P, _P, _P, ct.c_int32, _P, ct.c_int32,
+                               ct.POINTER(CDiagnostics), _P, _P, _P, _P]),
+    "aehmc_meads_update": (_I, [_P, _I64, _I64, _P, _P, _D, _D, ct.POINTER(CMeadsState), _P]),
+    "aehmc_meads_warmup": (_I, [_P, _I64, _P, _I64, _D, _D, _D, _P, _P, _P, _P, ct.c_int32, _P, ct.c_int32,
+                                ct.POINTER(CDiagnostics), ct.POINTER(CMeadsState), _P]),
     "aehmc_nuts_step": (_I, [_P, _I64, _P, _D, _I64, _D, _P, _P, _P, ct.POINTER(CDiagnostics), _P]),
     "aehmc_nuts_sample": (_I, [_P, _I64, _P, _D, _I64, _D, _I64, _P, _P, _P, ct.POINTER(CDiagnostics),
                                _P, _P, _P, _P, _P]),

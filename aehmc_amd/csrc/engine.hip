@@ -31,6 +31,8 @@
 #include "nuts_pc_dense.cuh"
 #include "pooled_adapt.cuh"
 #include "chees.cuh"
+#include "ghmc_fused.cuh"
+#include "meads.cuh"
 
 using namespace aehmc;
 
@@ -49,7 +51,7 @@ constexpr size_t PROF_POOL = 8192;
 // one instantiation per program, named by the launch.  A new run-time compiled route registers here, and builds the
 // name of its instantiation beside the plan in its family header (KernelLaunch, engine.cuh).
 enum RtcProg { RTC_BASE, RTC_GLM, RTC_JBASE, RTC_JTWG, RTC_JWG, RTC_NUTS, RTC_JNUTS, RTC_WIDE, RTC_JWIDE, RTC_BLOCK, RTC_HMC,
-               RTC_JHMCF, RTC_JHMC, RTC_GLMK };
+               RTC_JHMCF, RTC_JHMC, RTC_GLMK, RTC_GHMC, RTC_JGHMC };
 struct RtcRow {
   const char *mode;                  // "AEHMC_CUSTOM_TARGET" (engine.cuh: target_elem calls aehmc_custom_elem), "AEHMC_JOINT_TARGET"
                                      // (leap_small_dense calls aehmc_logp through dual.cuh), or none: the GLM kernels
@@ -78,8 +80,10 @@ static const RtcRow RTC_TABLE[] = {
     /* RTC_JHMCF */ {"AEHMC_JOINT_TARGET", {"hmc_fused.cuh"}, {}},
     /* RTC_JHMC */ {"AEHMC_JOINT_TARGET", {}, {}},
     /* RTC_GLMK */ {nullptr, {"glm_rows.cuh"}, {}},  // (one instantiation of the one-launch GLM kernels)
+    /* RTC_GHMC */ {"AEHMC_CUSTOM_TARGET", {"ghmc_fused.cuh"}, {}},
+    /* RTC_JGHMC */ {"AEHMC_JOINT_TARGET", {"ghmc_fused.cuh"}, {}},
 };
-static_assert(sizeof(RTC_TABLE) / sizeof(RTC_TABLE[0]) == RTC_GLMK + 1, "one row per RtcProg, in its order");
+static_assert(sizeof(RTC_TABLE) / sizeof(RTC_TABLE[0]) == RTC_JGHMC + 1, "one row per RtcProg, in its order");
 static const std::string &RTC_JWG_NUTS = RTC_TABLE[RTC_JWG].names[0], &RTC_JWG_HMC = RTC_TABLE[RTC_JWG].names[1];  // (nuts_run / hmc_run spell no template arguments)
 // a program and the wavefronts per SIMD its workgroup-per-chain kernels are compiled for (AEHMC_WG_MIN_WAVES 3 / 4:
 // RTC_GLMK and RTC_JWG, see wg_program; 0: not defined)
@@ -178,6 +182,10 @@ struct aehmc_ctx {
   size_t chees_work_bytes = 0;
   double *chees_loop = nullptr;  // aehmc_chees_warmup: the positions before a transition [C,D], momentum . imm [C,D] (kept, grown)
   size_t chees_loop_bytes = 0;
+  double *meads_work = nullptr;  // MEADS update: column sums, m, sd, row norms, Frobenius rows, the two [D,D] products (kept, grown)
+  size_t meads_work_bytes = 0;
+  double *ghmc_cell = nullptr;  // aehmc_ghmc_sample with host parameters: eps, alpha, delta [3]
+  size_t ghmc_cell_bytes = 0;
   double *hmc_lens = nullptr;  // aehmc_hmc_sample_lengths: the call's trajectory lengths, int64 [num_samples] (kept, grown)
   size_t hmc_lens_bytes = 0;
   double *syrk_work = nullptr;  // symmetric rank-C update of a mid-size D: the parts of the chain range (kept, grown)
@@ -347,6 +355,8 @@ extern "C" int aehmc_destroy(aehmc_ctx *ctx) {
   if (ctx->pool_work) (void)hipFree(ctx->pool_work);
   if (ctx->chees_work) (void)hipFree(ctx->chees_work);
   if (ctx->chees_loop) (void)hipFree(ctx->chees_loop);
+  if (ctx->meads_work) (void)hipFree(ctx->meads_work);
+  if (ctx->ghmc_cell) (void)hipFree(ctx->ghmc_cell);
   if (ctx->hmc_lens) (void)hipFree(ctx->hmc_lens);
   if (ctx->syrk_work) (void)hipFree(ctx->syrk_work);
   if (ctx->glm_XT) (void)hipFree(ctx->glm_XT);
@@ -2922,6 +2932,120 @@ extern "C" int aehmc_chees_warmup(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int6
                                     nd == 2 ? 1.0 : (nd == 1 ? 0.0 : inverse_mass_scalar), out->is_turning,
                                     out->acceptance_probability, state, stream))
       return rc;
+  }
+  return 0;
+}
+
+// ---- generalised HMC (ghmc_fused.cuh) and its MEADS warm-up (meads.cuh) ----
+// T transitions in one launch; `params`: eps, alpha, delta on the device
+static int ghmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, const double *params, const double *scale, int64_t scale_n,
+                    double divergence_threshold, int64_t T, double *q, double *U, double *g, double *momentum,
+                    int32_t has_momentum, double *slice, int32_t has_slice, const aehmc_diagnostics *out, double *samples,
+                    double *acc_hist, int32_t *div_hist, hipStream_t st) {
+  if (T < 1) FAIL("ghmc: number of transitions must be >= 1");
+  if (C < 1 || !rng || !params || !scale || !q || !U || !g || !momentum || !slice) FAIL("ghmc: bad arguments");
+  if (!out->acceptance_probability || !out->is_diverging) FAIL("diagnostics arrays missing");
+  if (!ctx->has_tgt) FAIL("set_target must be called first");
+  const int64_t D = ctx->tgt.D;
+  const int tkind = ctx->tgt.kind;
+  if (D > GHMC_MAX_D)
+    FAIL("ghmc: D = " + std::to_string(D) + " is above the " + std::to_string(GHMC_MAX_D) +
+         " coordinates a wavefront holds in registers (k_ghmc_fused); there is no other route");
+  if (scale_n != 1 && scale_n != D)
+    FAIL("ghmc: the scale is ONE scalar or [D] vector shared by all chains (scale_n = 1 or D), got " + std::to_string(scale_n) +
+         " entries; dense and per-chain preconditioners are not supported");
+  GhmcArgs f{};
+  f.C = C; f.D = D; f.T = T; f.thr = divergence_threshold; f.params = params; f.scale = scale; f.scale_n = (int)scale_n;
+  f.rng = rng; f.q = q; f.U = U; f.g = g; f.v = momentum; f.slice = slice; f.has_v = has_momentum; f.has_slice = has_slice;
+  f.out = *out; f.samples = samples; f.acc_hist = acc_hist; f.div_hist = div_hist;
+  if (ghmc_target_is_elem(tkind)) {
+    f.tkind = tkind; f.mu = ctx->tgt.mu; f.sigma = ctx->tgt.sigma; f.log_sigma = ctx->log_sigma;
+    return profiled(ctx, st, [&](bool) -> int { HIPCHK(tu::ghmc_fused(f, st)); return 0; });
+  }
+  if (tkind == AEHMC_T_CUSTOM) {  // user-defined coordinate-wise target: the kernel compiled against the user's function
+    f.tkind = AEHMC_T_CUSTOM; f.cparams = ctx->bound.d_cparams;
+    return profiled(ctx, st, [&](bool) -> int { return rtc_launch(ctx, RTC_GHMC, ghmc_fused_launch(D, AEHMC_T_CUSTOM, C), st, f); });
+  }
+  if (tkind == AEHMC_T_JOINT) {
+    if (!ctx->bound.has_grad)
+      FAIL("ghmc: a joint density needs its reverse-mode program (AEHMC_JOINT_GRAD: a traced Python function, "
+           "targets.from_callable(..., reverse=True) below 65 coordinates); forward mode is not supported");
+    f.tkind = AEHMC_T_JOINT; f.cparams = ctx->bound.d_cparams;
+    return profiled(ctx, st, [&](bool) -> int { return rtc_launch(ctx, RTC_JGHMC, ghmc_fused_launch(D, AEHMC_T_JOINT, C), st, f); });
+  }
+  FAIL("ghmc: the bound target (kind " + std::to_string(tkind) + ") is not supported: generalised HMC runs the "
+       "coordinate-wise targets, targets.Custom and joint densities with a reverse-mode program (no dense MVN, regression "
+       "or GLM target)");
+}
+
+extern "C" int aehmc_ghmc_sample(aehmc_ctx *ctx, int64_t C, uint64_t *rng, const double *params, double step_size,
+                                 double alpha, double delta, const double *scale, int64_t scale_n,
+                                 double divergence_threshold, int64_t num_samples, double *q, double *U, double *g,
+                                 double *momentum, int32_t has_momentum, double *slice, int32_t has_slice,
+                                 const aehmc_diagnostics *out, double *samples, double *acceptance_history,
+                                 int32_t *divergence_history, void *stream) {
+  if (!ctx || !out) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (!params) {  // host numbers: into the ctx's own cell on the caller's stream, then the one code path
+    if (!(step_size > 0)) FAIL("ghmc: step_size must be positive");
+    if (!(alpha > 0 && alpha <= 1)) FAIL("ghmc: alpha must lie in (0, 1]");
+    if (!(delta >= 0)) FAIL("ghmc: delta must be >= 0");
+    if (int rc = grow(ctx, &ctx->ghmc_cell, &ctx->ghmc_cell_bytes, 3 * sizeof(double))) return rc;
+    HIPCHK(tu::meads_set3(ctx->ghmc_cell, step_size, alpha, delta, st));
+    params = ctx->ghmc_cell;
+  }
+  return ghmc_run(ctx, C, rng, params, scale, scale_n, divergence_threshold, num_samples, q, U, g, momentum, has_momentum,
+                  slice, has_slice, out, samples, acceptance_history, divergence_history, st);
+}
+
+extern "C" int aehmc_meads_update(aehmc_ctx *ctx, int64_t C, int64_t D, const double *position,
+                                  const double *potential_energy_grad, double step_size_multiplier, double damping_slowdown,
+                                  const aehmc_meads_state *state, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (!state || D <= 0 || !position || !potential_energy_grad) FAIL("meads: bad arguments");
+  if (C < 2) FAIL("meads: the cross-chain statistics need at least 2 chains");
+  if (!state->params || !state->scale || !state->count || !state->skipped) FAIL("meads: state arrays missing");
+  if (!(step_size_multiplier > 0)) FAIL("meads: step_size_multiplier must be positive");
+  MeadsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.C = C; a.D = D; a.multiplier = step_size_multiplier; a.slowdown = damping_slowdown;
+  a.Q = position; a.G = potential_energy_grad; a.s = *state;
+  pool_parts(C, D, a.P, a.rows_per);
+  if (int rc = grow(ctx, &ctx->meads_work, &ctx->meads_work_bytes, meads_work_doubles(C, D) * sizeof(double))) return rc;
+  a.part = ctx->meads_work;
+  a.m = a.part + (size_t)a.P * D;
+  a.sd = a.m + D;  // (adjacent: k_meads_scalars copies both at once)
+  a.fro = a.sd + D;
+  a.nz = a.fro + 2 * D;
+  a.ng = a.nz + C;
+  a.Sz = a.ng + C;
+  a.Sg = a.Sz + (size_t)D * D;
+  HIPCHK(hipMemsetAsync(a.Sz, 0, (size_t)2 * D * D * sizeof(double), st));
+  HIPCHK(tu::meads_means(a, st));
+  if (int rc = syrk(ctx, C, D, position, D, a.m, 0.0, nullptr, nullptr, a.Sz, D, st)) return rc;
+  if (int rc = syrk(ctx, C, D, potential_energy_grad, D, nullptr, 0.0, nullptr, nullptr, a.Sg, D, st)) return rc;
+  HIPCHK(tu::meads_finish(a, st));
+  return 0;
+}
+
+extern "C" int aehmc_meads_warmup(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_t num_steps, double step_size_multiplier,
+                                  double damping_slowdown, double divergence_threshold, double *q, double *U, double *g,
+                                  double *momentum, int32_t has_momentum, double *slice, int32_t has_slice,
+                                  const aehmc_diagnostics *out, const aehmc_meads_state *state, void *stream) {
+  if (!ctx || !out || !state) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx->has_tgt) FAIL("set_target must be called first");
+  if (num_steps < 0) FAIL("meads: num_steps must be >= 0");
+  const int64_t D = ctx->tgt.D;
+  if (int rc = aehmc_meads_update(ctx, C, D, q, g, step_size_multiplier, damping_slowdown, state, stream)) return rc;
+  for (int64_t i = 0; i < num_steps; i++) {
+    if (int rc = ghmc_run(ctx, C, rng, state->params, state->scale, D, divergence_threshold, 1, q, U, g, momentum,
+                          has_momentum || i > 0, slice, has_slice || i > 0, out, nullptr, nullptr, nullptr, (hipStream_t)stream))
+      return rc;
+    if (int rc = aehmc_meads_update(ctx, C, D, q, g, step_size_multiplier, damping_slowdown, state, stream)) return rc;
   }
   return 0;
 }

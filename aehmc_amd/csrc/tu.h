@@ -14,6 +14,8 @@ struct HmcLengths;
 struct GemmStreamK;
 struct PoolArgs;
 struct CheesArgs;
+struct GhmcArgs;
+struct MeadsArgs;
 namespace tu {
 // gemm_f64.cuh
 hipError_t gemm_nt_f64(int64_t M, int64_t N, int64_t K, const double *A, int64_t lda, const double *B, int64_t ldb,
@@ -94,5 +96,11 @@ hipError_t pool_scalars(const PoolArgs &a, hipStream_t st);
 // chees.cuh
 hipError_t chees_init(const CheesArgs &a, double initial_step_size, double initial_trajectory_length, hipStream_t st);
 hipError_t chees_update(const CheesArgs &a, hipStream_t st);
+// ghmc_fused.cuh
+hipError_t ghmc_fused(const GhmcArgs &a, hipStream_t st);
+// meads.cuh (the two rank-C products of an update run between meads_means and meads_finish)
+hipError_t meads_set3(double *cell, double x, double y, double z, hipStream_t st);
+hipError_t meads_means(const MeadsArgs &a, hipStream_t st);
+hipError_t meads_finish(const MeadsArgs &a, hipStream_t st);
 }  // namespace tu
 }  // namespace aehmc

@@ -686,6 +686,68 @@ class Engine:
                         q.data_ptr(), U.data_ptr(), g.data_ptr(), ct.byref(c), ct.byref(cstate), self.stream)
         return out
 
+    # ------------------------------------------------------------------ generalised HMC, MEADS warm-up
+    def _ghmc_carry(self, C, D, momentum, slice_):
+        """The whitened momentum [C, D] and the slice [C] a call works on in place: copies of what was handed in, or
+        fresh arrays the kernel fills; and the two has_ flags."""
+        f64 = torch.float64
+        v = (_dev_f64(momentum, self.device).reshape(C, D).clone() if momentum is not None
+             else torch.empty(C, D, dtype=f64, device=self.device))
+        u = (_dev_f64(slice_, self.device).reshape(C).clone() if slice_ is not None
+             else torch.empty(C, dtype=f64, device=self.device))
+        return v, u, int(momentum is not None), int(slice_ is not None)
+
+    def ghmc_sample(self, rng, params, scale, thr, n, q, U, g, momentum=None, slice_=None, keep_samples=True, history=True):
+        """``n`` generalised-HMC transitions in one launch (``aehmc_ghmc_sample``).  ``params``: a device tensor [3]
+        (eps, alpha, delta) or a tuple of three host floats; ``scale``: a device tensor [1] or [D]."""
+        C, D = q.shape
+        out, c = self._diag(C, D, False)
+        v, u, has_v, has_u = self._ghmc_carry(C, D, momentum, slice_)
+        samples, acc, div = self._history_buffers(n, C, D, keep_samples, None) if history else (None, None, None)
+        on_device = isinstance(params, torch.Tensor)
+        eps, alpha, delta = (0.0, 0.0, 0.0) if on_device else (float(x) for x in params)
+        self._check(self.lib.aehmc_ghmc_sample(
+            self.ctx, C, rng.data_ptr(), params.data_ptr() if on_device else None, eps, alpha, delta, scale.data_ptr(),
+            scale.numel(), float(thr), int(n), q.data_ptr(), U.data_ptr(), g.data_ptr(), v.data_ptr(), has_v,
+            u.data_ptr(), has_u, ct.byref(c), samples.data_ptr() if samples is not None else None,
+            acc.data_ptr() if history else None, div.data_ptr() if history else None, self.stream), "aehmc_ghmc_sample")
+        out["momentum"], out["slice"] = v, u
+        out["samples"], out["acceptance_history"], out["divergence_history"] = samples, acc, div
+        return out
+
+    def meads_alloc(self, D, initial_step_size, with_sums=False):
+        """The state of a MEADS adaptation before any update: params (eps0, 1, 0.5), scale 1 [D], count = skipped = 0;
+        ``with_sums``: also ``sums`` [8 + 2 D], which an update fills with its intermediate sums."""
+        dev, f64 = self.device, torch.float64
+        st = dict(params=torch.tensor([float(initial_step_size), 1.0, 0.5], dtype=f64, device=dev),
+                  scale=torch.ones(D, dtype=f64, device=dev),
+                  count=torch.zeros(1, dtype=torch.int64, device=dev), skipped=torch.zeros(1, dtype=torch.int64, device=dev))
+        if with_sums:
+            st["sums"] = torch.zeros(8 + 2 * D, dtype=f64, device=dev)
+        return st
+
+    @staticmethod
+    def meads_cstate(st):
+        return _lib.CMeadsState(**{k: v.data_ptr() for k, v in st.items()})
+
+    def meads_update(self, C, D, position, gradient, multiplier, slowdown, st):
+        self._check(self.lib.aehmc_meads_update(self.ctx, C, D, position.data_ptr(), gradient.data_ptr(), float(multiplier),
+                                                float(slowdown), ct.byref(self.meads_cstate(st)), self.stream),
+                    "aehmc_meads_update")
+
+    def meads_warmup(self, rng, n, multiplier, slowdown, thr, q, U, g, st, momentum=None, slice_=None):
+        """The whole MEADS warm-up in one C-ABI call (``aehmc_meads_warmup``): an update, then ``n`` x (transition on
+        the state's own parameters, update)."""
+        C, D = q.shape
+        out, c = self._diag(C, D, False)
+        v, u, has_v, has_u = self._ghmc_carry(C, D, momentum, slice_)
+        self._check(self.lib.aehmc_meads_warmup(
+            self.ctx, C, rng.data_ptr(), int(n), float(multiplier), float(slowdown), float(thr), q.data_ptr(), U.data_ptr(),
+            g.data_ptr(), v.data_ptr(), has_v, u.data_ptr(), has_u, ct.byref(c), ct.byref(self.meads_cstate(st)),
+            self.stream), "aehmc_meads_warmup")
+        out["momentum"], out["slice"] = v, u
+        return out
+
     def syrk_tn(self, X, S, centre=None, w=0.0, delta=None):
         """S[i, j] += sum_c (X[c, i] - centre[i]) (X[c, j] - centre[j]) + w delta[i] delta[j] for j <= i, in place
         (aehmc_syrk_tn; elements above the diagonal are unspecified afterwards)."""

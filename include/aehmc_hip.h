@@ -135,6 +135,18 @@ typedef struct {
                                             runs the same either way) */
 } aehmc_chees_state;
 
+/* state of the MEADS warm-up (meads.run): the four parameters of generalised HMC, adapted from all chains.  Before the
+ * first update the caller fills params = (initial step size, 1, 0.5), scale = 1, count = skipped = 0. */
+typedef struct {
+  double *params;                        /* [3]: step size eps, momentum refreshment alpha, slice drift delta */
+  double *scale;                         /* [D]: the preconditioner s, in the role of sqrt(inverse_mass_matrix) */
+  int64_t *count;                        /* [1]: updates done so far */
+  int64_t *skipped;                      /* [1]: of them, those the guard refused (parameters left as they were) */
+  double *sums;                          /* NULL, or [8 + 2 D]: a copy of what the last update summed -- sum |z_c|^4,
+                                            sum |z_c|^2, sum |gs_c|^4, sum |gs_c|^2, the two scaled Frobenius sums (Z, Gs),
+                                            lam(Z), lam(Gs), then the column means m [D] and sd [D] (diagnostics) */
+} aehmc_meads_state;
+
 /* per-transition outputs == trajectory.py:379-384 Diagnostics (+ n_leapfrog) */
 typedef struct {
   double *momentum;               /* [C,D] Diagnostics.state.momentum */
@@ -452,6 +464,56 @@ int aehmc_chees_warmup(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_t num_ste
                        double learning_rate, int64_t max_num_steps, double inverse_mass_scalar,
                        double divergence_threshold, double *q, double *U, double *g, const aehmc_diagnostics *out,
                        const aehmc_chees_state *state, void *stream);
+
+/* Generalised HMC with a persistent WHITENED momentum v ~ N(0, I) and a non-reversible slice variable u in (-1, 1)
+ * (Hoffman & Sountsov 2022): num_samples >= 1 transitions of every chain in one launch, each exactly
+ * one leapfrog.  `scale` (device, scale_n = 1 or D, shared by all chains) plays the role of sqrt(inverse_mass_matrix); the
+ * bound metric is not read.  One transition:
+ *   z = D standard normals of generator site #1;  v = sqrt(1 - alpha) v + sqrt(alpha) z  (has_momentum = 0: the first
+ *   transition of the call sets v = z);  u = fmod((u + 1) + delta, 2) - 1  (has_slice = 0: first u = 2 r - 1 with r one
+ *   double of site #2, the only draw that site makes);  H0 = U + v.v / 2;
+ *   vh = v - (eps / 2)(s g), q' = q + eps (s vh), g' = dU/dq(q'), v' = vh - (eps / 2)(s g');
+ *   d = H0 - (U' + v'.v' / 2), NaN -> -inf;  is_diverging = |d| > divergence_threshold;  acceptance_probability =
+ *   min(1, exp d);  accept iff d > -inf and log|u| <= d -- no random number;
+ *   accept: (q, U, g, v) = (q', U', g', v'), u = u exp(-d);  reject: v = -v (the refreshed one), u unchanged.
+ * Parameters: `params` (device, [3]: eps, alpha, delta -- the cell of an aehmc_meads_state, say), or NULL and the three
+ * host numbers, which the engine places in a cell of its own on the caller's stream: one code path either way.
+ * In place: q, U, g, `momentum` [C,D] and `slice` [C] (read only with their has_ flag, always written).  `out` as HMC
+ * fills it: acceptance_probability, is_diverging, n_leapfrog = num_samples, is_turning reused as the accept flag;
+ * out->momentum is not written.  Optional per-transition outputs as for HMC sampling.
+ * Bound target: the coordinate-wise ones of the library, a user-defined coordinate-wise one, or a joint density that
+ * brings its reverse-mode program, D <= 1024.  Anything else -- a regression or GLM target, a joint density without that
+ * program, D > 1024, scale_n not 1 or D -- is an error that names the limit; there is no other route. */
+int aehmc_ghmc_sample(aehmc_ctx *ctx, int64_t C, uint64_t *rng, const double *params, double step_size, double alpha,
+                      double delta, const double *scale, int64_t scale_n, double divergence_threshold,
+                      int64_t num_samples, double *q, double *U, double *g, double *momentum, int32_t has_momentum,
+                      double *slice, int32_t has_slice, const aehmc_diagnostics *out, double *samples,
+                      double *acceptance_history, int32_t *divergence_history, void *stream);
+
+/* One MEADS update (Hoffman & Sountsov 2022, the all-chains variant) from positions and potential gradients [C,D], C >= 2:
+ *   m = column means, var_i = (1 / C) sum_c (Q_ci - m_i)^2, sd = sqrt(var), Z = (Q - m) / sd, Gs = G sd;
+ *   lam(X) for X [n,d], S = X X^T:  [(sum_ab S_ab^2 - sum_a S_aa^2) / (n (n - 1))] / [sum_a S_aa / n];
+ *   eps = min(1, step_size_multiplier / sqrt(lam(Gs)));
+ *   gamma = max(1 / sqrt(lam(Z)), 1 / ((count + 1)^damping_slowdown eps));
+ *   alpha = 1 - exp(-2 eps gamma);  delta = alpha / 2;  scale = sd;  count += 1.
+ * If eps, alpha, delta or some sd_i is not finite, eps <= 0, or some sd_i = 0, the parameters and the scale stay as they
+ * were and skipped += 1 (count still advances).  The C x C matrix is never formed: sum_ab S_ab^2 is the squared
+ * Frobenius norm of X^T X, taken from the two symmetric rank-C products (the centred one of Q scaled by 1 / (sd_i sd_j),
+ * the uncentred one of G by sd_i sd_j).  Sums run in an order fixed by (C, D), no atomics: two calls are bit-equal.  The
+ * ctx keeps the scratch (two [D,D] matrices among it). */
+int aehmc_meads_update(aehmc_ctx *ctx, int64_t C, int64_t D, const double *position, const double *potential_energy_grad,
+                       double step_size_multiplier, double damping_slowdown, const aehmc_meads_state *state,
+                       void *stream);
+
+/* The whole MEADS warm-up in one call: an update on the starting state, then num_steps x (one generalised-HMC transition
+ * that reads state->params and state->scale where they lie; an update on the new q, g).  Nothing is read back: the call
+ * returns with every step enqueued.  `momentum`, `slice`, their flags and `out` as for the sampling call above; after the
+ * first transition both are carried.  The same kernels in the same order as a caller's own loop over the two calls above
+ * (which hands the parameters back as host numbers: the same bits). */
+int aehmc_meads_warmup(aehmc_ctx *ctx, int64_t C, uint64_t *rng, int64_t num_steps, double step_size_multiplier,
+                       double damping_slowdown, double divergence_threshold, double *q, double *U, double *g,
+                       double *momentum, int32_t has_momentum, double *slice, int32_t has_slice,
+                       const aehmc_diagnostics *out, const aehmc_meads_state *state, void *stream);
 
 /* step_size.dual_averaging_adaptation(target, gamma, t0, kappa) -> update (step_size.py:9-100 over
  * algorithms.dual_averaging, algorithms.py:17-115) as a stand-alone building block around any kernel
