@@ -94,6 +94,7 @@ SYMBOLS = {
     "aehmc_summary_hdi": (_I, [_P, _I64, _I64, _P, _D, _P, _P, _P, _P, _I64, _P]),
     "aehmc_summary_quantile_mcse": (_I, [_P, _I64, _I64, _I64, _P, ct.POINTER(_D), _P, _P, _P, _P, _I64, _P]),
     "aehmc_beta_quantile": (_I, [_P, _I64, _P, _P, _P, _P, _P]),
+    "aehmc_summary_psis": (_I, [_P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "aehmc_set_option": (_I, [_P, ct.c_char_p, _I64]),
     "aehmc_workspace_bytes": (_I64, [_P, _I64, _I64]),
     "aehmc_set_workspace": (_I, [_P, _P, _I64]),

@@ -1417,6 +1417,23 @@ extern "C" int aehmc_summary_quantile_mcse(aehmc_ctx *ctx, int64_t R, int64_t D,
   HIPCHK(tu::quantile_mcse(samples, R, D, (int)Q, probs, ess, out, (long long *)ranks, work, T, (hipStream_t)stream));
   return 0;
 }
+// Pareto-smoothed importance sampling (psis.cuh): one more consumer of the sorted columns.  Without log_ratios the
+// ratios are -log_values, the leave-one-out case: no negated copy of the log-likelihood has to exist.
+extern "C" int aehmc_summary_psis(aehmc_ctx *ctx, int64_t R, int64_t D, const double *log_ratios, const double *reff,
+                                  const double *log_values, double *log_weights, double *pareto_k, int64_t *tail_len,
+                                  double *log_mean, void *work, int64_t work_bytes, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (R < 1 || D < 1 || (!log_ratios && !log_values) || !pareto_k || !work) FAIL("summary_psis: bad arguments");
+  if ((log_values != nullptr) != (log_mean != nullptr))
+    FAIL("summary_psis: log_values and log_mean go together, one of them is null");
+  int64_t T = 0;
+  if (int rc = posterior_shape(ctx, "summary_psis", R, D, work, work_bytes, &T)) return rc;
+  const bool neg = !log_ratios;
+  HIPCHK(tu::psis(neg ? log_values : log_ratios, neg, reff, log_values, log_weights, pareto_k, (long long *)tail_len,
+                  log_mean, R, D, work, T, (hipStream_t)stream));
+  return 0;
+}
 extern "C" int aehmc_beta_quantile(aehmc_ctx *ctx, int64_t n, const double *p, const double *a, const double *b,
                                    double *out, void *stream) {
   if (!ctx) return -2;

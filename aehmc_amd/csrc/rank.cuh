@@ -108,7 +108,8 @@ struct RankTileArgs {
 
 // (1) Workgroup (x: 1 << tw_log2 coordinates of the tile, y: chunk of draws).  Lane (c, rl) reads the draws rl,
 // rl + 256 / tw, ... of a block of 256 rows at coordinate c (the tw lanes of a draw read one contiguous row segment);
-// then lane t writes key t of every column of the block.
+// then lane t writes key t of every column of the block.  NEG: the keys are those of -x (psis.cuh's leave-one-out ratios).
+template <bool NEG>
 __global__ __launch_bounds__(RANK_THREADS) void k_rank_keys(RankTileArgs a, unsigned long long *__restrict__ keys,
                                                             unsigned *__restrict__ nan) {
   __shared__ unsigned long long s_key[RANK_TILE * RANK_STRIDE];
@@ -127,7 +128,8 @@ __global__ __launch_bounds__(RANK_THREADS) void k_rank_keys(RankTileArgs a, unsi
       for (int j = 0; j < tw; ++j) {
         const int row = j * rpi + rl;
         if (rb + row < r1) {
-          const double v = rank_value(a.x[(rb + row) * a.D + d], a.centre, d);
+          const double xv = a.x[(rb + row) * a.D + d];
+          const double v = rank_value(NEG ? -xv : xv, a.centre, d);
           n_nan += v != v;  // (a NaN that the fold makes counts too)
           s_key[c * RANK_STRIDE + row] = rank_key(v);
         }
@@ -353,13 +355,18 @@ inline RankTileGeom rank_tile_geom(const double *x, const double *centre, long l
 }
 
 // Steps (1) and (2) for the tile of `g`: afterwards w.keys[RANK_PASSES & 1] (the first buffer) holds the tile's sorted
-// key columns [Tc][R] and w.nan its NaN counts; w.counts is free again.  Shared by launch_rank and posterior.cuh.
-inline hipError_t launch_rank_sort(const RankTileGeom &g, const RankWork &w, hipStream_t st) {
+// key columns [Tc][R] and w.nan its NaN counts; w.counts and the second key buffer are free again.  Shared by
+// launch_rank, posterior.cuh and psis.cuh (neg: the columns of -x).
+inline hipError_t launch_rank_sort(const RankTileGeom &g, const RankWork &w, hipStream_t st, bool neg = false) {
   const long long R = g.a.R, Tc = g.a.T;
   const long long chunk = rank_chunk(R), chunks = rank_chunks(R);
   if (hipError_t e = hipMemsetAsync(w.nan, 0, (size_t)Tc * sizeof(unsigned), st); e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_rank_keys, dim3((unsigned)g.subs, (unsigned)g.rc), dim3(RANK_THREADS), 0, st, g.a, w.keys[0],
-                     w.nan);
+  if (neg)
+    hipLaunchKernelGGL(k_rank_keys<true>, dim3((unsigned)g.subs, (unsigned)g.rc), dim3(RANK_THREADS), 0, st, g.a,
+                       w.keys[0], w.nan);
+  else
+    hipLaunchKernelGGL(k_rank_keys<false>, dim3((unsigned)g.subs, (unsigned)g.rc), dim3(RANK_THREADS), 0, st, g.a,
+                       w.keys[0], w.nan);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   const dim3 grid((unsigned)chunks, (unsigned)Tc);
   for (int p = 0; p < RANK_PASSES; ++p) {

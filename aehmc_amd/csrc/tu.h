@@ -85,6 +85,10 @@ hipError_t hdi(const double *x, long long R, long long D, long long m, double *l
 hipError_t quantile_mcse(const double *x, long long R, long long D, int Q, const double *probs, const double *ess,
                          double *out, long long *ranks, void *work, long long T, hipStream_t st);
 hipError_t beta_quantile(long long n, const double *p, const double *a, const double *b, double *out, hipStream_t st);
+// psis.cuh (the same scratch and tiles again; neg: the ratios are -x; reff [D], v [R][D], log_weights [R][D], tail_len
+// [D] may be null, log_mean [D] goes with v)
+hipError_t psis(const double *x, bool neg, const double *reff, const double *v, double *log_weights, double *pareto_k,
+                long long *tail_len, double *log_mean, long long R, long long D, void *work, long long T, hipStream_t st);
 // syrk_f64.cuh, pooled_adapt.cuh
 hipError_t syrk_tn(long long C, long long D, const double *X, long long ldx, const double *centre, double w,
                    const double *w_dev, const double *delta, double *S, long long lds, double *partial, hipStream_t st);

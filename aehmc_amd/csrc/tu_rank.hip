@@ -2,6 +2,7 @@
 #include "tu.h"
 #include "rank.cuh"
 #include "posterior.cuh"
+#include "psis.cuh"
 
 namespace aehmc {
 namespace tu {
@@ -25,6 +26,11 @@ hipError_t quantile_mcse(const double *x, long long R, long long D, int Q, const
 }
 hipError_t beta_quantile(long long n, const double *p, const double *a, const double *b, double *out, hipStream_t st) {
   return launch_beta_quantile(n, p, a, b, out, st);
+}
+hipError_t psis(const double *x, bool neg, const double *reff, const double *v, double *log_weights, double *pareto_k,
+                long long *tail_len, double *log_mean, long long R, long long D, void *work, long long T,
+                hipStream_t st) {
+  return launch_psis(x, neg, reff, v, log_weights, pareto_k, tail_len, log_mean, R, D, work, T, st);
 }
 }  // namespace tu
 }  // namespace aehmc

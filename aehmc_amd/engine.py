@@ -937,6 +937,25 @@ class Engine:
                     "aehmc_beta_quantile")
         return out
 
+    def summary_psis(self, log_ratios, reff=None, log_values=None, weights=True, _work_bytes=None):
+        """(log_weights [R, D] or None, pareto_k [D], tail_len [D] int64, log_mean [D] or None): Pareto-smoothed
+        importance sampling of every column of log_ratios [R, D]; reff [D] (device) or None for 1.  With log_values
+        [R, D], log_mean = log sum exp(log_weights + log_values); ``log_ratios=None`` then means -log_values (PSIS-LOO
+        of a log-likelihood, without a negated copy).  ``weights=False``: the log-weights are not stored.
+        ``_work_bytes`` as in ``summary_rank``."""
+        R, D = (log_ratios if log_ratios is not None else log_values).shape
+        work = self._rank_work(R, D, _work_bytes)
+        lw = torch.empty(R, D, dtype=torch.float64, device=self.device) if weights else None
+        k = torch.empty(D, dtype=torch.float64, device=self.device)
+        tail = torch.empty(D, dtype=torch.int64, device=self.device)
+        mean = torch.empty(D, dtype=torch.float64, device=self.device) if log_values is not None else None
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._check(self.lib.aehmc_summary_psis(self.ctx, R, D, ptr(log_ratios), ptr(reff), ptr(log_values), ptr(lw),
+                                                k.data_ptr(), tail.data_ptr(), ptr(mean), work.data_ptr(), work.numel(),
+                                                self.stream),
+                    "aehmc_summary_psis")
+        return lw, k, tail, mean
+
     def profile_enable(self, on=True):
         self._check(self.lib.aehmc_profile_enable(self.ctx, int(on)), "aehmc_profile_enable")
 

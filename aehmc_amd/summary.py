@@ -33,6 +33,11 @@ of consecutive order statistics), ``mcse_quantile`` / ``mcse_median`` (two order
 that a beta quantile of the coordinate's own ESS gives; csrc/posterior.cuh), ``mcse_sd``, and ``table`` for the
 ``az.summary`` columns at once.
 
+And for comparing models, from the pointwise log-likelihood of the stored draws (one observation is one "coordinate"):
+``psislw`` (Pareto-smoothed importance weights and the Pareto shape k per observation, csrc/psis.cuh, again on the
+sorted columns), ``loo`` (PSIS-LOO: the weights are used where they are formed and never stored), ``relative_eff`` and
+``waic``.
+
 Without the stored draws: ``QuantileSketch``, a fixed-grid histogram per coordinate that ``run`` can feed next to its
 ``Accumulator`` (csrc/sketch.cuh) -- ``quantiles``, ``median`` and ``interval`` of the pooled draws to within one bin
 width, with ``resolved`` to say where that bound holds.
@@ -506,6 +511,151 @@ def table(samples, prob: float = 0.9, *, batched: bool = True, max_lag: Optional
     return PosteriorTable(mean=s.mean, sd=s.sd, hdi_lower=lower, hdi_upper=upper, mcse_mean=s.mcse,
                           mcse_sd=mcse_sd(samples, batched=batched, max_lag=max_lag), ess_bulk=r.ess_bulk,
                           ess_tail=r.ess_tail, rhat=r.rhat, num_draws=s.num_draws, num_chains=s.num_chains)
+
+
+# loo / waic / relative_eff: what torch forms on the way (exp of a block of columns, its log-sum-exp) stays under this
+# many bytes, at least one column
+MODEL_BLOCK_BYTES = 128 << 20
+
+
+def _column_blocks(S, D):
+    step = max(1, MODEL_BLOCK_BYTES // (8 * S))
+    return [(d0, min(d0 + step, D)) for d0 in range(0, D, step)]
+
+
+def _reff_columns(reff, shape, D, eng):
+    """``reff`` -- a float, or a device tensor shaped like one chain's position -- as a device tensor [D], or None
+    for 1."""
+    if isinstance(reff, torch.Tensor):
+        if tuple(reff.shape) != shape:
+            raise ValueError(f"reff must be a float or a tensor of shape {shape}, got shape {tuple(reff.shape)}")
+        if reff.dtype != torch.float64:
+            raise ValueError(f"reff must be float64, got {reff.dtype}")
+        if reff.device != eng.device:
+            raise ValueError(f"reff must be on {eng.device}, it is on {reff.device}")
+        return reff.reshape(D).contiguous()
+    if not isinstance(reff, (int, float)) or isinstance(reff, bool):
+        raise ValueError(f"reff must be a float or a tensor, got {reff!r}")
+    reff = float(reff)
+    if not (math.isfinite(reff) and reff > 0.0):
+        raise ValueError(f"reff must be finite and positive, got {reff}")
+    return None if reff == 1.0 else torch.full((D,), reff, dtype=torch.float64, device=eng.device)
+
+
+def psislw(log_ratios, reff=1.0, *, batched: bool = True):
+    """``(log_weights, pareto_k)``: Pareto-smoothed importance sampling (Vehtari, Simpson, Gelman, Yao & Gabry; ArviZ's
+    ``psislw``) of stored log importance ratios, per coordinate and with the chains pooled.  ``log_ratios`` as
+    ``summarize`` takes its draws -- one observation, or whatever else the ratios belong to, is one trailing
+    "coordinate"; ``log_weights`` is shaped like it and sums to 1 after ``exp`` over the pooled draws of a coordinate,
+    ``pareto_k`` like one chain's position.  ``reff``: the relative efficiency of the draws, a float or a device tensor
+    shaped like one chain's position; the tail holds ``ceil(min(S / 5, 3 sqrt(S / reff)))`` of the S pooled draws at
+    most.  The largest draws above the cutoff (strictly: ties at the cutoff stay out) are replaced by the expected
+    order statistics of the generalised Pareto distribution fitted to them (Zhang & Stephens' estimator with ArviZ's
+    priors), tied draws sharing the mean weight of their places, so that the weights do not depend on the order of the
+    draws.  ``pareto_k`` is +inf where fewer than 5 draws lie above the cutoff (nothing is smoothed) and NaN where the
+    fit fails; a coordinate with a NaN, a +inf, nothing but -inf, or a ``reff`` that is not finite and positive is NaN
+    throughout.  csrc/psis.cuh, on the sorted columns of csrc/rank.cuh."""
+    x, shape = _pooled(log_ratios, batched)
+    eng = get_engine()
+    _on_device(eng, x)
+    lw, k, _, _ = eng.summary_psis(x, _reff_columns(reff, shape, x.shape[1], eng))
+    return lw.reshape(log_ratios.shape), k.reshape(shape)
+
+
+def relative_eff(log_lik, *, batched: bool = True, max_lag: Optional[int] = None):
+    """The relative efficiency that ``loo`` hands to the smoothing, shaped like one chain's position: per observation
+    ``summarize(exp(log_lik - max)).ess / S`` over the S pooled draws (R ``loo``'s ``relative_eff`` of the
+    likelihood), and 1 where that is not finite and positive.  ``max_lag`` and the length limit as in ``summarize``."""
+    x, shape = _pooled(log_lik, batched)
+    _check_rank_run(log_lik, batched, max_lag)
+    _on_device(get_engine(), x)
+    S, D = x.shape
+    pool = tuple(range(2 if batched else 1))
+    out = []
+    for d0, d1 in _column_blocks(S, D) if shape else [(0, 1)]:
+        blk = log_lik[..., d0:d1] if shape else log_lik
+        e = torch.exp(blk - blk.amax(dim=pool, keepdim=True)).contiguous()
+        out.append(summarize(e, batched=batched, max_lag=max_lag).ess.reshape(-1) / S)
+    r = torch.cat(out)
+    return torch.where(torch.isfinite(r) & (r > 0), r, torch.ones_like(r)).reshape(shape)
+
+
+def _pooled_lppd(x):
+    """log mean_s exp(x) per column of x [S, D], a block of columns at a time."""
+    S, D = x.shape
+    return torch.cat([torch.logsumexp(x[:, d0:d1], dim=0) for d0, d1 in _column_blocks(S, D)]) - math.log(S)
+
+
+class LooResult(NamedTuple):
+    """PSIS-LOO of a model.  ``elpd``, ``se`` and ``p`` are floats: the expected log pointwise predictive density, its
+    standard error ``sqrt(n_data var(elpd_i))`` and the effective number of parameters ``sum(lppd_i - elpd_i)``.
+    ``elpd_i``, ``pareto_k``, ``lppd_i`` and ``tail_len`` (int64: the draws that were smoothed, -1 for an observation
+    that is NaN) are device tensors shaped like one chain's position.  ``warning``: some ``pareto_k`` lies above
+    ``k_threshold = min(1 - 1 / log10(S), 0.7)``, the estimate of that observation is unreliable."""
+    elpd: float
+    se: float
+    p: float
+    elpd_i: torch.Tensor
+    pareto_k: torch.Tensor
+    lppd_i: torch.Tensor
+    tail_len: torch.Tensor
+    k_threshold: float
+    warning: bool
+    n_samples: int
+    n_data: int
+
+
+def loo(log_lik, reff=None, *, batched: bool = True, max_lag: Optional[int] = None) -> LooResult:
+    """Leave-one-out cross-validation by Pareto-smoothed importance sampling (``az.loo``, R's ``loo``) from the
+    pointwise log-likelihood ``log_lik``, laid out as ``summarize`` takes its draws: one observation is one trailing
+    "coordinate", [N, C, n_data] with ``batched``.  Per observation the log ratios are ``-log_lik``, smoothed as in
+    ``psislw``, and ``elpd_i = log sum_s w_s exp(log_lik_s)``; the weights are never stored and no negated copy of
+    ``log_lik`` is made: besides the sort's scratch the call allocates a few blocks of ``MODEL_BLOCK_BYTES`` at most
+    (torch's temporaries for ``relative_eff`` and ``lppd_i``), nothing the size of ``log_lik``.
+    ``reff``: as in ``psislw``, or None for ``relative_eff(log_lik)`` (``max_lag`` goes there, and ``summarize``'s
+    length limit applies; pass ``reff=1.0`` for independent draws).  ``lppd_i = log mean_s exp(log_lik_s)``."""
+    x, shape = _pooled(log_lik, batched)
+    eng = get_engine()
+    _on_device(eng, x)
+    S, D = x.shape
+    if reff is None:
+        r = relative_eff(log_lik, batched=batched, max_lag=max_lag).reshape(D)
+    else:
+        r = _reff_columns(reff, shape, D, eng)
+    _, k, tail, elpd_i = eng.summary_psis(None, r, x, weights=False)
+    lppd_i = _pooled_lppd(x)
+    threshold = min(1.0 - 1.0 / math.log10(S), 0.7) if S > 1 else -math.inf
+    return LooResult(elpd=elpd_i.sum().item(), se=math.sqrt(D * torch.var(elpd_i, unbiased=False).item()),
+                     p=(lppd_i - elpd_i).sum().item(), elpd_i=elpd_i.reshape(shape), pareto_k=k.reshape(shape),
+                     lppd_i=lppd_i.reshape(shape), tail_len=tail.reshape(shape), k_threshold=threshold,
+                     warning=bool((k > threshold).any().item()), n_samples=S, n_data=D)
+
+
+class WaicResult(NamedTuple):
+    """The widely applicable information criterion on the elpd scale: ``elpd_i = lppd_i - p_i``, ``elpd`` and ``p``
+    their sums (floats), ``se = sqrt(n_data var(elpd_i))``; the per-observation tensors are shaped like one chain's
+    position."""
+    elpd: float
+    se: float
+    p: float
+    elpd_i: torch.Tensor
+    p_i: torch.Tensor
+    lppd_i: torch.Tensor
+
+
+def waic(log_lik, *, batched: bool = True) -> WaicResult:
+    """WAIC from the pointwise log-likelihood ``log_lik`` as ``loo`` takes it: ``lppd_i = log mean_s exp(log_lik_s)``
+    and ``p_i`` the sample variance (divisor S - 1) of ``log_lik`` over the S pooled draws.  torch reductions, a block
+    of ``MODEL_BLOCK_BYTES`` at a time."""
+    x, shape = _pooled(log_lik, batched)
+    _on_device(get_engine(), x)
+    S, D = x.shape
+    lppd_i = _pooled_lppd(x)
+    p_i = torch.cat([torch.var(x[:, d0:d1], dim=0, unbiased=True) for d0, d1 in _column_blocks(S, D)])
+    elpd_i = lppd_i - p_i
+    return WaicResult(elpd=elpd_i.sum().item(), se=math.sqrt(D * torch.var(elpd_i, unbiased=False).item()),
+                      p=p_i.sum().item(), elpd_i=elpd_i.reshape(shape), p_i=p_i.reshape(shape),
+                      lppd_i=lppd_i.reshape(shape))
 
 
 # aehmc_hip.h: AEHMC_SUMMARY_SKETCH_MIN_BINS / _MAX_BINS -- the grids of QuantileSketch (a power of two in between)

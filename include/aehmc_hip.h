@@ -713,6 +713,43 @@ int aehmc_summary_quantile_mcse(aehmc_ctx *ctx, int64_t R, int64_t D, int64_t Q,
 int aehmc_beta_quantile(aehmc_ctx *ctx, int64_t n, const double *p, const double *a, const double *b, double *out,
                         void *stream);
 
+/* ---- Pareto-smoothed importance sampling: PSIS weights, Pareto k, PSIS-LOO (aehmc_amd/summary.py) ----
+ * Vehtari, Simpson, Gelman, Yao & Gabry, "Pareto smoothed importance sampling", with Zhang & Stephens' (2009) fit of
+ * the generalised Pareto distribution and the prior constants of ArviZ's _gpdfit: what az.loo / R's loo compute, per
+ * column of log_ratios [R, D] (R pooled draws, D columns: one observation is one coordinate), in fp64.  One more
+ * consumer of the sorted key columns of `rank` above (csrc/psis.cuh): `work` is that of aehmc_summary_rank_work(R, D),
+ * 256-byte aligned, anything from one coordinate's need upward; 1 <= R < 2^31.  No floating-point atomics: every output
+ * is the same bits on every run and for every size of `work`.  Under a permutation of the rows pareto_k and tail_len
+ * keep their bits and every row keeps the bits of its log-weight (they come from the sorted column); log_mean is summed
+ * along the rows and is equal to rounding only.
+ *
+ * Per column x, with reff = reff[d] (device, [D]) or 1 if reff is NULL:
+ *  - mx = max(x).  A NaN in the column, an mx that is not finite (a +inf, or all -inf) or a reff that is not finite
+ *    and > 0: every output of the column is NaN and tail_len = -1.  -inf entries are ordinary: weight 0.  y = x - mx.
+ *  - M = ceil(min(R / 5, 3 sqrt(R / reff))) held to [0, R - 1]; with s the sorted y, cut = max(s[R - M - 1],
+ *    log(DBL_MIN)); the tail is the draws with y > cut, strictly, n = tail_len <= M of them.
+ *  - n <= 4: pareto_k = +inf and nothing is smoothed.  Otherwise t_j = exp(s_j) - exp(cut) over the tail, ascending,
+ *    m = 30 + floor(sqrt n), b_i = (1 - sqrt(m / (i - 0.5))) / (3 t_q) + 1 / t_n for i = 1 ... m with
+ *    t_q = t[floor(n / 4 + 0.5) - 1], k_i = mean_j log1p(-b_i t_j), L_i = n (log(-b_i / k_i) - k_i - 1),
+ *    w_i = 1 / sum_l exp(L_l - L_i), weights below 10 DBL_EPSILON dropped and the rest renormalised, b = sum w_i b_i,
+ *    k' = mean_j log1p(-b t_j), sigma = -k' / b, pareto_k = (n k' + 5) / (n + 10).  If that is not finite or sigma is
+ *    not > 0 the fit has failed: pareto_k = NaN and nothing is smoothed.
+ *  - smoothing: place j = 0 ... n - 1 of the tail gets min(log(sigma gpinv((j + 0.5) / n) + exp(cut)), 0),
+ *    gpinv(p) = expm1(-k log1p(-p)) / k, or -log1p(-p) when |k| < DBL_EPSILON.  Tied tail draws that occupy the places
+ *    lo ... hi - 1 all receive the log of the mean of the exp of those places' values, summed in ascending place: the
+ *    weights are a function of the multiset of draws, and without ties they are ArviZ's psislw.
+ *  - log_weights [R, D] (or NULL: not stored) = the result minus the log of the sum of its exp: sum exp = 1.
+ *  - with log_values [R, D]: log_mean [D] = log sum_s exp(log_weights + log_values), whether or not log_weights is
+ *    stored; log_mean is required if and only if log_values is given.
+ * pareto_k [D] is required, tail_len [D] (int64) may be NULL.
+ *
+ * PSIS-LOO is log_ratios = -log_lik, log_values = log_lik, and log_mean is then elpd_loo_i.  For that case log_ratios
+ * may be NULL: the ratios are then -log_values, no negated copy is read, and with log_weights NULL the call touches no
+ * memory of size R D besides its input. */
+int aehmc_summary_psis(aehmc_ctx *ctx, int64_t R, int64_t D, const double *log_ratios, const double *reff,
+                       const double *log_values, double *log_weights, double *pareto_k, int64_t *tail_len,
+                       double *log_mean, void *work, int64_t work_bytes, void *stream);
+
 /* window_adaptation.run (window_adaptation.py:17-116) for a NUTS kernel: num_steps x (one transition
  * with the current per-chain parameters, then aehmc_adapt_update), enqueued in one call.  `stage` /
  * `is_window_end` [num_steps] are HOST arrays from build_schedule.  Before the call the caller binds
