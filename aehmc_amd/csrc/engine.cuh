@@ -131,6 +131,41 @@ struct NutsSampleArgs {
   int roll;
 };
 
+// Per-transition trajectory lengths from device memory (jittered HMC, the ChEES warm-up): transition t of a launch runs
+// min(max(Ls[t * ls], 0), Lmax) leapfrogs; ls = 1: one length per transition, ls = 0: one cell for the whole launch
+// (the warm-up's num_steps).  The clamp bounds the trajectory loop whatever the memory holds.  Every HMC kernel that
+// has the mode carries the three fields in its argument struct (HmcSampleArgs::len; HmcFusedArgs: Ls, ls, Lmax) and a
+// trailing `bool LS` template parameter: only the LS instantiation reads them (hmc_length below), the other runs the
+// launch constant L and is the kernel it always was.
+struct HmcLengths {
+  const long long *Ls;
+  long long ls, Lmax;
+};
+// what an HMC launch that runs T transitions is told about the call
+struct HmcSampleArgs {
+  long long L, T;      // leapfrogs per transition (the LS instantiations: see `len`), transitions
+  double *samples;     // optional per-transition outputs, as in NutsSampleArgs: [T][C][D]
+  double *acc_hist;    // [T][C]
+  int *div_hist;       // [T][C]
+  const double *prec;  // small dense / block kernels: the dense target's precision [D, D]
+  double *imm_ws;      // per-chain dense metrics: [C, D, D] workspace for the transposed matrices
+  HmcLengths len;      // read only by the LS instantiations
+};
+// The per-transition record of a launch that runs several transitions, transition t of chain c.  record_hist: called by the
+// one lane that holds the chain's scalars; record_row: by the chain's wavefront, its position row as it stands in a.q.
+__device__ __forceinline__ void record_hist(const EngineArgs &a, double *acc_hist, int *div_hist, long long t, long long c,
+                                            double acc, int div) {
+  if (acc_hist) acc_hist[(size_t)t * a.C + c] = acc;
+  if (div_hist) div_hist[(size_t)t * a.C + c] = div;
+}
+__device__ __forceinline__ void record_row(const EngineArgs &a, double *samples, long long t, long long c, int lane) {
+  if (samples) {
+    double *dst = samples + ((size_t)t * a.C + c) * a.D;
+    const size_t row = (size_t)c * a.D;
+    for (long long i = lane; i < a.D; i += 64) dst[i] = a.q[row + i];
+  }
+}
+
 // two-entry arrays are picked with a select, never indexed dynamically (a dynamic index
 // into the kernel-argument struct or ChainCtl sends them to scratch memory)
 template <class T>
@@ -1134,17 +1169,9 @@ AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_hmc_begin_diag(EngineArg
   rng_store(a, c, lane, rng, 0, 0);
   hmc_init_chain<false>(a, c, lane);
 }
-// Per-transition trajectory lengths from device memory (jittered HMC, the ChEES warm-up): transition t of a launch runs
-// min(max(Ls[t * ls], 0), Lmax) leapfrogs; ls = 1: one length per transition, ls = 0: one cell for the whole launch
-// (the warm-up's num_steps).  The clamp bounds the trajectory loop whatever the memory holds.  The EngineArgs kernels take
-// it as a trailing parameter pack `Len... len`, empty (the launch constant L, the kernel as it always was) or one
-// HmcLengths; HmcFusedArgs carries the three fields.  The value is the same for every lane; readfirstlane on both halves
-// says so to the compiler, which then keeps the trip count in scalar registers and the trajectory loop unmasked.
-struct HmcLengths {
-  const long long *Ls;
-  long long ls, Lmax;
-};
-__device__ __forceinline__ long long hmc_length(long long L, long long) { return L; }
+// Transition t's trajectory length of an LS instantiation (HmcLengths, above).  The value is the same for every lane;
+// readfirstlane on both halves says so to the compiler, which then keeps the trip count in scalar registers and the
+// trajectory loop unmasked.
 __device__ __forceinline__ long long hmc_length(long long L, long long t, const HmcLengths &n) {
   if (!n.Ls) return L;
   const long long v = n.Ls[t * n.ls];
@@ -1211,10 +1238,8 @@ __global__ __launch_bounds__(256) void k_hmc_end(EngineArgs a, long long L) {
 }
 // The HMC transition of a small dense problem in one launch (see above: same matrices in LDS, same
 // in-wavefront products, literal dense mode); the chain's scalars stay in registers between the stages.
-template <bool MD, bool TD, bool PC = false, class... Len>
-__global__ __launch_bounds__(FUSED_DENSE_BLOCK) AEHMC_USER_DENSITY_512 void k_hmc_fused_dense(EngineArgs a, const double *prec, double *imm_ws, long long L,
-                                                                         long long nt, double *samples, double *acc_hist,
-                                                                         int *div_hist, Len... len) {
+template <bool MD, bool TD, bool PC = false, bool LS = false>
+__global__ __launch_bounds__(FUSED_DENSE_BLOCK) AEHMC_USER_DENSITY_512 void k_hmc_fused_dense(EngineArgs a, HmcSampleArgs h) {
   extern __shared__ __attribute__((aligned(16))) double fd_lds[];
   const int D = (int)a.D, DD = D * D;
   constexpr bool MLDS = MD && !PC;
@@ -1225,16 +1250,16 @@ __global__ __launch_bounds__(FUSED_DENSE_BLOCK) AEHMC_USER_DENSITY_512 void k_hm
       immT[k * D + i] = a.imm[e];
       smT[k * D + i] = a.sqrt_mass[e];
     }
-    if (TD) PT[k * D + i] = prec[e];
+    if (TD) PT[k * D + i] = h.prec[e];
   }
   __syncthreads();
   AEHMC_CHAIN_OF_WAVE();
   const size_t row = (size_t)c * a.D;
-  const double *const immW = PC ? imm_ws + (size_t)c * DD : immT;  // PC: this chain's transposed copy (global)
-  if (PC) wave_transpose_to(a.imm + (size_t)c * DD, imm_ws + (size_t)c * DD, D, lane);
-  // nt consecutive transitions of the chain in this launch (kernel.sample(nt)); per-transition records optional
-  for (long long tt = 0; tt < nt; tt++) {
-  const long long Lt = hmc_length(L, tt, len...);
+  const double *const immW = PC ? h.imm_ws + (size_t)c * DD : immT;  // PC: this chain's transposed copy (global)
+  if (PC) wave_transpose_to(a.imm + (size_t)c * DD, h.imm_ws + (size_t)c * DD, D, lane);
+  // h.T consecutive transitions of the chain in this launch (kernel.sample(T)); per-transition records optional
+  for (long long tt = 0; tt < h.T; tt++) {
+  const long long Lt = LS ? hmc_length(h.L, tt, h.len) : h.L;
   {
     Pcg64 g1 = pcg_load(a.rng + (size_t)c * a.nsites * 4);
     draw_momentum<MD>(a, c, lane, g1);
@@ -1262,10 +1287,10 @@ __global__ __launch_bounds__(FUSED_DENSE_BLOCK) AEHMC_USER_DENSITY_512 void k_hm
     if (on) a.cur_v[el] = v;
   }
   hmc_end_chain<MD>(a, c, lane, ct, Lt);
-  if (samples && on) samples[((size_t)tt * a.C + c) * a.D + lane] = a.q[el];  // (what this lane holds now)
+  if (h.samples && on) h.samples[((size_t)tt * a.C + c) * a.D + lane] = a.q[el];  // (what this lane holds now)
   if (lane == 0) {
-    if (acc_hist) acc_hist[(size_t)tt * a.C + c] = a.out.acceptance_probability[c];
-    if (div_hist) div_hist[(size_t)tt * a.C + c] = a.out.is_diverging[c];
+    if (h.acc_hist) h.acc_hist[(size_t)tt * a.C + c] = a.out.acceptance_probability[c];
+    if (h.div_hist) h.div_hist[(size_t)tt * a.C + c] = a.out.is_diverging[c];
   }
   __threadfence_block();  // the next transition's lanes read the energy lane 0 has just written
   }
@@ -1280,8 +1305,8 @@ struct KernelLaunch {
   size_t dyn;
 };
 inline const char *bool_arg(bool b) { return b ? "true" : "false"; }
-// the trailing template argument of an instantiation that takes its trajectory lengths from device memory (HmcLengths)
-inline const char *lengths_arg(bool lengths) { return lengths ? ", aehmc::HmcLengths>" : ">"; }
+// the trailing template argument of an instantiation that takes its trajectory lengths from device memory (LS)
+inline const char *lengths_arg(bool lengths) { return lengths ? ", true>" : ">"; }
 inline KernelLaunch hmc_fused_dense_launch(bool md, bool td, bool pc, long long D, long long C, bool lengths = false) {
   return {std::string("aehmc::k_hmc_fused_dense<") + bool_arg(md) + ", " + bool_arg(td) + ", " + bool_arg(pc) + lengths_arg(lengths),
           dim3((unsigned)((C + FUSED_DENSE_BLOCK / 64 - 1) / (FUSED_DENSE_BLOCK / 64))), dim3(FUSED_DENSE_BLOCK),
@@ -1402,21 +1427,14 @@ __global__ __launch_bounds__(256) void k_nuts_joint_rows(EngineArgs a, NutsSampl
     U_state = pick2(ct.U_slot, ct.prop_slot);
     nleap_sum += ct.nleap;
     __threadfence_block();
-    if (m.samples) {
-      double *dst = m.samples + ((size_t)t_idx * a.C + c) * a.D;
-      for (long long i = lane; i < a.D; i += 64) dst[i] = a.q[row + i];
-    }
-    if (lane == 0) {
-      if (m.acc_hist) m.acc_hist[(size_t)t_idx * a.C + c] = ct.acc_prob;
-      if (m.div_hist) m.div_hist[(size_t)t_idx * a.C + c] = ct.out_div;
-    }
+    record_row(a, m.samples, t_idx, c, lane);
+    if (lane == 0) record_hist(a, m.acc_hist, m.div_hist, t_idx, c, ct.acc_prob, ct.out_div);
   }
   rng_store(a, c, lane, rng, 0, 3);
   if (lane == 0 && m.nleap_total) m.nleap_total[c] = nleap_sum;
 }
-// HMC: nt transitions x L leapfrogs in one launch (hmc_run's lock-step loop for one chain per wavefront)
-__global__ __launch_bounds__(256) void k_hmc_joint_rows(EngineArgs a, long long L, long long nt, double *samples,
-                                                        double *acc_hist, int *div_hist) {
+// HMC: h.T transitions x h.L leapfrogs in one launch (hmc_run's lock-step loop for one chain per wavefront)
+__global__ __launch_bounds__(256) void k_hmc_joint_rows(EngineArgs a, HmcSampleArgs h) {
   extern __shared__ __attribute__((aligned(16))) double joint_rows[];
   AEHMC_CHAIN_OF_WAVE();
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1424,26 +1442,20 @@ __global__ __launch_bounds__(256) void k_hmc_joint_rows(EngineArgs a, long long 
   const size_t row = (size_t)c * a.D;
   Pcg64 g1 = pcg_load(a.rng + (size_t)c * a.nsites * 4), g2 = pcg_load(a.rng + ((size_t)c * a.nsites + 1) * 4);
   double U_state = a.U[c];
-  for (long long tt = 0; tt < nt; tt++) {
+  for (long long tt = 0; tt < h.T; tt++) {
     draw_momentum<false>(a, c, lane, g1);
     ChainCtl ct = hmc_init_chain<false>(a, c, lane, &U_state);
-    for (long long l = 0; l < L; l++) {  // trajectory.py:86-95
+    for (long long l = 0; l < h.L; l++) {  // trajectory.py:86-95
       double U_new = 0.0;
       leap_stages<true, true, false, false>(a, c, lane, 1, U_new);
       ct.U_cur = joint_rows_eval(a, a.cur_q + row, a.cur_g + row, qr, lane);
       leap_stages<false, false, true, false>(a, c, lane, 1, U_new);
     }
     __threadfence_block();
-    const HmcEnd e = hmc_end_chain_rng<false>(a, c, lane, ct, L, g2);
+    const HmcEnd e = hmc_end_chain_rng<false>(a, c, lane, ct, h.L, g2);
     if (e.acc) U_state = ct.U_cur;
-    if (samples) {
-      double *dst = samples + ((size_t)tt * a.C + c) * a.D;
-      for (long long i = lane; i < a.D; i += 64) dst[i] = a.q[row + i];
-    }
-    if (lane == 0) {
-      if (acc_hist) acc_hist[(size_t)tt * a.C + c] = e.pa;
-      if (div_hist) div_hist[(size_t)tt * a.C + c] = e.is_div;
-    }
+    record_row(a, h.samples, tt, c, lane);
+    if (lane == 0) record_hist(a, h.acc_hist, h.div_hist, tt, c, e.pa, e.is_div);
   }
   if (lane == 0) {
     pcg_store(a.rng + (size_t)c * a.nsites * 4, g1);
@@ -1535,14 +1547,8 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_w
       U_state = pick2(ct.U_slot, ct.prop_slot);
       nleap_sum += ct.nleap;
       __threadfence_block();
-      if (m.samples) {
-        double *dst = m.samples + ((size_t)t_idx * a.C + c) * a.D;
-        for (long long i = lane; i < a.D; i += 64) dst[i] = a.q[row + i];
-      }
-      if (lane == 0) {
-        if (m.acc_hist) m.acc_hist[(size_t)t_idx * a.C + c] = ct.acc_prob;
-        if (m.div_hist) m.div_hist[(size_t)t_idx * a.C + c] = ct.out_div;
-      }
+      record_row(a, m.samples, t_idx, c, lane);
+      if (lane == 0) record_hist(a, m.acc_hist, m.div_hist, t_idx, c, ct.acc_prob, ct.out_div);
     }
   }
   if (leader) {
@@ -1551,8 +1557,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_w
   }
 }
 template <int W>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_waves(W)))) void k_hmc_joint_wg(EngineArgs a, long long L, long long nt, double *samples,
-                                                         double *acc_hist, int *div_hist) {
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_waves(W)))) void k_hmc_joint_wg(EngineArgs a, HmcSampleArgs h) {
   extern __shared__ __attribute__((aligned(16))) double joint_rows[];
   const int tid = threadIdx.x, lane = tid & 63;
   const bool leader = __builtin_amdgcn_readfirstlane(tid >> 6) == 0;
@@ -1561,13 +1566,13 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_w
   const size_t row = (size_t)c * a.D;
   Pcg64 g1 = pcg_load(a.rng + (size_t)c * a.nsites * 4), g2 = pcg_load(a.rng + ((size_t)c * a.nsites + 1) * 4);
   double U_state = a.U[c];
-  for (long long tt = 0; tt < nt; tt++) {
+  for (long long tt = 0; tt < h.T; tt++) {
     ChainCtl ct = {};
     if (leader) {
       draw_momentum<false>(a, c, lane, g1);
       ct = hmc_init_chain<false>(a, c, lane, &U_state);
     }
-    for (long long l = 0; l < L; l++) {  // trajectory.py:86-95
+    for (long long l = 0; l < h.L; l++) {  // trajectory.py:86-95
       double U_new = 0.0;
       if (leader) {
         leap_stages<true, true, false, false>(a, c, lane, 1, U_new);
@@ -1583,16 +1588,10 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_w
     }
     if (leader) {
       __threadfence_block();
-      const HmcEnd e = hmc_end_chain_rng<false>(a, c, lane, ct, L, g2);
+      const HmcEnd e = hmc_end_chain_rng<false>(a, c, lane, ct, h.L, g2);
       if (e.acc) U_state = ct.U_cur;
-      if (samples) {
-        double *dst = samples + ((size_t)tt * a.C + c) * a.D;
-        for (long long i = lane; i < a.D; i += 64) dst[i] = a.q[row + i];
-      }
-      if (lane == 0) {
-        if (acc_hist) acc_hist[(size_t)tt * a.C + c] = e.pa;
-        if (div_hist) div_hist[(size_t)tt * a.C + c] = e.is_div;
-      }
+      record_row(a, h.samples, tt, c, lane);
+      if (lane == 0) record_hist(a, h.acc_hist, h.div_hist, tt, c, e.pa, e.is_div);
     }
   }
   if (leader && lane == 0) {

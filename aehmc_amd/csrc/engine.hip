@@ -2600,6 +2600,15 @@ static HmcFusedArgs hmc_fused_args(const aehmc_ctx *ctx, int64_t C, uint64_t *rn
   f.rng = rng; f.q = q; f.U = U; f.g = g; f.out = *out;
   return f;
 }
+// one library instantiation of k_hmc_fused_dense (LS: the trajectory lengths come from h.len)
+template <bool MD, bool TD, bool PC, bool LS>
+static hipError_t launch_hmc_fused_dense(const KernelLaunch &k, const EngineArgs &a, const HmcSampleArgs &h, hipStream_t st) {
+  if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_fused_dense<MD, TD, PC, LS>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.dyn))
+    return e;
+  hipLaunchKernelGGL((k_hmc_fused_dense<MD, TD, PC, LS>), k.grid, k.block, k.dyn, st, a, h);
+  return hipGetLastError();
+}
 // The trajectory lengths of a call that does not run one L throughout: `dev`[t * stride] on the device (stride 1: one per
 // transition; 0: one cell for the whole call, the ChEES warm-up's num_steps), clamped to [0, max] by the kernels; `host`:
 // the same [T] entries where the caller knows them (nullptr: the warm-up's cell), `sum` their total.
@@ -2732,112 +2741,77 @@ static int hmc_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size, i
   a.eps = step_size; a.thr = divergence_threshold;
   a.rng = rng; a.nsites = 2;
   a.q = q; a.U = U; a.g = g; a.out = *out;
+  // The routes below run the whole call in one launch on (EngineArgs, HmcSampleArgs): the kernel, then n_leapfrog of the
+  // whole call where the kernel does not write it itself (fill_n_leapfrog)
+  HmcSampleArgs h{(long long)L, (long long)T, samples, acc_hist, (int *)div_hist, ctx->tgt.prec, nullptr, dl};
+  const auto run = [&](auto launch, int64_t n_leapfrog, bool only_multi) -> int {
+    if (int rc = profiled(ctx, st, launch)) return rc;
+    return fill_n_leapfrog(ctx, C, n_leapfrog, T, out, only_multi, st);
+  };
   if (path == HMC_PATH_FUSED_DENSE) {  // small dense problems: all T transitions in one launch (k_hmc_fused_dense), as for NUTS
     const bool tjoint = a.tkind == AEHMC_T_JOINT;
     const bool md = a.met_ndim == 2, td = a.tkind == AEHMC_T_DENSE_MVN, pc = md && ctx->met.per_chain;
     EngineArgs b = a;
     b.linear = 0;  // literal products (metrics.py:71)
     const KernelLaunch k = hmc_fused_dense_launch(md, td, pc, D, C, len != nullptr);
-    double *imm_ws = nullptr;
     if (pc) {  // the chains' transposed matrices
       if (int rc = grow(ctx, &ctx->fd_ws, &ctx->fd_ws_bytes, (size_t)C * D * D * sizeof(double))) return rc;
-      imm_ws = ctx->fd_ws;
+      h.imm_ws = ctx->fd_ws;
     }
-#define AEHMC_FD_LAUNCH(MDV, TDV, PCV)                                                                         \
-  do {                                                                                                         \
-    if (len) {                                                                                                 \
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_fused_dense<MDV, TDV, PCV, HmcLengths>), \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.dyn));                     \
-      hipLaunchKernelGGL((k_hmc_fused_dense<MDV, TDV, PCV, HmcLengths>), k.grid, k.block, k.dyn, st, b, ctx->tgt.prec, \
-                         imm_ws, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, dl);          \
-    } else {                                                                                                   \
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_fused_dense<MDV, TDV, PCV>),             \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.dyn));                     \
-      hipLaunchKernelGGL((k_hmc_fused_dense<MDV, TDV, PCV>), k.grid, k.block, k.dyn, st, b, ctx->tgt.prec, imm_ws, \
-                         (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);                      \
-    }                                                                                                          \
-  } while (0)
-    const auto launch = [&](bool) -> int {
-      if (tjoint) {  // the same kernel, compiled against the user's density
-        const double *noprec = nullptr;
-        if (int rc = len ? rtc_launch(ctx, RTC_JHMC, k, st, b, noprec, imm_ws, (long long)L, (long long)T, samples, acc_hist,
-                                      (int *)div_hist, dl)
-                         : rtc_launch(ctx, RTC_JHMC, k, st, b, noprec, imm_ws, (long long)L, (long long)T, samples, acc_hist,
-                                      (int *)div_hist))
-          return rc;
-      } else if (md && td && pc) AEHMC_FD_LAUNCH(true, true, true);
+#define AEHMC_FD_LAUNCH(MDV, TDV, PCV) \
+  HIPCHK((len ? launch_hmc_fused_dense<MDV, TDV, PCV, true> : launch_hmc_fused_dense<MDV, TDV, PCV, false>)(k, b, h, st))
+    return run([&](bool) -> int {
+      if (tjoint) return rtc_launch(ctx, RTC_JHMC, k, st, b, h);  // the same kernel, compiled against the user's density
+      if (md && td && pc) AEHMC_FD_LAUNCH(true, true, true);
       else if (md && td) AEHMC_FD_LAUNCH(true, true, false);
       else if (md && pc) AEHMC_FD_LAUNCH(true, false, true);
       else if (md) AEHMC_FD_LAUNCH(true, false, false);
       else AEHMC_FD_LAUNCH(false, true, false);
-      HIPCHK(hipGetLastError());
       return 0;
-    };
+    }, total, true);
 #undef AEHMC_FD_LAUNCH
-    if (int rc = profiled(ctx, st, launch)) return rc;
-    return fill_n_leapfrog(ctx, C, total, T, out, true, st);
   }
   if (path == HMC_PATH_GLM_ROWS) {  // row-reduction target with D <= 32, scalar / diagonal metric: all T transitions in one launch (glm_rows.cuh)
     const bool wg = glm_wg_wanted(ctx, D, C);
     const std::string name = glm_name(wg ? "k_hmc_glm_wg" : "k_hmc_glm_rows", D, wg);
-    const auto launch = [&](bool) -> int {
+    return run([&](bool) -> int {
       int waves = 0;
       if (wg)
         if (int rc = wg_program(ctx, RTC_GLMK, name, &waves)) return rc;
-      return rtc_launch(ctx, {RTC_GLMK, waves}, name, wg ? dim3((unsigned)C) : chain_grid(C), dim3(wg ? 512 : 256), 0, st, a,
-                        (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, (const double *)ctx->glm_XT,
-                        ctx->glm_y, (long long)ctx->glm_N);
-    };
-    if (int rc = profiled(ctx, st, launch)) return rc;
-    return fill_n_leapfrog(ctx, C, L * T, T, out, false, st);
+      return rtc_launch(ctx, {RTC_GLMK, waves}, name, wg ? dim3((unsigned)C) : chain_grid(C), dim3(wg ? 512 : 256), 0, st, a, h,
+                        (const double *)ctx->glm_XT, ctx->glm_y, (long long)ctx->glm_N);
+    }, L * T, false);
   }
   if (path == HMC_PATH_JOINT_WG) {  // traced joint density with long data sweeps, few chains: a workgroup per chain (k_hmc_joint_wg)
-    const auto launch = [&](bool) -> int {
+    return run([&](bool) -> int {
       int waves = 0;
       if (int rc = wg_program(ctx, RTC_JWG, RTC_JWG_HMC, &waves)) return rc;
-      return rtc_launch(ctx, {RTC_JWG, waves}, RTC_JWG_HMC, dim3((unsigned)C), dim3(512), (size_t)2 * D * sizeof(double), st, a,
-                        (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);
-    };
-    if (int rc = profiled(ctx, st, launch)) return rc;
-    return fill_n_leapfrog(ctx, C, L * T, T, out, false, st);
+      return rtc_launch(ctx, {RTC_JWG, waves}, RTC_JWG_HMC, dim3((unsigned)C), dim3(512), (size_t)2 * D * sizeof(double), st, a, h);
+    }, L * T, false);
   }
   if (path == HMC_PATH_JOINT_ROWS) {  // all T transitions in one launch, the lock-step loop of a chain in one wavefront (k_hmc_joint_rows)
-    const auto launch = [&](bool) -> int {
-      return rtc_launch(ctx, RTC_JBASE, "aehmc::k_hmc_joint_rows", chain_grid(C), dim3(256), (size_t)8 * D * sizeof(double), st, a,
-                        (long long)L, (long long)T, samples, acc_hist, (int *)div_hist);
-    };
-    if (int rc = profiled(ctx, st, launch)) return rc;
-    return fill_n_leapfrog(ctx, C, L * T, T, out, false, st);
+    return run([&](bool) -> int {
+      return rtc_launch(ctx, RTC_JBASE, "aehmc::k_hmc_joint_rows", chain_grid(C), dim3(256), (size_t)8 * D * sizeof(double), st, a, h);
+    }, L * T, false);
   }
   if (path == HMC_PATH_PC_DENSE) {  // all T transitions in one launch, the wavefront that owns a chain streaming its matrix (nuts_pc_dense.cuh)
-    const auto launch = [&](bool) -> int { HIPCHK(tu::hmc_pc_dense(a, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, st)); return 0; };
-    if (int rc = profiled(ctx, st, launch)) return rc;
-    return fill_n_leapfrog(ctx, C, L * T, T, out, false, st);
+    return run([&](bool) -> int { HIPCHK(tu::hmc_pc_dense(a, h, st)); return 0; }, L * T, false);
   }
   if (path == HMC_PATH_BLOCK_DENSE) {  // all T transitions in one launch, a workgroup per 16 chains, products on MFMA (nuts_block.cuh)
     if (int rc = grow(ctx, &ctx->blk_pack, &ctx->blk_pack_bytes, blk_pack_bytes(D))) return rc;
     double *bp = ctx->blk_pack;
-    const auto launch = [&](bool) -> int {
+    return run([&](bool) -> int {
       if (a.tkind == AEHMC_T_CUSTOM) {  // user-defined coordinate-wise target: the same kernels, compiled against the user's function (round 5)
         BlkMats mats;
         HIPCHK(blk_pack_matrices(a, nullptr, bp, mats, st));
         EngineArgs b = a;
         b.imm = mats.imm; b.sqrt_mass = mats.sqrt_mass;
-        const KernelLaunch k = block_launch(/*nuts*/ false, ctx->opt_block_dense != 2, D, C, len != nullptr);
-        return len ? rtc_launch(ctx, RTC_BLOCK, k, st, b, (const double *)nullptr, (long long)L, (long long)T, samples, acc_hist,
-                                (int *)div_hist, dl)
-                   : rtc_launch(ctx, RTC_BLOCK, k, st, b, (const double *)nullptr, (long long)L, (long long)T, samples, acc_hist,
-                                (int *)div_hist);
+        return rtc_launch(ctx, RTC_BLOCK, block_launch(/*nuts*/ false, ctx->opt_block_dense != 2, D, C, len != nullptr), st, b, h);
       }
-      const HmcLengths *dlp = len ? &dl : nullptr;
-      if (ctx->opt_block_dense != 2 && block_reg_supported(D))
-        HIPCHK(tu::hmc_block_reg(a, ctx->tgt.prec, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, bp, st, dlp));
-      else
-        HIPCHK(tu::hmc_block_dense(a, ctx->tgt.prec, (long long)L, (long long)T, samples, acc_hist, (int *)div_hist, bp, st, dlp));
+      if (ctx->opt_block_dense != 2 && block_reg_supported(D)) HIPCHK(tu::hmc_block_reg(a, h, bp, st));
+      else HIPCHK(tu::hmc_block_dense(a, h, bp, st));
       return 0;
-    };
-    if (int rc = profiled(ctx, st, launch)) return rc;
-    return fill_n_leapfrog(ctx, C, total, T, out, true, st);
+    }, total, true);
   }
   for (int64_t t = 0; t < T; t++) {
     EngineArgs wa;  // whitened mode: each transition mapped in and out on its own (white_begin / white_end)

@@ -149,47 +149,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(glm_rows_mi
     U_state = pick2(ct.U_slot, ct.prop_slot);
     nleap_sum += ct.nleap;
     __threadfence_block();
-    if (m.samples) {
-      double *dst = m.samples + ((size_t)t_idx * a.C + c) * a.D;
-      for (long long i = lane; i < a.D; i += 64) dst[i] = a.q[row + i];
-    }
-    if (lane == 0) {
-      if (m.acc_hist) m.acc_hist[(size_t)t_idx * a.C + c] = ct.acc_prob;
-      if (m.div_hist) m.div_hist[(size_t)t_idx * a.C + c] = ct.out_div;
-    }
+    record_row(a, m.samples, t_idx, c, lane);
+    if (lane == 0) record_hist(a, m.acc_hist, m.div_hist, t_idx, c, ct.acc_prob, ct.out_div);
   }
   rng_store(a, c, lane, rng, 0, 3);
   if (lane == 0 && m.nleap_total) m.nleap_total[c] = nleap_sum;
 }
 template <int DA>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(glm_rows_min_waves(DA)))) void k_hmc_glm_rows(EngineArgs a, long long L, long long nt, double *samples, double *acc_hist,
-                                                      int *div_hist, const double *XT, const double *y, long long N) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(glm_rows_min_waves(DA)))) void k_hmc_glm_rows(EngineArgs a, HmcSampleArgs h, const double *XT, const double *y, long long N) {
   __shared__ double glm_q[4][DA];
   AEHMC_CHAIN_OF_WAVE();
   double *const qs = glm_q[__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))];
   const size_t row = (size_t)c * a.D;
   Pcg64 g1 = pcg_load(a.rng + (size_t)c * a.nsites * 4), g2 = pcg_load(a.rng + ((size_t)c * a.nsites + 1) * 4);
   double U_state = a.U[c];
-  for (long long tt = 0; tt < nt; tt++) {
+  for (long long tt = 0; tt < h.T; tt++) {
     draw_momentum<false>(a, c, lane, g1);
     ChainCtl ct = hmc_init_chain<false>(a, c, lane, &U_state);
-    for (long long l = 0; l < L; l++) {  // trajectory.py:86-95
+    for (long long l = 0; l < h.L; l++) {  // trajectory.py:86-95
       double U_new = 0.0;
       leap_stages<true, true, false, false>(a, c, lane, 1, U_new);
       ct.U_cur = glm_rows_eval<DA>(a, XT, y, N, a.cur_q + row, a.cur_g + row, qs, lane);
       leap_stages<false, false, true, false>(a, c, lane, 1, U_new);
     }
     __threadfence_block();
-    const HmcEnd e = hmc_end_chain_rng<false>(a, c, lane, ct, L, g2);
+    const HmcEnd e = hmc_end_chain_rng<false>(a, c, lane, ct, h.L, g2);
     if (e.acc) U_state = ct.U_cur;
-    if (samples) {
-      double *dst = samples + ((size_t)tt * a.C + c) * a.D;
-      for (long long i = lane; i < a.D; i += 64) dst[i] = a.q[row + i];
-    }
-    if (lane == 0) {
-      if (acc_hist) acc_hist[(size_t)tt * a.C + c] = e.pa;
-      if (div_hist) div_hist[(size_t)tt * a.C + c] = e.is_div;
-    }
+    record_row(a, h.samples, tt, c, lane);
+    if (lane == 0) record_hist(a, h.acc_hist, h.div_hist, tt, c, e.pa, e.is_div);
   }
   if (lane == 0) {
     pcg_store(a.rng + (size_t)c * a.nsites * 4, g1);
@@ -294,14 +281,8 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_w
       U_state = pick2(ct.U_slot, ct.prop_slot);
       nleap_sum += ct.nleap;
       __threadfence_block();
-      if (m.samples) {
-        double *dst = m.samples + ((size_t)t_idx * a.C + c) * a.D;
-        for (long long i = lane; i < a.D; i += 64) dst[i] = a.q[row + i];
-      }
-      if (lane == 0) {
-        if (m.acc_hist) m.acc_hist[(size_t)t_idx * a.C + c] = ct.acc_prob;
-        if (m.div_hist) m.div_hist[(size_t)t_idx * a.C + c] = ct.out_div;
-      }
+      record_row(a, m.samples, t_idx, c, lane);
+      if (lane == 0) record_hist(a, m.acc_hist, m.div_hist, t_idx, c, ct.acc_prob, ct.out_div);
     }
   }
   if (leader) {
@@ -310,8 +291,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_w
   }
 }
 template <int DA, int W>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_waves(W)))) void k_hmc_glm_wg(EngineArgs a, long long L, long long nt, double *samples, double *acc_hist,
-                                                       int *div_hist, const double *XT, const double *y, long long N) {
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_waves(W)))) void k_hmc_glm_wg(EngineArgs a, HmcSampleArgs h, const double *XT, const double *y, long long N) {
   __shared__ double glm_q[DA];
   __shared__ double glm_part[W * (DA + 1) + 1];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -320,13 +300,13 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_w
   const size_t row = (size_t)c * a.D;
   Pcg64 g1 = pcg_load(a.rng + (size_t)c * a.nsites * 4), g2 = pcg_load(a.rng + ((size_t)c * a.nsites + 1) * 4);
   double U_state = a.U[c];
-  for (long long tt = 0; tt < nt; tt++) {
+  for (long long tt = 0; tt < h.T; tt++) {
     ChainCtl ct = {};
     if (leader) {
       draw_momentum<false>(a, c, lane, g1);
       ct = hmc_init_chain<false>(a, c, lane, &U_state);
     }
-    for (long long l = 0; l < L; l++) {  // trajectory.py:86-95
+    for (long long l = 0; l < h.L; l++) {  // trajectory.py:86-95
       double U_new = 0.0;
       if (leader) {
         leap_stages<true, true, false, false>(a, c, lane, 1, U_new);
@@ -341,16 +321,10 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(wg_min_w
     }
     if (leader) {
       __threadfence_block();
-      const HmcEnd e = hmc_end_chain_rng<false>(a, c, lane, ct, L, g2);
+      const HmcEnd e = hmc_end_chain_rng<false>(a, c, lane, ct, h.L, g2);
       if (e.acc) U_state = ct.U_cur;
-      if (samples) {
-        double *dst = samples + ((size_t)tt * a.C + c) * a.D;
-        for (long long i = lane; i < a.D; i += 64) dst[i] = a.q[row + i];
-      }
-      if (lane == 0) {
-        if (acc_hist) acc_hist[(size_t)tt * a.C + c] = e.pa;
-        if (div_hist) div_hist[(size_t)tt * a.C + c] = e.is_div;
-      }
+      record_row(a, h.samples, tt, c, lane);
+      if (lane == 0) record_hist(a, h.acc_hist, h.div_hist, tt, c, e.pa, e.is_div);
     }
   }
   if (leader && lane == 0) {

@@ -195,7 +195,6 @@ __global__ __launch_bounds__(BLK_THREADS) void k_nuts_block_dense(EngineArgs a, 
   const long long c0 = (long long)blockIdx.x * BLK_CHAINS, c = c0 + wave;
   const bool valid = c < a.C;
   const int S = (int)blk_lds_stride(a.D);
-  const size_t row = (size_t)(valid ? c : 0) * a.D;
   ChainRng rng = {};
   ChainCtl ct = {};
   ct.done = 1;
@@ -241,14 +240,8 @@ __global__ __launch_bounds__(BLK_THREADS) void k_nuts_block_dense(EngineArgs a, 
     if (valid) {
       U_state = pick2(ct.U_slot, ct.prop_slot);
       nleap_sum += ct.nleap;
-      if (m.samples) {
-        double *dst = m.samples + ((size_t)t_idx * a.C + c) * a.D;
-        for (long long i = lane; i < a.D; i += 64) dst[i] = a.q[row + i];
-      }
-      if (lane == 0) {
-        if (m.acc_hist) m.acc_hist[(size_t)t_idx * a.C + c] = ct.acc_prob;
-        if (m.div_hist) m.div_hist[(size_t)t_idx * a.C + c] = ct.out_div;
-      }
+      record_row(a, m.samples, t_idx, c, lane);
+      if (lane == 0) record_hist(a, m.acc_hist, m.div_hist, t_idx, c, ct.acc_prob, ct.out_div);
     }
   }
   if (valid) {
@@ -261,18 +254,15 @@ __global__ __launch_bounds__(BLK_THREADS) void k_nuts_block_dense(EngineArgs a, 
   }
 }
 
-// HMC: hmc_run's lock-step loop (engine.hip) for 16 chains, nt transitions x L leapfrogs in one launch.
-template <bool TDENSE, class... Len>
-__global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_dense(EngineArgs a, const double *prec, long long L,
-                                                                  long long nt, double *samples, double *acc_hist,
-                                                                  int *div_hist, Len... len) {
+// HMC: hmc_run's lock-step loop (engine.hip) for 16 chains, h.T transitions x h.L leapfrogs in one launch.
+template <bool TDENSE, bool LS = false>
+__global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_dense(EngineArgs a, HmcSampleArgs h) {
   extern __shared__ __attribute__((aligned(16))) double blk_lds[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const long long c0 = (long long)blockIdx.x * BLK_CHAINS, c = c0 + wave;
   const bool valid = c < a.C;
   const int S = (int)blk_lds_stride(a.D);
-  const size_t row = (size_t)(valid ? c : 0) * a.D;
   Pcg64 g1 = {}, g2 = {};
   double U_state = 0.0;
   BlkTimer tm;
@@ -281,8 +271,8 @@ __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_dense(EngineArgs a, c
     g2 = pcg_load(a.rng + ((size_t)c * a.nsites + 1) * 4);
     U_state = a.U[c];
   }
-  for (long long tt = 0; tt < nt; tt++) {
-    const long long Lt = hmc_length(L, tt, len...);  // (the same for every chain: the barriers inside the products hold)
+  for (long long tt = 0; tt < h.T; tt++) {
+    const long long Lt = LS ? hmc_length(h.L, tt, h.len) : h.L;  // (the same for every chain: the barriers inside the products hold)
     if (valid) draw_momentum<true>(a, c, lane, g1);
     blk_gemm(blk_lds, S, a.zbuf, a.sqrt_mass, a.cur_p, a.D, c0, a.C, wave, lane, tm);
     blk_gemm(blk_lds, S, a.cur_p, a.imm, a.cur_v, a.D, c0, a.C, wave, lane, tm);
@@ -294,7 +284,7 @@ __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_dense(EngineArgs a, c
         double U_new = 0.0;
         if (leap_linear<12>(a, c, lane, 1, U_new)) ct.U_cur = U_new;
       }
-      if (TDENSE) blk_gemm(blk_lds, S, a.rbuf, prec, a.cur_g, a.D, c0, a.C, wave, lane, tm);
+      if (TDENSE) blk_gemm(blk_lds, S, a.rbuf, h.prec, a.cur_g, a.D, c0, a.C, wave, lane, tm);
       blk_gemm(blk_lds, S, a.cur_g, a.imm, a.cur_w, a.D, c0, a.C, wave, lane, tm);
       if (valid) {
         double U_new = 0.0;
@@ -305,14 +295,8 @@ __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_dense(EngineArgs a, c
       __threadfence_block();
       const HmcEnd e = hmc_end_chain_rng<true>(a, c, lane, ct, Lt, g2);
       if (e.acc) U_state = ct.U_cur;
-      if (samples) {  // (a.q: what this lane has just written, or left untouched on rejection)
-        double *dst = samples + ((size_t)tt * a.C + c) * a.D;
-        for (long long i = lane; i < a.D; i += 64) dst[i] = a.q[row + i];
-      }
-      if (lane == 0) {
-        if (acc_hist) acc_hist[(size_t)tt * a.C + c] = e.pa;
-        if (div_hist) div_hist[(size_t)tt * a.C + c] = e.is_div;
-      }
+      record_row(a, h.samples, tt, c, lane);  // (a.q: what this lane has just written, or left untouched on rejection)
+      if (lane == 0) record_hist(a, h.acc_hist, h.div_hist, tt, c, e.pa, e.is_div);
     }
   }
   if (valid && lane == 0) {
@@ -363,32 +347,25 @@ inline hipError_t launch_nuts_block_dense(EngineArgs a, NutsSampleArgs m, double
   return hipGetLastError();
 }
 
-inline hipError_t launch_hmc_block_dense(EngineArgs a, const double *prec, long long L, long long nt,
-                                         double *samples, double *acc_hist, int *div_hist, double *bp, hipStream_t st,
-                                         const HmcLengths *len = nullptr) {
-  const bool td = a.tkind == AEHMC_T_DENSE_MVN;
+// (LS: the instantiation that reads the trajectory lengths h.len from device memory)
+inline hipError_t launch_hmc_block_dense(EngineArgs a, HmcSampleArgs h, double *bp, hipStream_t st) {
+  const bool td = a.tkind == AEHMC_T_DENSE_MVN, ls = h.len.Ls != nullptr;
   BlkMats mats;
-  if (hipError_t e = blk_pack_matrices(a, prec, bp, mats, st)) return e;
-  a.imm = mats.imm; a.sqrt_mass = mats.sqrt_mass;
+  if (hipError_t e = blk_pack_matrices(a, h.prec, bp, mats, st)) return e;
+  a.imm = mats.imm; a.sqrt_mass = mats.sqrt_mass; h.prec = mats.prec;
   const size_t dyn = blk_lds_bytes(a.D);
   const dim3 grid((unsigned)((a.C + BLK_CHAINS - 1) / BLK_CHAINS)), block(BLK_THREADS);
-#define AEHMC_BLK(TDV)                                                                                       \
+#define AEHMC_BLK(TDV, LSV)                                                                                  \
   do {                                                                                                       \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_block_dense<TDV>),              \
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_block_dense<TDV, LSV>),         \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);                \
-    if (e == hipSuccess && len)                                                                              \
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_block_dense<TDV, HmcLengths>),           \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);                         \
     if (e != hipSuccess) return e;                                                                           \
-    if (len)                                                                                                 \
-      hipLaunchKernelGGL((k_hmc_block_dense<TDV, HmcLengths>), grid, block, dyn, st, a, mats.prec, L, nt, samples, \
-                         acc_hist, div_hist, *len);                                                          \
-    else                                                                                                     \
-      hipLaunchKernelGGL((k_hmc_block_dense<TDV>), grid, block, dyn, st, a, mats.prec, L, nt, samples, acc_hist, \
-                         div_hist);                                                                          \
+    hipLaunchKernelGGL((k_hmc_block_dense<TDV, LSV>), grid, block, dyn, st, a, h);                           \
   } while (0)
-  if (td) AEHMC_BLK(true);
-  else AEHMC_BLK(false);
+  if (td && ls) AEHMC_BLK(true, true);
+  else if (td) AEHMC_BLK(true, false);
+  else if (ls) AEHMC_BLK(false, true);
+  else AEHMC_BLK(false, false);
 #undef AEHMC_BLK
   return hipGetLastError();
 }

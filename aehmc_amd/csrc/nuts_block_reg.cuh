@@ -295,10 +295,7 @@ __global__ __launch_bounds__(BLK_THREADS) void k_nuts_block_reg(EngineArgs a, Nu
         for (int r = 0; r < R; r++)
           if (ok[r]) dst[EI(r)] = AT(a.q, r);
       }
-      if (lane == 0) {
-        if (m.acc_hist) m.acc_hist[(size_t)t_idx * a.C + c] = ct.acc_prob;
-        if (m.div_hist) m.div_hist[(size_t)t_idx * a.C + c] = ct.out_div;
-      }
+      if (lane == 0) record_hist(a, m.acc_hist, m.div_hist, t_idx, c, ct.acc_prob, ct.out_div);
     }
   }
   if (valid) {
@@ -317,13 +314,11 @@ __global__ __launch_bounds__(BLK_THREADS) void k_nuts_block_reg(EngineArgs a, Nu
 #undef AT
 }
 
-// HMC: nt transitions x L leapfrogs, the chains' q, p, v in registers, dU/dq and w = imm dU/dq in the LDS rows the
+// HMC: h.T transitions x h.L leapfrogs, the chains' q, p, v in registers, dU/dq and w = imm dU/dq in the LDS rows the
 // products write (as above) -- hmc_run's lock-step loop: hmc_init_chain, leap_linear<12> / <3>, hmc_end_chain.  The
 // state a rejection falls back to is the caller's q / dU/dq, rewritten at every accepted transition.
-template <int R, bool TDENSE, class... Len>
-__global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_reg(EngineArgs a, const double *prec, long long L,
-                                                                long long nt, double *samples, double *acc_hist,
-                                                                int *div_hist, Len... len) {
+template <int R, bool TDENSE, bool LS = false>
+__global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_reg(EngineArgs a, HmcSampleArgs h) {
   extern __shared__ __attribute__((aligned(16))) double blk_lds[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -356,7 +351,7 @@ __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_reg(EngineArgs a, con
   Pcg64 g1 = {}, g2 = {};
   double U = 0.0, eps = 0.0, pa = 0.0;
   int is_div = 0, acc = 0;
-  long long Lt = L;
+  long long Lt = h.L;
   if (valid) {
     g1 = pcg_load(a.rng + (size_t)c * a.nsites * 4);
     g2 = pcg_load(a.rng + ((size_t)c * a.nsites + 1) * 4);
@@ -365,9 +360,9 @@ __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_reg(EngineArgs a, con
   }
   const double b = 0.5 * (1.0 * eps), aa = 1 * (1.0 * eps);  // direction +1 (launch_leapfrog: ct.dir = 1)
   blk_barrier_lds();
-  for (long long tt = 0; tt < nt; tt++) {
-    const bool last_t = tt == nt - 1;
-    Lt = hmc_length(L, tt, len...);  // (the same for every chain: the barriers between the products hold)
+  for (long long tt = 0; tt < h.T; tt++) {
+    const bool last_t = tt == h.T - 1;
+    Lt = LS ? hmc_length(h.L, tt, h.len) : h.L;  // (the same for every chain: the barriers between the products hold)
     if (valid) {
       wave_normals(g1, D, [=](long long i, double z) { xrow[i] = z; });
       __threadfence_block();
@@ -423,7 +418,7 @@ __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_reg(EngineArgs a, con
       if (!TDENSE && valid) U_cur = target_finish(a, wave_sum(usum));
       blk_barrier_lds();
       if (TDENSE) {
-        blk_gemm_lds(xbuf, ybuf, S, prec, D, wave, lane, tb);
+        blk_gemm_lds(xbuf, ybuf, S, h.prec, D, wave, lane, tb);
         blk_barrier_lds();
         blk_gemm_lds(ybuf, xbuf, S, a.imm, D, wave, lane, tb);
         blk_barrier_lds();
@@ -476,16 +471,13 @@ __global__ __launch_bounds__(BLK_THREADS) void k_hmc_block_reg(EngineArgs a, con
 #pragma unroll
         for (int r = 0; r < R; r++) q[r] = ok[r] ? AT(a.q, r) : 0.0;
       }
-      if (samples) {
-        double *dst = samples + ((size_t)tt * a.C + c) * D;
+      if (h.samples) {
+        double *dst = h.samples + ((size_t)tt * a.C + c) * D;
 #pragma unroll
         for (int r = 0; r < R; r++)
           if (ok[r]) dst[EI(r)] = q[r];
       }
-      if (lane == 0) {
-        if (acc_hist) acc_hist[(size_t)tt * a.C + c] = pa;
-        if (div_hist) div_hist[(size_t)tt * a.C + c] = is_div;
-      }
+      if (lane == 0) record_hist(a, h.acc_hist, h.div_hist, tt, c, pa, is_div);
     }
   }
   if (valid && lane == 0) {
@@ -526,39 +518,29 @@ inline hipError_t launch_nuts_block_reg(EngineArgs a, NutsSampleArgs m, double *
 }
 
 template <int R>
-inline hipError_t launch_hmc_block_reg_r(const EngineArgs &a, const double *prec, long long L, long long nt,
-                                         double *samples, double *acc_hist, int *div_hist, hipStream_t st,
-                                         const HmcLengths *len) {
+inline hipError_t launch_hmc_block_reg_r(const EngineArgs &a, const HmcSampleArgs &h, hipStream_t st) {
+  const bool td = a.tkind == AEHMC_T_DENSE_MVN, ls = h.len.Ls != nullptr;
   const size_t dyn = blk_reg_lds_bytes(a.D);
   const dim3 grid((unsigned)((a.C + BLK_CHAINS - 1) / BLK_CHAINS)), block(BLK_THREADS);
-#define AEHMC_BLK(TDV)                                                                                       \
+#define AEHMC_BLK(TDV, LSV)                                                                                  \
   do {                                                                                                       \
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_block_reg<R, TDV>),             \
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_block_reg<R, TDV, LSV>),        \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);                \
-    if (e == hipSuccess && len)                                                                              \
-      e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_hmc_block_reg<R, TDV, HmcLengths>),          \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);                         \
     if (e != hipSuccess) return e;                                                                           \
-    if (len)                                                                                                 \
-      hipLaunchKernelGGL((k_hmc_block_reg<R, TDV, HmcLengths>), grid, block, dyn, st, a, prec, L, nt, samples, \
-                         acc_hist, div_hist, *len);                                                          \
-    else                                                                                                     \
-      hipLaunchKernelGGL((k_hmc_block_reg<R, TDV>), grid, block, dyn, st, a, prec, L, nt, samples, acc_hist, \
-                         div_hist);                                                                          \
+    hipLaunchKernelGGL((k_hmc_block_reg<R, TDV, LSV>), grid, block, dyn, st, a, h);                          \
   } while (0)
-  if (a.tkind == AEHMC_T_DENSE_MVN) AEHMC_BLK(true);
-  else AEHMC_BLK(false);
+  if (td && ls) AEHMC_BLK(true, true);
+  else if (td) AEHMC_BLK(true, false);
+  else if (ls) AEHMC_BLK(false, true);
+  else AEHMC_BLK(false, false);
 #undef AEHMC_BLK
   return hipGetLastError();
 }
-inline hipError_t launch_hmc_block_reg(EngineArgs a, const double *prec, long long L, long long nt, double *samples,
-                                       double *acc_hist, int *div_hist, double *bp, hipStream_t st,
-                                       const HmcLengths *len = nullptr) {
+inline hipError_t launch_hmc_block_reg(EngineArgs a, HmcSampleArgs h, double *bp, hipStream_t st) {
   BlkMats mats;
-  if (hipError_t e = blk_pack_matrices(a, prec, bp, mats, st)) return e;
-  a.imm = mats.imm; a.sqrt_mass = mats.sqrt_mass;
-  return a.D <= 128 ? launch_hmc_block_reg_r<2>(a, mats.prec, L, nt, samples, acc_hist, div_hist, st, len)
-                    : launch_hmc_block_reg_r<4>(a, mats.prec, L, nt, samples, acc_hist, div_hist, st, len);
+  if (hipError_t e = blk_pack_matrices(a, h.prec, bp, mats, st)) return e;
+  a.imm = mats.imm; a.sqrt_mass = mats.sqrt_mass; h.prec = mats.prec;
+  return a.D <= 128 ? launch_hmc_block_reg_r<2>(a, h, st) : launch_hmc_block_reg_r<4>(a, h, st);
 }
 // The run-time compiled block kernel of a coordinate-wise user-defined target, for NUTS or for HMC: the register
 // kernel where it exists (`reg_allowed`: the "block_dense" option is not 2), the work-row kernel otherwise

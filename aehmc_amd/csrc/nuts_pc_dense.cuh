@@ -111,36 +111,29 @@ __global__ __launch_bounds__(256) void k_nuts_pc_dense(EngineArgs a, NutsSampleA
     U_state = pick2(ct.U_slot, ct.prop_slot);
     nleap_sum += ct.nleap;
     __threadfence_block();
-    if (m.samples) {
-      double *dst = m.samples + ((size_t)t_idx * a.C + c) * a.D;
-      for (long long i = lane; i < a.D; i += 64) dst[i] = a.q[row + i];
-    }
-    if (lane == 0) {
-      if (m.acc_hist) m.acc_hist[(size_t)t_idx * a.C + c] = ct.acc_prob;
-      if (m.div_hist) m.div_hist[(size_t)t_idx * a.C + c] = ct.out_div;
-    }
+    record_row(a, m.samples, t_idx, c, lane);
+    if (lane == 0) record_hist(a, m.acc_hist, m.div_hist, t_idx, c, ct.acc_prob, ct.out_div);
   }
   rng_store(a, c, lane, rng, 0, 3);
   if (lane == 0 && m.nleap_total) m.nleap_total[c] = nleap_sum;
 }
 
-// HMC: hmc_run's lock-step loop (engine.hip) for one chain per wavefront, nt transitions x L leapfrogs in one launch.
+// HMC: hmc_run's lock-step loop (engine.hip) for one chain per wavefront, h.T transitions x h.L leapfrogs in one launch.
 template <int R>
-__global__ __launch_bounds__(256) void k_hmc_pc_dense(EngineArgs a, long long L, long long nt, double *samples,
-                                                       double *acc_hist, int *div_hist) {
+__global__ __launch_bounds__(256) void k_hmc_pc_dense(EngineArgs a, HmcSampleArgs h) {
   AEHMC_CHAIN_OF_WAVE();
   const int D = (int)a.D;
   const size_t row = (size_t)c * a.D;
   const double *const imm = a.imm + (size_t)c * D * D, *const sm = a.sqrt_mass + (size_t)c * D * D;
   Pcg64 g1 = pcg_load(a.rng + (size_t)c * a.nsites * 4), g2 = pcg_load(a.rng + ((size_t)c * a.nsites + 1) * 4);
   double U_state = a.U[c];
-  for (long long tt = 0; tt < nt; tt++) {
+  for (long long tt = 0; tt < h.T; tt++) {
     draw_momentum<true>(a, c, lane, g1);
     wave_matvec_stream<R>(sm, a.zbuf + row, a.cur_p + row, D, lane);   // p = L^-T z
     wave_matvec_stream<R>(imm, a.cur_p + row, a.cur_v + row, D, lane);  // v = imm p
     wave_matvec_stream<R>(imm, a.g + row, a.cur_w + row, D, lane);      // w = imm dU/dq
     ChainCtl ct = hmc_init_chain<true>(a, c, lane, &U_state);
-    for (long long l = 0; l < L; l++) {  // trajectory.py:86-95
+    for (long long l = 0; l < h.L; l++) {  // trajectory.py:86-95
       double U_new = 0.0;
       if (leap_linear<12>(a, c, lane, 1, U_new)) ct.U_cur = U_new;
       __threadfence_block();
@@ -148,16 +141,10 @@ __global__ __launch_bounds__(256) void k_hmc_pc_dense(EngineArgs a, long long L,
       if (leap_linear<3>(a, c, lane, 1, U_new)) ct.U_cur = U_new;
     }
     __threadfence_block();
-    const HmcEnd e = hmc_end_chain_rng<true>(a, c, lane, ct, L, g2);
+    const HmcEnd e = hmc_end_chain_rng<true>(a, c, lane, ct, h.L, g2);
     if (e.acc) U_state = ct.U_cur;
-    if (samples) {  // (a.q: what this lane has just written, or left untouched on rejection)
-      double *dst = samples + ((size_t)tt * a.C + c) * a.D;
-      for (long long i = lane; i < a.D; i += 64) dst[i] = a.q[row + i];
-    }
-    if (lane == 0) {
-      if (acc_hist) acc_hist[(size_t)tt * a.C + c] = e.pa;
-      if (div_hist) div_hist[(size_t)tt * a.C + c] = e.is_div;
-    }
+    record_row(a, h.samples, tt, c, lane);  // (a.q: what this lane has just written, or left untouched on rejection)
+    if (lane == 0) record_hist(a, h.acc_hist, h.div_hist, tt, c, e.pa, e.is_div);
   }
   if (lane == 0) {
     pcg_store(a.rng + (size_t)c * a.nsites * 4, g1);
@@ -175,14 +162,13 @@ inline hipError_t launch_nuts_pc_dense(const EngineArgs &a, const NutsSampleArgs
   return hipGetLastError();
 }
 
-inline hipError_t launch_hmc_pc_dense(const EngineArgs &a, long long L, long long nt, double *samples, double *acc_hist,
-                                      int *div_hist, hipStream_t st) {
+inline hipError_t launch_hmc_pc_dense(const EngineArgs &a, const HmcSampleArgs &h, hipStream_t st) {
   const dim3 grid((unsigned)((a.C + 3) / 4)), block(256);
   const int R = (int)((a.D + 63) / 64);
-  if (R <= 2) hipLaunchKernelGGL((k_hmc_pc_dense<2>), grid, block, 0, st, a, L, nt, samples, acc_hist, div_hist);
-  else if (R <= 4) hipLaunchKernelGGL((k_hmc_pc_dense<4>), grid, block, 0, st, a, L, nt, samples, acc_hist, div_hist);
-  else if (R <= 6) hipLaunchKernelGGL((k_hmc_pc_dense<6>), grid, block, 0, st, a, L, nt, samples, acc_hist, div_hist);
-  else hipLaunchKernelGGL((k_hmc_pc_dense<8>), grid, block, 0, st, a, L, nt, samples, acc_hist, div_hist);
+  if (R <= 2) hipLaunchKernelGGL((k_hmc_pc_dense<2>), grid, block, 0, st, a, h);
+  else if (R <= 4) hipLaunchKernelGGL((k_hmc_pc_dense<4>), grid, block, 0, st, a, h);
+  else if (R <= 6) hipLaunchKernelGGL((k_hmc_pc_dense<6>), grid, block, 0, st, a, h);
+  else hipLaunchKernelGGL((k_hmc_pc_dense<8>), grid, block, 0, st, a, h);
   return hipGetLastError();
 }
 

@@ -10,7 +10,7 @@ namespace aehmc {
 struct EngineArgs;
 struct NutsSampleArgs;
 struct HmcFusedArgs;
-struct HmcLengths;
+struct HmcSampleArgs;
 struct GemmStreamK;
 struct PoolArgs;
 struct CheesArgs;
@@ -35,15 +35,12 @@ hipError_t nuts_resident_dense(const EngineArgs &a, const NutsSampleArgs &m, hip
 hipError_t nuts_block_roll(const EngineArgs &a, const NutsSampleArgs &m, double *bp, hipStream_t st);
 hipError_t nuts_block_reg(const EngineArgs &a, const NutsSampleArgs &m, double *bp, hipStream_t st);
 hipError_t nuts_block_dense(const EngineArgs &a, const NutsSampleArgs &m, double *bp, hipStream_t st);
-// (`len`: trajectory lengths from device memory, or nullptr -- the launch constant L)
-hipError_t hmc_block_reg(const EngineArgs &a, const double *prec, long long L, long long nt, double *samples,
-                         double *acc_hist, int *div_hist, double *bp, hipStream_t st, const HmcLengths *len);
-hipError_t hmc_block_dense(const EngineArgs &a, const double *prec, long long L, long long nt, double *samples,
-                           double *acc_hist, int *div_hist, double *bp, hipStream_t st, const HmcLengths *len);
+// (h.len.Ls: trajectory lengths from device memory, or nullptr -- the launch constant h.L)
+hipError_t hmc_block_reg(const EngineArgs &a, const HmcSampleArgs &h, double *bp, hipStream_t st);
+hipError_t hmc_block_dense(const EngineArgs &a, const HmcSampleArgs &h, double *bp, hipStream_t st);
 // nuts_pc_dense.cuh
 hipError_t nuts_pc_dense(const EngineArgs &a, const NutsSampleArgs &m, hipStream_t st);
-hipError_t hmc_pc_dense(const EngineArgs &a, long long L, long long nt, double *samples, double *acc_hist, int *div_hist,
-                        hipStream_t st);
+hipError_t hmc_pc_dense(const EngineArgs &a, const HmcSampleArgs &h, hipStream_t st);
 // hmc_fused.cuh
 hipError_t hmc_fused(const HmcFusedArgs &a, hipStream_t st);
 hipError_t hmc_resident(const HmcFusedArgs &a, const double *zbuf, int nt, hipStream_t st);

@@ -6,9 +6,6 @@
 namespace aehmc {
 namespace tu {
 hipError_t nuts_pc_dense(const EngineArgs &a, const NutsSampleArgs &m, hipStream_t st) { return launch_nuts_pc_dense(a, m, st); }
-hipError_t hmc_pc_dense(const EngineArgs &a, long long L, long long nt, double *samples, double *acc_hist, int *div_hist,
-                        hipStream_t st) {
-  return launch_hmc_pc_dense(a, L, nt, samples, acc_hist, div_hist, st);
-}
+hipError_t hmc_pc_dense(const EngineArgs &a, const HmcSampleArgs &h, hipStream_t st) { return launch_hmc_pc_dense(a, h, st); }
 }  // namespace tu
 }  // namespace aehmc

@@ -1,6 +1,6 @@
 """CPU-side checks of the per-transition trajectory lengths: how ``kernel.sample`` reads its ``num_integration_steps``
 argument, and that the kernel instantiations which read the lengths from device memory compile against a user density
-(`hipcc -fsyntax-only`, device pass) beside the launch-constant ones, whose names and signatures stay what they were."""
+(`hipcc -fsyntax-only`, device pass) beside the launch-constant ones, whose names stay what they were."""
 import os
 import shutil
 import subprocess
@@ -53,12 +53,12 @@ __device__ void aehmc_custom_elem(double q, long long i, const double *const *pr
 template __global__ void aehmc::k_hmc_fused<2, 5, false, true>(aehmc::HmcFusedArgs);
 template __global__ void aehmc::k_hmc_fused<2, 5, true, true>(aehmc::HmcFusedArgs);
 template __global__ void aehmc::k_hmc_wide<256, 8, 5, false>(aehmc::HmcFusedArgs, const double *, int);
-template __global__ void aehmc::k_hmc_block_reg<2, false, aehmc::HmcLengths>(aehmc::EngineArgs, const double *, long long, long long, double *, double *, int *, aehmc::HmcLengths);
-template __global__ void aehmc::k_hmc_block_dense<false, aehmc::HmcLengths>(aehmc::EngineArgs, const double *, long long, long long, double *, double *, int *, aehmc::HmcLengths);
-template __global__ void aehmc::k_hmc_fused_dense<true, false, false, aehmc::HmcLengths>(aehmc::EngineArgs, const double *, double *, long long, long long, double *, double *, int *, aehmc::HmcLengths);
-// the launch-constant kernels: an empty pack, the signatures they always had
-template __global__ void aehmc::k_hmc_block_reg<2, false>(aehmc::EngineArgs, const double *, long long, long long, double *, double *, int *);
-template __global__ void aehmc::k_hmc_fused_dense<true, false, false>(aehmc::EngineArgs, const double *, double *, long long, long long, double *, double *, int *);
+template __global__ void aehmc::k_hmc_block_reg<2, false, true>(aehmc::EngineArgs, aehmc::HmcSampleArgs);
+template __global__ void aehmc::k_hmc_block_dense<false, true>(aehmc::EngineArgs, aehmc::HmcSampleArgs);
+template __global__ void aehmc::k_hmc_fused_dense<true, false, false, true>(aehmc::EngineArgs, aehmc::HmcSampleArgs);
+// the launch-constant kernels: LS left at its default, the names they always had
+template __global__ void aehmc::k_hmc_block_reg<2, false>(aehmc::EngineArgs, aehmc::HmcSampleArgs);
+template __global__ void aehmc::k_hmc_fused_dense<true, false, false>(aehmc::EngineArgs, aehmc::HmcSampleArgs);
 '''
 
 

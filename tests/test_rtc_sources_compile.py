@@ -40,8 +40,8 @@ template __global__ void aehmc::k_hmc_fused<2, 5, true>(aehmc::HmcFusedArgs);
 template __global__ void aehmc::k_nuts_block_reg<2, false>(aehmc::EngineArgs, aehmc::NutsSampleArgs);
 template __global__ void aehmc::k_nuts_block_reg<4, false>(aehmc::EngineArgs, aehmc::NutsSampleArgs);
 template __global__ void aehmc::k_nuts_block_dense<false>(aehmc::EngineArgs, aehmc::NutsSampleArgs);
-template __global__ void aehmc::k_hmc_block_reg<2, false>(aehmc::EngineArgs, const double *, long long, long long, double *, double *, int *);
-template __global__ void aehmc::k_hmc_block_dense<false>(aehmc::EngineArgs, const double *, long long, long long, double *, double *, int *);
+template __global__ void aehmc::k_hmc_block_reg<2, false>(aehmc::EngineArgs, aehmc::HmcSampleArgs);
+template __global__ void aehmc::k_hmc_block_dense<false>(aehmc::EngineArgs, aehmc::HmcSampleArgs);
 '''
 
 JOINT = r'''
@@ -58,8 +58,8 @@ template <class V> __device__ auto aehmc_logp(const V &q, const double *const *p
 // (k_new_state_joint is not a template: the syntax pass checks its body as it is)
 template __global__ void aehmc::k_nuts_resident<64, 1, true, 8, false>(aehmc::EngineArgs, aehmc::NutsSampleArgs);
 template __global__ void aehmc::k_nuts_resident<64, 1, false, 9, false>(aehmc::EngineArgs, aehmc::NutsSampleArgs);
-template __global__ void aehmc::k_hmc_fused_dense<false, false, false>(aehmc::EngineArgs, const double *, double *, long long, long long, double *, double *, int *);
-template __global__ void aehmc::k_hmc_fused_dense<true, false, true>(aehmc::EngineArgs, const double *, double *, long long, long long, double *, double *, int *);
+template __global__ void aehmc::k_hmc_fused_dense<false, false, false>(aehmc::EngineArgs, aehmc::HmcSampleArgs);
+template __global__ void aehmc::k_hmc_fused_dense<true, false, true>(aehmc::EngineArgs, aehmc::HmcSampleArgs);
 '''
 
 
@@ -82,9 +82,9 @@ __device__ void aehmc_glm_prior(double q, long long i, const double *const *prm,
 #include "glm_rows.cuh"
 template __global__ void aehmc::k_nuts_glm_rows<8>(aehmc::EngineArgs, aehmc::NutsSampleArgs, const double *, const double *, long long);
 template __global__ void aehmc::k_nuts_glm_rows<32>(aehmc::EngineArgs, aehmc::NutsSampleArgs, const double *, const double *, long long);
-template __global__ void aehmc::k_hmc_glm_rows<16>(aehmc::EngineArgs, long long, long long, double *, double *, int *, const double *, const double *, long long);
+template __global__ void aehmc::k_hmc_glm_rows<16>(aehmc::EngineArgs, aehmc::HmcSampleArgs, const double *, const double *, long long);
 template __global__ void aehmc::k_nuts_glm_wg<8, 8>(aehmc::EngineArgs, aehmc::NutsSampleArgs, const double *, const double *, long long);
-template __global__ void aehmc::k_hmc_glm_wg<32, 8>(aehmc::EngineArgs, long long, long long, double *, double *, int *, const double *, const double *, long long);
+template __global__ void aehmc::k_hmc_glm_wg<32, 8>(aehmc::EngineArgs, aehmc::HmcSampleArgs, const double *, const double *, long long);
 '''
 
 
@@ -125,7 +125,7 @@ def traced_program(fn):
     wg = ("template __global__ void aehmc::k_nuts_resident<64, 2, true, 0, false>(aehmc::EngineArgs, aehmc::NutsSampleArgs);\n"
           "template __global__ void aehmc::k_nuts_resident<64, 8, false, 0, false>(aehmc::EngineArgs, aehmc::NutsSampleArgs);\n"
           "template __global__ void aehmc::k_nuts_joint_wg<8>(aehmc::EngineArgs, aehmc::NutsSampleArgs);\n"
-          "template __global__ void aehmc::k_hmc_joint_wg<8>(aehmc::EngineArgs, long long, long long, double *, double *, int *);\n"
+          "template __global__ void aehmc::k_hmc_joint_wg<8>(aehmc::EngineArgs, aehmc::HmcSampleArgs);\n"
           "template __global__ void aehmc::k_hmc_fused<2, 7, false>(aehmc::HmcFusedArgs);\n"
           "template __global__ void aehmc::k_hmc_fused<16, 7, false>(aehmc::HmcFusedArgs);\n")
     return ("#define AEHMC_JOINT_TARGET 1\n" + tgt.source + '#include "engine.cuh"\n#include "nuts_resident.cuh"\n#include "hmc_fused.cuh"\n'
