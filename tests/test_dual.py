@@ -1,6 +1,9 @@
 """csrc/dual.cuh (forward-mode differentiation of user-defined log-densities) compiled as plain C++ on the CPU: every
 overloaded operator / function against central differences, and a template density instantiated with double and with
-Dual (the way the run-time compiled kernels use it).  Reference: aehmc/hmc.py:33-34 (aesara.grad of the potential)."""
+Dual (the way the run-time compiled kernels use it).  Reference: aehmc/hmc.py:33-34 (aesara.grad of the potential).
+Every function one at a time, value and derivative, against mpmath at 50 digits (what numpy's own formulas hide -- s (1 - s),
+1 - t t, exp(-x x) -- and the edges): tests/dual_ref.py with tests/test_dual_reference_host.py, on the device
+tests/test_gpu_dual_reference.py."""
 import os
 import subprocess
 
