@@ -275,17 +275,21 @@ __device__ __forceinline__ double vel_diag(const EngineArgs &a, long long c, lon
   return a.imm[c * a.imm_cs + (a.met_ndim == 0 ? 0 : i)] * p;
 }
 
-// One wavefront's pass over the D elements of its chain, four elements per lane in flight:
+// One wavefront's pass over the D elements of its chain, UN (four unless stated) elements per lane in flight
+// (UN = 0: the plain loop, one element at a time):
 // `load(i)` returns what element i needs from memory, `use(i, loaded)` computes and stores.
 // All loads of a batch are issued before its first store (the pointers in EngineArgs may
 // alias as far as the compiler knows, so a plain loop waits for every load before the next
 // store and streams at a quarter of HBM speed).  Each lane still visits its elements in
-// ascending order: sums are bit-identical to the plain loop.
-template <class Load, class Use>
+// ascending order: sums are bit-identical to the plain loop.  A pass is valid as long as every element is
+// read and written at its own index only and no array is both a source and a destination of another index.
+template <int UN = 4, class Load, class Use>
 __device__ __forceinline__ void wave_pass(long long D, int lane, Load load, Use use) {
-  constexpr int UN = 4;
+  if constexpr (UN == 0) {
+    for (long long i = lane; i < D; i += 64) use(i, load(i));
+  } else
   for (long long i0 = lane; i0 < D; i0 += 64 * UN) {
-    decltype(load(0LL)) vals[UN];
+    decltype(load(0LL)) vals[UN ? UN : 1];
 #pragma unroll
     for (int u = 0; u < UN; u++) {
       const long long i = i0 + 64 * u;
@@ -298,12 +302,25 @@ __device__ __forceinline__ void wave_pass(long long D, int lane, Load load, Use 
     }
   }
 }
+// Depths of the NUTS passes behind nuts_book's main one.  DEEP: the stage kernels whose bookkeeping pass carries part of
+// the leapfrog (nuts_book FUSE != 0 -- every lock-step launch of a dense or whitened problem and of a coordinate-wise
+// target, k_nuts_pc_dense, nuts_block.cuh).  Pure copies hold few registers per element and go eight deep.  The kernels
+// on the unfused pass (FUSE = 0: whole-transition kernels at their register limit, the run-time compiled rows kernels, the
+// literal dense mode) keep the one-element loops, with which they need the registers they needed before
+// (profiles/stage_tail/INDEX.md has both tables).
+template <bool DEEP>
+struct TailDepth {
+  static constexpr int COPY = DEEP ? 8 : 0, BATCH = DEEP ? 4 : 0, TURN_LV = DEEP ? 4 : 2;
+};
 struct Ld2 { double a, b; };
 struct Ld3 { double a, b, c; };
 struct Ld4 { double a, b, c, d; };
 struct Ld5 { double a, b, c, d, e; };
 struct Ld6 { double a, b, c, d, e, f; };
 struct Ld9 { double a, b, c, d, e, f, g, h, i; };
+// one element of the U-turn sweep over LV checkpoint levels (nuts_book)
+template <int LV>
+struct TurnLd { double p, v, s, kp[LV], ks[LV], kv[LV]; };
 
 // ---------------------------------------------------------------------------------
 // Leapfrog stages (integrators.py:54-73).  DO1: p_half = p - (0.5 eps) g.
@@ -433,44 +450,71 @@ __device__ __forceinline__ void rng_store(const EngineArgs &a, long long c, int 
 // ---------------------------------------------------------------------------------
 // NUTS bookkeeping after one leapfrog of the chain's moving end (cur_*).
 // ---------------------------------------------------------------------------------
-template <bool MET_DENSE>
+template <bool MET_DENSE, bool DEEP>
 __device__ __forceinline__ void copy_cur_to_slot(const EngineArgs &a, size_t row, int lane,
                                                  int slot) {
-  for (long long i = lane; i < a.D; i += 64) {
-    pick2(a.slot_q, slot)[row + i] = a.cur_q[row + i];
-    pick2(a.slot_p, slot)[row + i] = a.cur_p[row + i];
-    pick2(a.slot_g, slot)[row + i] = a.cur_g[row + i];
-  }
+  double *sq = pick2(a.slot_q, slot) + row, *sp = pick2(a.slot_p, slot) + row, *sg = pick2(a.slot_g, slot) + row;
+  wave_pass<TailDepth<DEEP>::COPY>(a.D, lane,
+                     [&](long long i) { return Ld3{a.cur_q[row + i], a.cur_p[row + i], a.cur_g[row + i]}; },
+                     [&](long long i, const Ld3 &x) {
+                       sq[i] = x.a;
+                       sp[i] = x.b;
+                       sg[i] = x.c;
+                     });
 }
 
-template <bool MET_DENSE>
-__device__ inline void nuts_begin_expansion(const EngineArgs &a, long long c, int lane,
+// HALF (k_step_white_ahead only): a chain that turns round also forms the first two stages of its next leapfrog
+// in the copy pass, from the values that pass has loaded -- white_half_step's expressions on the same bits -- instead
+// of reading the three rows back behind it
+template <bool MET_DENSE, bool HALF = false, bool DEEP = false>
+__device__ __forceinline__ void nuts_begin_expansion(const EngineArgs &a, long long c, int lane,
                                             ChainCtl &ct, int prev_dir, ChainRng &rng) {
   int go_right = rng_bernoulli(rng.g[1], 0.5);  // trajectory.py:516
   ct.dir = go_right;
   ct.step = 0;
   if (prev_dir >= 0 && prev_dir != go_right) {  // cur <- the other end (trajectory.py:518)
     const size_t row = (size_t)c * a.D;
-    for (long long i = lane; i < a.D; i += 64) {
-      a.cur_q[row + i] = pick2(a.end_q, go_right)[row + i];
-      a.cur_p[row + i] = pick2(a.end_p, go_right)[row + i];
-      a.cur_g[row + i] = pick2(a.end_g, go_right)[row + i];
-      if (MET_DENSE) a.cur_v[row + i] = pick2(a.end_v, go_right)[row + i];
-      if (MET_DENSE && a.linear) a.cur_w[row + i] = pick2(a.end_w, go_right)[row + i];
-    }
+    const bool lin = MET_DENSE && a.linear;
+    const double *eq = pick2(a.end_q, go_right) + row, *ep = pick2(a.end_p, go_right) + row;
+    const double *eg = pick2(a.end_g, go_right) + row;
+    const double *ev = MET_DENSE ? pick2(a.end_v, go_right) + row : nullptr;
+    const double *ew = lin ? pick2(a.end_w, go_right) + row : nullptr;
+    const double step_size = (go_right ? 1.0 : -1.0) * (a.eps_c ? a.eps_c[c] : a.eps);
+    const double b = 0.5 * step_size, aa = 1 * step_size;
+    // sources are the end_* rows, destinations the cur_* rows (and phalf, rbuf): no array is both
+    wave_pass<(MET_DENSE || HALF) ? TailDepth<DEEP>::BATCH : TailDepth<DEEP>::COPY>(
+        a.D, lane,
+        [&](long long i) { return Ld5{eq[i], ep[i], eg[i], MET_DENSE ? ev[i] : 0.0, lin ? ew[i] : 0.0}; },
+        [&](long long i, const Ld5 &x) {
+          a.cur_q[row + i] = x.a;
+          a.cur_p[row + i] = x.b;
+          a.cur_g[row + i] = x.c;
+          if (MET_DENSE) a.cur_v[row + i] = x.d;
+          if (lin) a.cur_w[row + i] = x.e;
+          if (HALF) {  // white_half_step
+            const double ph = x.b - b * x.c;
+            a.phalf[row + i] = ph;
+            a.rbuf[row + i] = x.a + aa * vel_diag(a, c, i, ph);
+          }
+        });
     ct.U_cur = pick2(ct.U_end, go_right);
   }
 }
 
-__device__ inline void nuts_write_outputs(const EngineArgs &a, long long c, int lane,
+template <bool DEEP>
+__device__ __forceinline__ void nuts_write_outputs(const EngineArgs &a, long long c, int lane,
                                           const ChainCtl &ct) {
   const size_t row = (size_t)c * a.D;
   const int s = ct.prop_slot;
-  for (long long i = lane; i < a.D; i += 64) {
-    a.q[row + i] = pick2(a.slot_q, s)[row + i];
-    a.g[row + i] = pick2(a.slot_g, s)[row + i];
-    if (a.out.momentum) a.out.momentum[row + i] = pick2(a.slot_p, s)[row + i];
-  }
+  const double *sq = pick2(a.slot_q, s) + row, *sp = pick2(a.slot_p, s) + row, *sg = pick2(a.slot_g, s) + row;
+  double *const mom = a.out.momentum;
+  wave_pass<TailDepth<DEEP>::COPY>(a.D, lane,
+                     [&](long long i) { return Ld3{sq[i], sg[i], mom ? sp[i] : 0.0}; },
+                     [&](long long i, const Ld3 &x) {
+                       a.q[row + i] = x.a;
+                       a.g[row + i] = x.b;
+                       if (mom) mom[row + i] = x.c;
+                     });
   if (lane == 0) {
     a.U[c] = pick2(ct.U_slot, s);
     a.out.acceptance_probability[c] = ct.acc_prob;
@@ -482,31 +526,45 @@ __device__ inline void nuts_write_outputs(const EngineArgs &a, long long c, int 
 }
 
 // expand_once after integrate() returned: trajectory.py:537-608
-template <bool MET_DENSE>
-__device__ inline void nuts_finalize_expansion(const EngineArgs &a, long long c, int lane,
+template <bool MET_DENSE, bool HALF, bool DEEP>
+__device__ __forceinline__ void nuts_finalize_expansion(const EngineArgs &a, long long c, int lane,
                                                ChainCtl &ct, bool is_div, bool has_term,
                                                ChainRng &rng) {
   const size_t row = (size_t)c * a.D;
   const int dir = ct.dir, oth = 1 - dir;
-  // one pass: moving end <- cur, psum += psub, whole-trajectory U-turn dots (metrics.py:75-104)
+  const bool lin = MET_DENSE && a.linear;
+  // one pass: moving end <- cur, psum += psub, whole-trajectory U-turn dots (metrics.py:75-104).  The OTHER end's
+  // momentum and velocity rows (end_p[oth], end_v[oth]) are read while this end's (end_*[dir]) are written: the two
+  // ends are different arrays; psum is read and written at the element's own index.
+  const double *po_row = pick2(a.end_p, oth) + row;
+  const double *vo_row = MET_DENSE ? pick2(a.end_v, oth) + row : nullptr;
+  double *eq = pick2(a.end_q, dir) + row, *ep = pick2(a.end_p, dir) + row, *eg = pick2(a.end_g, dir) + row;
+  double *ev = MET_DENSE ? pick2(a.end_v, dir) + row : nullptr;
+  double *ew = lin ? pick2(a.end_w, dir) + row : nullptr;
   double d_l = 0.0, d_r = 0.0;
-  for (long long i = lane; i < a.D; i += 64) {
-    double pc = a.cur_p[row + i], po = pick2(a.end_p, oth)[row + i];
-    double vc = MET_DENSE ? a.cur_v[row + i] : vel_diag(a, c, i, pc);
-    double vo = MET_DENSE ? pick2(a.end_v, oth)[row + i] : vel_diag(a, c, i, po);
-    double s = a.psum[row + i] + a.psub[row + i];
-    a.psum[row + i] = s;
-    double pl = dir ? po : pc, pr = dir ? pc : po;
-    double vl = dir ? vo : vc, vr = dir ? vc : vo;
-    double rho = s - (pr + pl) / 2;
-    d_l += vl * rho;
-    d_r += vr * rho;
-    pick2(a.end_q, dir)[row + i] = a.cur_q[row + i];
-    pick2(a.end_p, dir)[row + i] = pc;
-    pick2(a.end_g, dir)[row + i] = a.cur_g[row + i];
-    if (MET_DENSE) pick2(a.end_v, dir)[row + i] = vc;
-    if (MET_DENSE && a.linear) pick2(a.end_w, dir)[row + i] = a.cur_w[row + i];
-  }
+  wave_pass<TailDepth<DEEP>::BATCH>(a.D, lane,
+            [&](long long i) {
+              return Ld9{a.cur_p[row + i], po_row[i], MET_DENSE ? a.cur_v[row + i] : 0.0, MET_DENSE ? vo_row[i] : 0.0,
+                         a.psum[row + i], a.psub[row + i], a.cur_q[row + i], a.cur_g[row + i],
+                         lin ? a.cur_w[row + i] : 0.0};
+            },
+            [&](long long i, const Ld9 &x) {
+              double pc = x.a, po = x.b;
+              double vc = MET_DENSE ? x.c : vel_diag(a, c, i, pc);
+              double vo = MET_DENSE ? x.d : vel_diag(a, c, i, po);
+              double s = x.e + x.f;
+              a.psum[row + i] = s;
+              double pl = dir ? po : pc, pr = dir ? pc : po;
+              double vl = dir ? vo : vc, vr = dir ? vc : vo;
+              double rho = s - (pr + pl) / 2;
+              d_l += vl * rho;
+              d_r += vr * rho;
+              eq[i] = x.g;
+              ep[i] = pc;
+              eg[i] = x.h;
+              if (MET_DENSE) ev[i] = vc;
+              if (lin) ew[i] = x.i;
+            });
   d_l = wave_sum(d_l);
   d_r = wave_sum(d_r);
   const bool turning = (d_l <= 0) | (d_r <= 0);
@@ -516,11 +574,11 @@ __device__ inline void nuts_finalize_expansion(const EngineArgs &a, long long c,
   if (tree_merge_expansion<true>(ct, is_div, has_term, lane, [&](double pr) { return rng_bernoulli(rng.g[3], pr); }))
     ct.prop_slot ^= 1;
   if (tree_expansion_outcome(ct, is_div, has_term, turning, a.max_exp)) {
-    nuts_write_outputs(a, c, lane, ct);
+    nuts_write_outputs<DEEP>(a, c, lane, ct);
     ct.done = 1;  // caller keeps the chain alive while a phantom scan is pending
   } else {
     ct.j += 1;
-    nuts_begin_expansion<MET_DENSE>(a, c, lane, ct, dir, rng);
+    nuts_begin_expansion<MET_DENSE, HALF, DEEP>(a, c, lane, ct, dir, rng);
   }
 }
 
@@ -533,7 +591,7 @@ __device__ inline void nuts_finalize_expansion(const EngineArgs &a, long long c,
 // one trip to memory per step instead of three dependent ones.  Every lane adds the same terms in
 // the same order as the separate passes: identical bits.
 template <bool MET_DENSE, int FUSE = 0>
-__device__ inline void nuts_book(const EngineArgs &a, long long c, int lane, ChainCtl &ct,
+__device__ __forceinline__ void nuts_book(const EngineArgs &a, long long c, int lane, ChainCtl &ct,
                                  ChainRng &rng) {
   const size_t row = (size_t)c * a.D;
   const int step = ct.step;
@@ -548,6 +606,12 @@ __device__ inline void nuts_book(const EngineArgs &a, long long c, int lane, Cha
   double f_dl = 0.0, f_dr = 0.0;  // FUSE3: U-turn dots of level tmax (odd steps)
   constexpr bool FUSE3 = FUSE == 1;
   const bool f_turn = FUSE != 0 && step >= 1 && tmax >= tmin;
+  // Step 0 of a sub-trajectory always makes the new point its proposal (tree_sample_step), which is known before any
+  // memory is touched: the passes that hold q', p' and g' in registers (FUSE 2, 3, 4) write the proposal slot themselves.
+  constexpr bool SLOT0 = FUSE >= 2;
+  const bool f_slot = SLOT0 && step == 0;
+  double *sq0 = pick2(a.slot_q, ct.prop_slot ^ 1) + row, *sp0 = pick2(a.slot_p, ct.prop_slot ^ 1) + row;
+  double *sg0 = pick2(a.slot_g, ct.prop_slot ^ 1) + row;
   if (FUSE == 2) {
     const double step_size = (ct.dir ? 1.0 : -1.0) * (a.eps_c ? a.eps_c[c] : a.eps);
     const double b = 0.5 * step_size, aa = 1 * step_size;
@@ -573,6 +637,11 @@ __device__ inline void nuts_book(const EngineArgs &a, long long c, int lane, Cha
                 kd += v * p;
                 const double s2 = (step == 0) ? p : x.d + p;
                 a.psub[row + i] = s2;
+                if (f_slot) {                                   // copy_cur_to_slot
+                  sq0[i] = q;
+                  sp0[i] = p;
+                  sg0[i] = gnew;
+                }
                 if (even) {
                   ckp[i] = p;
                   cks[i] = s2;
@@ -614,6 +683,11 @@ __device__ inline void nuts_book(const EngineArgs &a, long long c, int lane, Cha
                 kd += v * p;
                 const double s = (step == 0) ? p : x.d + p;
                 a.psub[row + i] = s;
+                if (f_slot) {                           // copy_cur_to_slot (z' = r: the same bits)
+                  sq0[i] = x.b;
+                  sp0[i] = p;
+                  sg0[i] = x.a;
+                }
                 if (even) {
                   ckp[i] = p;
                   cks[i] = s;
@@ -695,50 +769,78 @@ __device__ inline void nuts_book(const EngineArgs &a, long long c, int lane, Cha
   const bool div = np.div;
   bool term = false;
   if (tree_sample_step<true>(ct, step, np, lane, [&](double pr) { return rng_bernoulli(rng.g[2], pr); })) {
-    copy_cur_to_slot<MET_DENSE>(a, row, lane, ct.prop_slot ^ 1);  // sub-trajectory proposal <- the new point
+    if (!f_slot) copy_cur_to_slot<MET_DENSE, FUSE != 0>(a, row, lane, ct.prop_slot ^ 1);  // sub-trajectory proposal <- the new point
     put2(ct.U_slot, ct.prop_slot ^ 1, ct.U_cur);
   }
   if (step >= 1) {
-    // is_iterative_turning termination.py:133-187
+    // is_iterative_turning termination.py:133-187: levels tmax ... tmin, stop at the first that turns.  The levels are
+    // known before any memory is touched, so up to TURN_LV of them share ONE sweep: cur_p, psub (cur_v) are read once,
+    // every level's checkpoint rows beside them, one (d_l, d_r) pair per level summed as a pass of its own would.  Levels
+    // below one that turns are read for nothing (valid rows: the reference reads them when the upper level does not turn).
     if (tmax >= tmin) {
+      constexpr int TURN_LV = TailDepth<FUSE != 0>::TURN_LV;
       int idx = tmax;
       bool crit = false;
-      for (;;) {
-        const double *kp = a.ckp + ((size_t)idx * a.C + c) * a.D;
-        const double *ks = a.cks + ((size_t)idx * a.C + c) * a.D;
-        const double *kv = MET_DENSE ? a.ckv + ((size_t)idx * a.C + c) * a.D : nullptr;
-        double d_l = 0.0, d_r = 0.0;
-        if (FUSE != 0 && idx == tmax) {
-          d_l = f_dl;
-          d_r = f_dr;
-        } else
-        wave_pass(a.D, lane,
-                  [&](long long i) {
-                    return Ld6{kp[i], a.cur_p[row + i], MET_DENSE ? kv[i] : 0.0, MET_DENSE ? a.cur_v[row + i] : 0.0,
-                               a.psub[row + i], ks[i]};
-                  },
-                  [&](long long i, const Ld6 &x) {
-                    double pl = x.a, pr = x.b;
-                    double vl = MET_DENSE ? x.c : vel_diag(a, c, i, pl);
-                    double vr = MET_DENSE ? x.d : vel_diag(a, c, i, pr);
-                    double sub = x.e - x.f + pl;
-                    double rho = sub - (pr + pl) / 2;
-                    d_l += vl * rho;
-                    d_r += vr * rho;
-                  });
-        d_l = wave_sum(d_l);
-        d_r = wave_sum(d_r);
+      if (FUSE != 0) {  // level tmax came with the main pass
+        const double d_l = wave_sum(f_dl), d_r = wave_sum(f_dr);
         crit = (d_l <= 0) | (d_r <= 0);
-        bool reached = (idx - 1) < tmin;
         idx -= 1;
-        if (crit || reached) break;
+      }
+      while (!crit && idx >= tmin) {
+        const int n = (idx - tmin + 1 < TURN_LV) ? idx - tmin + 1 : TURN_LV;  // levels idx, idx - 1, ..., idx - n + 1
+        const double *kp[TURN_LV], *ks[TURN_LV], *kv[TURN_LV];
+        double d_l[TURN_LV], d_r[TURN_LV];
+#pragma unroll
+        for (int k = 0; k < TURN_LV; k++) {
+          const size_t lv = (size_t)(k < n ? idx - k : idx);
+          kp[k] = a.ckp + (lv * a.C + c) * a.D;
+          ks[k] = a.cks + (lv * a.C + c) * a.D;
+          kv[k] = MET_DENSE ? a.ckv + (lv * a.C + c) * a.D : nullptr;
+          d_l[k] = d_r[k] = 0.0;
+        }
+        wave_pass<2>(a.D, lane,
+                     [&](long long i) {
+                       TurnLd<TURN_LV> x;
+                       x.p = a.cur_p[row + i];
+                       x.v = MET_DENSE ? a.cur_v[row + i] : 0.0;
+                       x.s = a.psub[row + i];
+#pragma unroll
+                       for (int k = 0; k < TURN_LV; k++) {
+                         x.kp[k] = k < n ? kp[k][i] : 0.0;
+                         x.ks[k] = k < n ? ks[k][i] : 0.0;
+                         x.kv[k] = (MET_DENSE && k < n) ? kv[k][i] : 0.0;
+                       }
+                       return x;
+                     },
+                     [&](long long i, const TurnLd<TURN_LV> &x) {
+                       const double pr = x.p;
+                       const double vr = MET_DENSE ? x.v : vel_diag(a, c, i, pr);
+#pragma unroll
+                       for (int k = 0; k < TURN_LV; k++) {
+                         if (k < n) {
+                           double pl = x.kp[k];
+                           double vl = MET_DENSE ? x.kv[k] : vel_diag(a, c, i, pl);
+                           double sub = x.s - x.ks[k] + pl;
+                           double rho = sub - (pr + pl) / 2;
+                           d_l[k] += vl * rho;
+                           d_r[k] += vr * rho;
+                         }
+                       }
+                     });
+#pragma unroll
+        for (int k = 0; k < TURN_LV; k++)
+          if (k < n && !crit) {
+            const double sl = wave_sum(d_l[k]), sr = wave_sum(d_r[k]);
+            crit = (sl <= 0) | (sr <= 0);
+          }
+        idx -= n;
       }
       term = crit;
     }
   }
   const TreeControl tc = tree_step_control(ct, step, div, term);
   if (tc.finalize) {
-    nuts_finalize_expansion<MET_DENSE>(a, c, lane, ct, tc.fin_div, tc.fin_term, rng);
+    nuts_finalize_expansion<MET_DENSE, FUSE == 4, FUSE != 0>(a, c, lane, ct, tc.fin_div, tc.fin_term, rng);
     if (step == 0) {
       // trajectory.py:336: integrate() returns the first-step tuple, yet the scan still
       // executes (and draws from site #3): finalized now, the chain keeps stepping as a phantom.
@@ -752,30 +854,37 @@ __device__ inline void nuts_book(const EngineArgs &a, long long c, int lane, Cha
 // nuts.py:113-125 after the momentum is in cur_p (and cur_v for a dense metric)
 // U_in (optional): the chain's potential energy from a register instead of a.U[c] (kernels that run several
 // transitions per launch keep it there)
-template <bool MET_DENSE>
-__device__ inline void nuts_init_chain(const EngineArgs &a, long long c, int lane, ChainCtl &ct,
+template <bool MET_DENSE, int UN = 0>
+__device__ __forceinline__ void nuts_init_chain(const EngineArgs &a, long long c, int lane, ChainCtl &ct,
                                        ChainRng &rng, const double *U_in = nullptr) {
   const size_t row = (size_t)c * a.D;
   double kd = 0.0;
-  for (long long i = lane; i < a.D; i += 64) {
-    double q = a.q[row + i], g = a.g[row + i], p = a.cur_p[row + i];
-    double v = MET_DENSE ? a.cur_v[row + i] : vel_diag(a, c, i, p);
-    kd += v * p;
-    a.cur_q[row + i] = q;
-    a.cur_g[row + i] = g;
+  const bool lin = MET_DENSE && a.linear;
+  // sources: the state (q, g) and the momentum rows (cur_p, cur_v, cur_w), none of which is written here
+  wave_pass<UN>(a.D, lane,
+            [&](long long i) {
+              return Ld5{a.q[row + i], a.g[row + i], a.cur_p[row + i], MET_DENSE ? a.cur_v[row + i] : 0.0,
+                         lin ? a.cur_w[row + i] : 0.0};
+            },
+            [&](long long i, const Ld5 &x) {
+              const double q = x.a, g = x.b, p = x.c;
+              const double v = MET_DENSE ? x.d : vel_diag(a, c, i, p);
+              kd += v * p;
+              a.cur_q[row + i] = q;
+              a.cur_g[row + i] = g;
 #pragma unroll
-    for (int e = 0; e < 2; e++) {
-      a.end_q[e][row + i] = q;
-      a.end_p[e][row + i] = p;
-      a.end_g[e][row + i] = g;
-      if (MET_DENSE) a.end_v[e][row + i] = v;
-      if (MET_DENSE && a.linear) a.end_w[e][row + i] = a.cur_w[row + i];
-    }
-    a.slot_q[0][row + i] = q;
-    a.slot_p[0][row + i] = p;
-    a.slot_g[0][row + i] = g;
-    a.psum[row + i] = p;
-  }
+              for (int e = 0; e < 2; e++) {
+                a.end_q[e][row + i] = q;
+                a.end_p[e][row + i] = p;
+                a.end_g[e][row + i] = g;
+                if (MET_DENSE) a.end_v[e][row + i] = v;
+                if (lin) a.end_w[e][row + i] = x.e;
+              }
+              a.slot_q[0][row + i] = q;
+              a.slot_p[0][row + i] = p;
+              a.slot_g[0][row + i] = g;
+              a.psum[row + i] = p;
+            });
   kd = wave_sum(kd);
   const double U = U_in ? *U_in : a.U[c];
   ct.H0 = U + 0.5 * kd;
@@ -839,7 +948,7 @@ AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_nuts_begin_diag(EngineAr
   ChainRng rng = rng_load(a, c);
   ChainCtl ct;
   draw_momentum<false>(a, c, lane, rng.g[0]);
-  nuts_init_chain<false>(a, c, lane, ct, rng);
+  nuts_init_chain<false, 4>(a, c, lane, ct, rng);
   rng_store(a, c, lane, rng, 0, 1);
   if (lane == 0) a.ctl[c] = ct;
 }
@@ -1066,19 +1175,14 @@ AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_white_half_step(EngineAr
 // k_step_white with the next half step formed inside the bookkeeping pass (nuts_book FUSE = 4).  That work stands unless
 // the chain is done (its rows are never read again) or its direction changed -- exactly when nuts_begin_expansion has
 // rewritten the cur_* rows; the phantom continuation after a finalised step 0 follows the same rule.  A live chain that
-// turned round forms the half step from its new rows.
+// turned round forms the half step in that very copy pass (nuts_begin_expansion HALF), from the values it moves.
 AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_step_white_ahead(EngineArgs a) {
   AEHMC_CHAIN_OF_WAVE();
   ChainCtl ct = a.ctl[c];
   if (ct.done) return;
   ChainRng rng = rng_load(a, c);
-  const int dir = ct.dir;
   nuts_book<false, 4>(a, c, lane, ct, rng);
   rng_store(a, c, lane, rng, 1, 3);
-  if (!ct.done && ct.dir != dir) {
-    __threadfence_block();
-    white_half_step(a, c, lane, ct.dir);
-  }
   if (lane == 0) a.ctl[c] = ct;
 }
 
