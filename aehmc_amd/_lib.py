@@ -89,7 +89,8 @@ SYMBOLS = {
     "aehmc_summary_quantiles": (_I, [_P, _I64, _I64, _I64, _P, ct.POINTER(_D), _P, _P, _I64, _P]),
     "aehmc_summary_sketch_update": (_I, [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
     "aehmc_summary_sketch_quantiles": (_I, [_P, _I64, _I64, _I64, ct.POINTER(_D), _P, _P, _P, _P, _P, _P]),
-    "aehmc_summary_rank_work": (_I64, [_I64, _I64]),
+    "aehmc_constrain": (_I, [_P, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "aehmc_summary_rank_work":(_I64, [_I64, _I64]),
     "aehmc_summary_rank": (_I, [_P, _I64, _I64, _P, _P, _I, _P, _P, _I64, _P]),
     "aehmc_summary_hdi": (_I, [_P, _I64, _I64, _P, _D, _P, _P, _P, _P, _I64, _P]),
     "aehmc_summary_quantile_mcse": (_I, [_P, _I64, _I64, _I64, _P, ct.POINTER(_D), _P, _P, _P, _P, _I64, _P]),

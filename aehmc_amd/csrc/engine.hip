@@ -1346,6 +1346,21 @@ extern "C" int aehmc_summary_sketch_quantiles(aehmc_ctx *ctx, int64_t D, int64_t
   return 0;
 }
 
+// Constrained draws (constrain.cuh): x [R, D_in] into y [R, D_out] through the per-output table; out of place.
+extern "C" int aehmc_constrain(aehmc_ctx *ctx, int64_t R, int64_t D_in, int64_t D_out, const double *x,
+                               const aehmc_constrain_entry *table, double *y, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (R < 1 || D_in < 1 || D_out < 1 || !x || !table || !y) FAIL("constrain: bad arguments");
+  if (D_in >= (int64_t)1 << 31 || D_out >= (int64_t)1 << 31) FAIL("constrain: D_in and D_out must be below 2^31");
+  if (R > INT64_MAX / 8 / D_in || R > INT64_MAX / 8 / D_out) FAIL("constrain: R is too large");
+  const uintptr_t xb = (uintptr_t)x, yb = (uintptr_t)y;
+  const uintptr_t xe = xb + (uintptr_t)(R * D_in * 8), ye = yb + (uintptr_t)(R * D_out * 8);
+  if (xb < ye && yb < xe) FAIL("constrain: x and y overlap; the map is out of place");
+  HIPCHK(tu::constrain(x, R, D_in, D_out, table, y, (hipStream_t)stream));
+  return 0;
+}
+
 // Average ranks and normal scores of the stored draws (rank.cuh): the same conventions.  The scratch decides the tile:
 // as many coordinates as it holds are sorted at a time, and the result does not depend on how many that is.
 extern "C" int64_t aehmc_summary_rank_work(int64_t R, int64_t D) {

@@ -68,6 +68,9 @@ hipError_t sketch_update(const double *x, long long R, long long D, int B, const
 hipError_t sketch_quantiles(const unsigned long long *counts, const double *lo, const double *width, long long D, int B,
                             int Q, int U, const long long *ranks, const int *lo_row, const int *hi_row, const double *g,
                             double *estimate, int *resolved, hipStream_t st);
+// constrain.cuh (x [R][D_in] into y [R][D_out], disjoint; table: D_out entries of 40 bytes on the device)
+hipError_t constrain(const double *x, long long R, long long D_in, long long D_out, const void *table, double *y,
+                     hipStream_t st);
 // rank.cuh (a tile of T coordinates needs rank_work_bytes(R, T) of scratch; rank_tile_width: the widest tile that
 // `bytes` hold, 0 if none; rank_default_tile: what fits under 256 MiB, at least 1)
 size_t rank_work_bytes(long long R, long long T);

@@ -881,6 +881,32 @@ class Engine:
                     "aehmc_summary_sketch_quantiles")
         return est, res
 
+    def constrain(self, x, table, d_out, out=None):
+        """y [R, d_out]: the rows of x [R, D_in] (fp64, contiguous) mapped through ``table``, the per-output entries
+        of csrc/constrain.cuh as a uint8 device tensor of 40 * d_out bytes (``transforms.Model`` builds it).  Out of
+        place: ``out``, if given, is [R, d_out], fp64, contiguous and shares no memory with x."""
+        R, D_in = x.shape
+        d_out = int(d_out)
+        if x.dtype != torch.float64 or not x.is_contiguous() or x.device != self.device:
+            raise ValueError(f"constrain: x must be a contiguous float64 tensor on {self.device}")
+        if table.dtype != torch.uint8 or table.numel() != 40 * d_out or table.device != self.device or \
+                not table.is_contiguous():
+            raise ValueError(f"constrain: the table must hold {d_out} entries of 40 bytes on {self.device}")
+        if out is None:
+            out = torch.empty(R, d_out, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or tuple(out.shape) != (R, d_out) or not out.is_contiguous() or \
+                out.device != self.device:
+            raise ValueError(f"constrain: out must be a contiguous float64 tensor [{R}, {d_out}] on {self.device}")
+        if R == 0:
+            return out
+        lo, hi = x.data_ptr(), x.data_ptr() + 8 * x.numel()
+        if out.data_ptr() < hi and lo < out.data_ptr() + 8 * out.numel():
+            raise ValueError("constrain: out overlaps the input; the map is out of place")
+        self._check(self.lib.aehmc_constrain(self.ctx, R, D_in, d_out, x.data_ptr(), table.data_ptr(), out.data_ptr(),
+                                             self.stream),
+                    "aehmc_constrain")
+        return out
+
     def summary_rank(self, samples, center, mode, _work_bytes=None):
         """out [R, D]: the average rank (mode 0) or the normal score (mode 1) of every draw of samples [R, D] among the
         draws of its coordinate; with center [D], of the folded draws |samples - center|.  ``_work_bytes``: scratch

@@ -819,7 +819,8 @@ class QuantileSketch:
 
 
 def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_integration_steps=None,
-        chunk: Optional[int] = None, max_lag: Optional[int] = None, sketch: Optional[QuantileSketch] = None):
+        chunk: Optional[int] = None, max_lag: Optional[int] = None, sketch: Optional[QuantileSketch] = None,
+        constrain=None):
     """Sample ``num_samples`` transitions per chain and summarise them without keeping them: ``kernel.sample`` is
     driven in chunks of ``chunk`` draws into one reused buffer and every chunk is folded into an ``Accumulator``.
     Returns ``(Summary, Diagnostics of the last transition, acceptance history, divergence history)`` -- what
@@ -834,6 +835,11 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
     ``sketch``: a ``QuantileSketch`` of the run's chains and position shape; every chunk is folded into it too, so that
     median and intervals are there when the run ends (``sketch.quantiles`` / ``interval`` / ``resolved``).  What is
     returned does not change.
+
+    ``constrain``: a ``transforms.Model`` of the position's length; every chunk is mapped to the constrained scale
+    (``aehmc_constrain``, one pass into a second reused buffer) before it is folded, so the Summary and the sketch are
+    those of the model's parameters, shaped ``(model.constrained_dim,)`` -- the mean of sigma, not of log sigma.  The
+    two buffers together stay under ``CHUNK_BYTES``; the chain state that is returned stays unconstrained.
 
     An HMC kernel needs ``num_integration_steps`` (as in ``window_adaptation.run``): an int, or one length per
     transition (a sequence of ``num_samples`` entries, as ``kernel.sample`` takes it -- the jittered lengths of
@@ -856,14 +862,22 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
     N = int(num_samples)
     if chunk is not None and int(chunk) < 1:
         raise ValueError("chunk must be at least 1")
-    acc = Accumulator(N, C, shape, max_lag=max_lag)
+    D_in = shape[0] if shape else 1
+    if constrain is not None:
+        if not (hasattr(constrain, "_constrain_rows") and hasattr(constrain, "constrained_dim")):
+            raise ValueError(f"constrain must be a transforms.Model, got {type(constrain).__name__}")
+        if constrain.dim != D_in:
+            raise ValueError(f"constrain maps positions of {constrain.dim} coordinates, the chains have {D_in}")
+    oshape = shape if constrain is None else (int(constrain.constrained_dim),)
+    acc = Accumulator(N, C, oshape, max_lag=max_lag)
     if sketch is not None and not (isinstance(sketch, QuantileSketch) and sketch.num_chains == C
                                    and sketch.shape == acc.shape):
         raise ValueError(f"sketch must be a QuantileSketch of {C} chains and shape {acc.shape}")
-    per_draw = C * acc.D * 8
+    per_draw = C * (D_in if constrain is None else D_in + acc.D) * 8
     chunk = min(N, int(chunk) if chunk is not None else max(1, CHUNK_BYTES // per_draw))
     dev = acc._eng.device
-    buf = torch.empty(chunk * C * acc.D, dtype=torch.float64, device=dev)
+    buf = torch.empty(chunk * C * D_in, dtype=torch.float64, device=dev)
+    cbuf = None if constrain is None else torch.empty(chunk * C * acc.D, dtype=torch.float64, device=dev)
     acc_hist = div_hist = info = total = None
     done = 0
     while done < N:
@@ -871,9 +885,12 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
         if lengths is not None:
             extra = (lengths[done:done + T],)
         samples, info, a, d = kernel.sample(state, step_size, inverse_mass_matrix, *extra, T, into=buf)
-        acc.update(samples.reshape((T, C) + shape))
+        if constrain is not None:
+            samples = constrain._constrain_rows(acc._eng, samples.reshape(T * C, D_in),
+                                                cbuf[:T * C * acc.D].view(T * C, acc.D))
+        acc.update(samples.reshape((T, C) + oshape))
         if sketch is not None:
-            sketch.update(samples.reshape((T, C) + shape))
+            sketch.update(samples.reshape((T, C) + oshape))
         if acc_hist is None:
             acc_hist = torch.empty((N,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
             div_hist = torch.empty((N,) + tuple(d.shape[1:]), dtype=d.dtype, device=d.device)

@@ -662,6 +662,43 @@ int aehmc_summary_sketch_quantiles(aehmc_ctx *ctx, int64_t D, int64_t B, int64_t
                                    const int64_t *counts, const double *lo, const double *width, double *estimate,
                                    int32_t *resolved, void *stream);
 
+/* ---- constrained draws from unconstrained positions (aehmc_amd/transforms.py) ----
+ * The samplers move in R^D_in; a model's parameters are scales, probabilities, ordered cut-points, mixture weights.
+ * `constrain` maps x [R, D_in] to y [R, D_out] (fp64, device) in one pass, OUT OF PLACE: the byte ranges of x and y must
+ * not overlap (refused otherwise).  D_out = D_in + the number of simplex segments.  1 <= R, 1 <= D_in, D_out < 2^31.
+ *
+ * table: D_out entries of 40 bytes each (the struct below) on the DEVICE, one per OUTPUT coordinate, built once per
+ * model: kind; pos and len, the entry's position in its segment and the segment's length in output coordinates (0 and 1
+ * for a coordinate-wise kind; ORDERED of n: j and n; SIMPLEX of K: j and K, fed by K - 1 inputs; len <=
+ * AEHMC_CONSTRAIN_MAX_LEN); first, the index of the segment's first INPUT coordinate (a coordinate-wise kind: the
+ * entry's own input); lo and hi, the bounds (0 where unused); reserved = 0.  An entry whose segment does not lie
+ * inside the row, or of an unknown kind, writes NaN and reads nothing.
+ *
+ * Formulas, every operation rounded on its own, in this order:
+ *   REAL      y = x
+ *   LOWER     y = lo + exp(x)
+ *   UPPER     y = hi - exp(x)
+ *   INTERVAL  s = 1 / (1 + exp(-x)) where x >= 0, else e / (1 + e) with e = exp(x);  y = lo + (hi - lo) s;
+ *             y = hi where s == 1 or y > hi
+ *   ORDERED   t = x_0;  t = t + exp(x_j) for j = 1 ... pos, ascending;  y = t
+ *   SIMPLEX   xt = (x_0 ... x_{K-2}, 0);  m = the largest xt_j (m = xt_0, replaced where xt_j > m, j ascending);
+ *             L = m + log(sum_j exp(xt_j - m)), the sum ascending in j;  y = exp(xt_pos - L)
+ * NaN in gives NaN out.  INTERVAL gives exactly lo and exactly hi for large |x|, never a NaN from a finite x.  exp
+ * overflow gives +inf in LOWER and ORDERED, -inf in UPPER.  A SIMPLEX with +inf among its inputs gives NaN (inf - inf),
+ * with -inf a weight of 0.  One thread computes one output from its inputs alone: the result depends neither on the
+ * launch geometry nor on how the rows are cut into calls.  All buffers are the caller's; the call touches neither the
+ * workspace, nor the target, nor the metric. */
+#define AEHMC_CONSTRAIN_MAX_LEN 64
+enum { AEHMC_CONSTRAIN_REAL = 0, AEHMC_CONSTRAIN_LOWER = 1, AEHMC_CONSTRAIN_UPPER = 2, AEHMC_CONSTRAIN_INTERVAL = 3,
+       AEHMC_CONSTRAIN_ORDERED = 4, AEHMC_CONSTRAIN_SIMPLEX = 5 };
+typedef struct aehmc_constrain_entry {
+  int32_t kind, pos, len, reserved;
+  int64_t first;
+  double lo, hi;
+} aehmc_constrain_entry;
+int aehmc_constrain(aehmc_ctx *ctx, int64_t R, int64_t D_in, int64_t D_out, const double *x,
+                    const aehmc_constrain_entry *table, double *y, void *stream);
+
 /* ---- average ranks and normal scores of the stored draws (aehmc_amd/summary.py) ----
  * What the rank-normalised split R-hat and the bulk ESS (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021) are
  * computed from: samples [R, D] as above, out [R, D].  mode 0: out = the average rank of every draw among the R draws
