@@ -90,6 +90,12 @@ SYMBOLS = {
     "aehmc_summary_sketch_update": (_I, [_P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
     "aehmc_summary_sketch_quantiles": (_I, [_P, _I64, _I64, _I64, ct.POINTER(_D), _P, _P, _P, _P, _P, _P]),
     "aehmc_constrain": (_I, [_P, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "aehmc_set_pointwise": (_I, [_P, ct.c_char_p, _I64, _I64, ct.c_int32, ct.POINTER(_P), ct.c_int32, ct.c_char_p]),
+    "aehmc_pointwise_eval": (_I, [_P, _I64, _P, _P, _P]),
+    "aehmc_pointwise_waic_fold": (_I, [_P, _I64, _P, _P, _I64, _P]),
+    "aehmc_waic_fold": (_I, [_P, _I64, _I64, _P, _P, _I64, _P]),
+    "aehmc_waic_merge": (_I, [_P, _I64, _P, _I64, _P, _I64, _P]),
+    "aehmc_waic_final": (_I, [_P, _I64, _P, _I64, _P, _P, _P]),
     "aehmc_summary_rank_work":(_I64, [_I64, _I64]),
     "aehmc_summary_rank": (_I, [_P, _I64, _I64, _P, _P, _I, _P, _P, _I64, _P]),
     "aehmc_summary_hdi": (_I, [_P, _I64, _I64, _P, _D, _P, _P, _P, _P, _I64, _P]),

@@ -33,6 +33,7 @@
 #include "chees.cuh"
 #include "ghmc_fused.cuh"
 #include "meads.cuh"
+#include "pointwise.cuh"
 
 using namespace aehmc;
 
@@ -51,12 +52,13 @@ constexpr size_t PROF_POOL = 8192;
 // one instantiation per program, named by the launch.  A new run-time compiled route registers here, and builds the
 // name of its instantiation beside the plan in its family header (KernelLaunch, engine.cuh).
 enum RtcProg { RTC_BASE, RTC_GLM, RTC_JBASE, RTC_JTWG, RTC_JWG, RTC_NUTS, RTC_JNUTS, RTC_WIDE, RTC_JWIDE, RTC_BLOCK, RTC_HMC,
-               RTC_JHMCF, RTC_JHMC, RTC_GLMK, RTC_GHMC, RTC_JGHMC };
+               RTC_JHMCF, RTC_JHMC, RTC_GLMK, RTC_GHMC, RTC_JGHMC, RTC_PW };
 struct RtcRow {
   const char *mode;                  // "AEHMC_CUSTOM_TARGET" (engine.cuh: target_elem calls aehmc_custom_elem), "AEHMC_JOINT_TARGET"
                                      // (leap_small_dense calls aehmc_logp through dual.cuh), or none: the GLM kernels
   std::vector<const char *> headers;
   std::vector<std::string> names;    // (a launch asks for one of them by the name written here: rtc_function fails otherwise)
+  bool engine = true;                // engine.cuh ahead of the family headers (not for a pointwise program: no target in it)
 };
 static const RtcRow RTC_TABLE[] = {
     // RTC_BASE: the lock-step engine's target-dependent kernels (+ new_state): what LAUNCH_T can ask for
@@ -82,8 +84,11 @@ static const RtcRow RTC_TABLE[] = {
     /* RTC_GLMK */ {nullptr, {"glm_rows.cuh"}, {}},  // (one instantiation of the one-launch GLM kernels)
     /* RTC_GHMC */ {"AEHMC_CUSTOM_TARGET", {"ghmc_fused.cuh"}, {}},
     /* RTC_JGHMC */ {"AEHMC_JOINT_TARGET", {"ghmc_fused.cuh"}, {}},
+    // RTC_PW: a pointwise program (pointwise.cuh: k_pointwise<FOLD, STAGE>), compiled against the POINTWISE binding -- never
+    // the target's; one instantiation per program
+    {"AEHMC_POINTWISE_TARGET", {"pointwise.cuh"}, {}, false},
 };
-static_assert(sizeof(RTC_TABLE) / sizeof(RTC_TABLE[0]) == RTC_JGHMC + 1, "one row per RtcProg, in its order");
+static_assert(sizeof(RTC_TABLE) / sizeof(RTC_TABLE[0]) == RTC_PW + 1, "one row per RtcProg, in its order");
 static const std::string &RTC_JWG_NUTS = RTC_TABLE[RTC_JWG].names[0], &RTC_JWG_HMC = RTC_TABLE[RTC_JWG].names[1];  // (nuts_run / hmc_run spell no template arguments)
 // a program and the wavefronts per SIMD its workgroup-per-chain kernels are compiled for (AEHMC_WG_MIN_WAVES 3 / 4:
 // RTC_GLMK and RTC_JWG, see wg_program; 0: not defined)
@@ -193,6 +198,13 @@ struct aehmc_ctx {
   double *blk_pack = nullptr;  // block-resident dense kernels: the launch's matrices zero-padded to [Dp][Dp] (kept, grown)
   size_t blk_pack_bytes = 0;
   CustomBinding bound;  // the user-defined target (aehmc_set_custom_target and its kin)
+  // the pointwise program (aehmc_set_pointwise): a binding of its own -- summary.run samples with the target while it
+  // folds --, what it said about itself, and the parts of a fold [parts][4][n_out] (kept, grown)
+  CustomBinding pw;
+  int64_t pw_D = 0, pw_n_out = 0;
+  int pw_n_head = 0;
+  double *pw_work = nullptr;
+  size_t pw_work_bytes = 0;
   std::string rtc_cache_dir;  // compiled code objects of user-defined targets, kept across processes (aehmc_set_rtc_cache)
   int64_t rtc_compiled = 0, rtc_loaded = 0;  // programs compiled by hipRTC / taken from rtc_cache_dir (aehmc_rtc_stats)
   // user-defined row-reduction target: data matrix X [N,D], its transpose (owned), responses, [C,N] / [C] work arrays (owned)
@@ -364,6 +376,8 @@ extern "C" int aehmc_destroy(aehmc_ctx *ctx) {
   if (ctx->glm_lsum) (void)hipFree(ctx->glm_lsum);
   white_release(ctx);
   custom_release(ctx->bound);
+  custom_release(ctx->pw);
+  if (ctx->pw_work) (void)hipFree(ctx->pw_work);
   for (int i = 0; i < NRING; i++)
     if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
   for (auto e : ctx->prof_ev) (void)hipEventDestroy(e);
@@ -479,21 +493,23 @@ extern "C" int aehmc_rtc_stats(const aehmc_ctx *ctx, int64_t *compiled, int64_t 
   return 0;
 }
 
-static int rtc_function(aehmc_ctx *ctx, RtcId id, const std::string &want, hipFunction_t *out) {
+// `b`: the binding whose source the program is compiled against and which keeps the code object (the target's, or the
+// pointwise program's)
+static int rtc_function(aehmc_ctx *ctx, CustomBinding &b, RtcId id, const std::string &want, hipFunction_t *out) {
   const RtcRow &row = RTC_TABLE[id.prog];
   const bool one = row.names.empty();  // one instantiation per program
   const std::tuple<int, int, std::string> key(id.prog, id.waves, one ? want : std::string());
-  auto it = ctx->bound.rtc.find(key);
-  if (it == ctx->bound.rtc.end()) {
+  auto it = b.rtc.find(key);
+  if (it == b.rtc.end()) {
     const std::vector<std::string> names = one ? std::vector<std::string>{want} : row.names;
-    if (ctx->bound.src.empty()) FAIL("internal: no user-defined target source");
+    if (b.src.empty()) FAIL("internal: no user-defined source");
     std::string src = RTC_PROLOGUE;
     if (id.waves) src += "#define AEHMC_WG_MIN_WAVES " + std::to_string(id.waves) + "\n";
     if (row.mode) src += std::string("#define ") + row.mode + " 1\n";
-    src += "#line 1 \"custom_target\"\n" + ctx->bound.src + "\n";
-    src += "#include \"engine.cuh\"\n";
+    src += "#line 1 \"custom_target\"\n" + b.src + "\n";
+    if (row.engine) src += "#include \"engine.cuh\"\n";
     for (const char *h : row.headers) src += std::string("#include \"") + h + "\"\n";
-    const std::string inc = "-I" + ctx->bound.inc;
+    const std::string inc = "-I" + b.inc;
     const char *opts[] = {"--offload-arch=" AEHMC_GPU_ARCH, "-O3", "-std=c++17", "-ffp-contract=off", inc.c_str(),
                           "-mllvm", "-disable-machine-licm"};  // (the flags of csrc/Makefile)
     std::vector<char> code;
@@ -557,7 +573,7 @@ static int rtc_function(aehmc_ctx *ctx, RtcId id, const std::string &want, hipFu
       }
       rp.fn[names[k]] = f;
     }
-    it = ctx->bound.rtc.emplace(key, rp).first;
+    it = b.rtc.emplace(key, rp).first;
   }
   auto f = it->second.fn.find(want);
   if (f == it->second.fn.end()) FAIL("internal: kernel " + want + " was not compiled");
@@ -565,10 +581,10 @@ static int rtc_function(aehmc_ctx *ctx, RtcId id, const std::string &want, hipFu
   return 0;
 }
 template <class... Args>
-static int rtc_launch(aehmc_ctx *ctx, RtcId id, const std::string &want, dim3 grid, dim3 block, size_t dyn, hipStream_t st,
-                      Args... args) {
+static int rtc_launch_on(aehmc_ctx *ctx, CustomBinding &b, RtcId id, const std::string &want, dim3 grid, dim3 block, size_t dyn,
+                         hipStream_t st, Args... args) {
   hipFunction_t f = nullptr;
-  if (int rc = rtc_function(ctx, id, want, &f)) return rc;
+  if (int rc = rtc_function(ctx, b, id, want, &f)) return rc;
   void *params[] = {(void *)&args...};
   {  // a code object whose register count does not fit the workgroup aborts the PROCESS when it is launched
      // (HSA_STATUS_ERROR_INVALID_ISA): an error return instead
@@ -592,6 +608,11 @@ static int rtc_launch(aehmc_ctx *ctx, RtcId id, const std::string &want, dim3 gr
   HIPCHK(hipModuleLaunchKernel(f, grid.x, grid.y, grid.z, block.x, block.y, block.z, (unsigned)dyn, st, params, nullptr));
   return 0;
 }
+template <class... Args>  // (against the bound target)
+static int rtc_launch(aehmc_ctx *ctx, RtcId id, const std::string &want, dim3 grid, dim3 block, size_t dyn, hipStream_t st,
+                      Args... args) {
+  return rtc_launch_on(ctx, ctx->bound, id, want, grid, block, dyn, st, args...);
+}
 template <class... Args>  // (a launch as its family header describes it)
 static int rtc_launch(aehmc_ctx *ctx, RtcId id, const KernelLaunch &k, hipStream_t st, Args... args) {
   return rtc_launch(ctx, id, k.name, k.grid, k.block, k.dyn, st, args...);
@@ -611,7 +632,7 @@ static int wg_program(aehmc_ctx *ctx, RtcProg prog, const std::string &want, int
   auto it = ctx->bound.wg_choice.find({prog, want});
   if (it == ctx->bound.wg_choice.end()) {
     hipFunction_t f = nullptr;
-    if (int rc = rtc_function(ctx, {prog, 4}, want, &f)) return rc;
+    if (int rc = rtc_function(ctx, ctx->bound, {prog, 4}, want, &f)) return rc;
     int scratch = 0;
     (void)hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, f);
     it = ctx->bound.wg_choice.emplace(std::make_pair((int)prog, want), scratch > WG_SCRATCH_MAX ? 3 : 4).first;
@@ -641,9 +662,10 @@ static CustomBinding custom_source(const char *source, const char *include_dir) 
   nb.sweep_terms = nb.has_sweep ? atoll(nb.src.c_str() + at + sizeof(sweep_key) - 1) : 0;
   return nb;
 }
-// installs `nb` (custom_source) with `params` in the ctx and compiles program `prog`; on failure the previous binding is
-// back in place
-static int custom_bind(aehmc_ctx *ctx, CustomBinding nb, const double *const *params, int32_t n_params, RtcProg prog) {
+// installs `nb` (custom_source) with `params` in `slot` (the ctx's target binding or its pointwise binding) and compiles
+// kernel `want` of program `prog`; on failure the previous binding is back in place.  The other slot is never touched
+static int custom_bind(aehmc_ctx *ctx, CustomBinding &slot, CustomBinding nb, const double *const *params, int32_t n_params,
+                       RtcProg prog, const std::string &want) {
   if (n_params < 0 || (n_params > 0 && !params)) FAIL("custom target: bad parameter list");
   nb.n_cparams = n_params;
   HIPCHK(hipMalloc((void **)&nb.d_cparams, (size_t)(n_params > 0 ? n_params : 1) * sizeof(double *)));
@@ -653,18 +675,18 @@ static int custom_bind(aehmc_ctx *ctx, CustomBinding nb, const double *const *pa
     FAIL("custom target: parameter table upload failed");
   }
   // the same function: its code objects and wg_program's picks among them stay
-  const bool same_source = ctx->bound.src == nb.src && ctx->bound.inc == nb.inc;
+  const bool same_source = slot.src == nb.src && slot.inc == nb.inc;
   const auto keep_programs = [&] {
     if (!same_source) return;
-    std::swap(nb.rtc, ctx->bound.rtc);
-    std::swap(nb.wg_choice, ctx->bound.wg_choice);
+    std::swap(nb.rtc, slot.rtc);
+    std::swap(nb.wg_choice, slot.wg_choice);
   };
   keep_programs();
-  std::swap(ctx->bound, nb);  // ctx: new binding; nb: the previous one
+  std::swap(slot, nb);  // ctx: new binding; nb: the previous one
   hipFunction_t f = nullptr;  // compile now: errors in the user's source surface here, not in the first step
-  if (int rc = rtc_function(ctx, prog, RTC_TABLE[prog].names[0], &f)) {
+  if (int rc = rtc_function(ctx, slot, prog, want, &f)) {
     const std::string err = ctx->err;
-    std::swap(ctx->bound, nb);  // ctx: the previous binding again; nb: the failed one
+    std::swap(slot, nb);  // ctx: the previous binding again; nb: the failed one
     keep_programs();
     custom_release(nb);
     ctx->err = err;
@@ -691,7 +713,7 @@ extern "C" int aehmc_set_custom_glm_target(aehmc_ctx *ctx, const char *source, i
   if (D <= 0 || N <= 0 || !X || !y) FAIL("GLM target needs D, N, X [N,D] and y [N]");
   double *XT = nullptr;  // (allocated before anything is replaced)
   HIPCHK(hipMalloc((void **)&XT, (size_t)N * D * sizeof(double)));
-  if (int rc = custom_bind(ctx, custom_source(source, include_dir), params, n_params, RTC_GLM)) {
+  if (int rc = custom_bind(ctx, ctx->bound, custom_source(source, include_dir), params, n_params, RTC_GLM, RTC_TABLE[RTC_GLM].names[0])) {
     (void)hipFree(XT);
     return rc;
   }
@@ -728,7 +750,7 @@ template <class... Args>
 static int joint_rows_launch(aehmc_ctx *ctx, RtcProg prog, const std::string &want, int64_t row, dim3 grid, dim3 block,
                              hipStream_t st, Args... args) {
   hipFunction_t f = nullptr;
-  if (int rc = rtc_function(ctx, prog, want, &f)) return rc;
+  if (int rc = rtc_function(ctx, ctx->bound, prog, want, &f)) return rc;
   int stat = 0;
   if (hipFuncGetAttribute(&stat, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, f) != hipSuccess || stat < 0)
     FAIL("joint target: the static LDS size of the compiled kernel could not be read");
@@ -750,7 +772,8 @@ extern "C" int aehmc_set_custom_joint_target(aehmc_ctx *ctx, const char *source,
   if (D <= 0 || D > dmax)
     FAIL("joint target: D must be in [1, " + std::to_string(dmax) + "]" +
          (grad ? std::string() : " without a reverse-mode program (AEHMC_JOINT_GRAD: up to " + std::to_string(JOINT_WIDE_MAX_D) + ")"));
-  if (int rc = custom_bind(ctx, std::move(nb), params, n_params, D > JOINT_ROWS_MAX_D ? RTC_JTWG : RTC_JBASE)) return rc;
+  const RtcProg prog = D > JOINT_ROWS_MAX_D ? RTC_JTWG : RTC_JBASE;
+  if (int rc = custom_bind(ctx, ctx->bound, std::move(nb), params, n_params, prog, RTC_TABLE[prog].names[0])) return rc;
   return custom_target(ctx, AEHMC_T_JOINT, D);
 }
 
@@ -759,7 +782,7 @@ extern "C" int aehmc_set_custom_target(aehmc_ctx *ctx, const char *source, int64
   if (!ctx || !source || !include_dir) return -2;
   HIPCHK(hipSetDevice(ctx->device));
   if (D <= 0) FAIL("target: D must be positive");
-  if (int rc = custom_bind(ctx, custom_source(source, include_dir), params, n_params, RTC_BASE)) return rc;
+  if (int rc = custom_bind(ctx, ctx->bound, custom_source(source, include_dir), params, n_params, RTC_BASE, RTC_TABLE[RTC_BASE].names[0])) return rc;
   return custom_target(ctx, AEHMC_T_CUSTOM, D);
 }
 
@@ -1358,6 +1381,96 @@ extern "C" int aehmc_constrain(aehmc_ctx *ctx, int64_t R, int64_t D_in, int64_t 
   const uintptr_t xe = xb + (uintptr_t)(R * D_in * 8), ye = yb + (uintptr_t)(R * D_out * 8);
   if (xb < ye && yb < xe) FAIL("constrain: x and y overlap; the map is out of place");
   HIPCHK(tu::constrain(x, R, D_in, D_out, table, y, (hipStream_t)stream));
+  return 0;
+}
+
+// ------------------------------------------------------------------ pointwise programs and streaming WAIC (pointwise.cuh)
+static std::string pw_kernel(bool fold, bool stage) {
+  return std::string("aehmc::k_pointwise<") + (fold ? "true" : "false") + ", " + (stage ? "true" : "false") + ">";
+}
+// Binds a pointwise program (tracing.trace_pointwise) BESIDE the target: a transaction like aehmc_set_custom_target -- a
+// failed compile leaves the previous pointwise binding in place -- that never touches the target's binding.
+extern "C" int aehmc_set_pointwise(aehmc_ctx *ctx, const char *source, int64_t D, int64_t n_out, int32_t n_head,
+                                   const double *const *params, int32_t n_params, const char *include_dir) {
+  if (!ctx || !source || !include_dir) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (D < 1 || D > JOINT_WIDE_MAX_D) FAIL("pointwise: D must be in [1, " + std::to_string(JOINT_WIDE_MAX_D) + "]");
+  if (n_out < 1 || (n_out + PW_TILE - 1) / PW_TILE > 65535) FAIL("pointwise: n_out must be in [1, " + std::to_string(65535LL * PW_TILE) + "]");
+  if (n_head < 0) FAIL("pointwise: n_head must not be negative");
+  const PwPlan plan = pw_plan(D, n_head);
+  if (plan.batch < 1) FAIL("pointwise: " + std::to_string(n_head) + " head values per row do not fit in LDS");
+  if (int rc = custom_bind(ctx, ctx->pw, custom_source(source, include_dir), params, n_params, RTC_PW, pw_kernel(false, plan.stage)))
+    return rc;
+  ctx->pw_D = D; ctx->pw_n_out = n_out; ctx->pw_n_head = n_head;
+  return 0;
+}
+static int pw_launch(aehmc_ctx *ctx, bool fold, int64_t R, const double *x, double *out, hipStream_t st) {
+  const PwPlan plan = pw_plan(ctx->pw_D, ctx->pw_n_head);
+  PwArgs a{};
+  a.x = x; a.out = out; a.prm = ctx->pw.d_cparams;
+  a.R = R; a.D = ctx->pw_D; a.n_out = ctx->pw_n_out; a.n_head = ctx->pw_n_head; a.batch = plan.batch;
+  const dim3 grid((unsigned)pw_parts(R), (unsigned)((ctx->pw_n_out + PW_TILE - 1) / PW_TILE));
+  return rtc_launch_on(ctx, ctx->pw, RTC_PW, pw_kernel(fold, plan.stage), grid, dim3(PW_TILE), plan.lds, st, a);
+}
+static int pw_check_rows(aehmc_ctx *ctx, const char *what, int64_t R, int64_t width) {
+  if (R < 1 || pw_parts(R) > 2147483647LL) FAIL(std::string(what) + ": R must be in [1, " + std::to_string(2147483647LL * PW_PART) + "]");
+  if (R > INT64_MAX / 8 / width) FAIL(std::string(what) + ": R is too large");
+  return 0;
+}
+extern "C" int aehmc_pointwise_eval(aehmc_ctx *ctx, int64_t R, const double *x, double *out, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (ctx->pw.src.empty()) FAIL("pointwise_eval: no pointwise program is bound (aehmc_set_pointwise)");
+  if (!x || !out) FAIL("pointwise_eval: bad arguments");
+  if (int rc = pw_check_rows(ctx, "pointwise_eval", R, std::max(ctx->pw_D, ctx->pw_n_out))) return rc;
+  return pw_launch(ctx, false, R, x, out, (hipStream_t)stream);
+}
+static int waic_state_check(aehmc_ctx *ctx, const char *what, const double *state, int64_t n_state) {
+  if (!state || n_state < 0) FAIL(std::string(what) + ": bad state");
+  if (n_state >= (int64_t)1 << 53) FAIL(std::string(what) + ": the draw count must stay below 2^53");
+  return 0;
+}
+extern "C" int aehmc_pointwise_waic_fold(aehmc_ctx *ctx, int64_t R, const double *x, double *state, int64_t n_state,
+                                         void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (ctx->pw.src.empty()) FAIL("pointwise_waic_fold: no pointwise program is bound (aehmc_set_pointwise)");
+  if (!x) FAIL("pointwise_waic_fold: bad arguments");
+  if (int rc = waic_state_check(ctx, "pointwise_waic_fold", state, n_state)) return rc;
+  if (int rc = pw_check_rows(ctx, "pointwise_waic_fold", R, std::max(ctx->pw_D, 4 * ctx->pw_n_out))) return rc;
+  if (int rc = grow(ctx, &ctx->pw_work, &ctx->pw_work_bytes, pw_work_doubles(R, ctx->pw_n_out) * sizeof(double))) return rc;
+  if (int rc = pw_launch(ctx, true, R, x, ctx->pw_work, (hipStream_t)stream)) return rc;
+  HIPCHK(tu::waic_merge(ctx->pw_work, pw_parts(R), PW_PART, R, state, (double)n_state, ctx->pw_n_out, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int aehmc_waic_fold(aehmc_ctx *ctx, int64_t R, int64_t n_obs, const double *x, double *state, int64_t n_state,
+                               void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!x || n_obs < 1 || (n_obs + PW_TILE - 1) / PW_TILE > 65535) FAIL("waic_fold: bad arguments (1 <= n_obs <= " + std::to_string(65535LL * PW_TILE) + ")");
+  if (int rc = waic_state_check(ctx, "waic_fold", state, n_state)) return rc;
+  if (int rc = pw_check_rows(ctx, "waic_fold", R, 4 * n_obs)) return rc;
+  if (int rc = grow(ctx, &ctx->pw_work, &ctx->pw_work_bytes, pw_work_doubles(R, n_obs) * sizeof(double))) return rc;
+  HIPCHK(tu::waic_fold_stored(x, R, n_obs, ctx->pw_work, (hipStream_t)stream));
+  HIPCHK(tu::waic_merge(ctx->pw_work, pw_parts(R), PW_PART, R, state, (double)n_state, n_obs, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int aehmc_waic_merge(aehmc_ctx *ctx, int64_t n_obs, double *state, int64_t n_state, const double *other,
+                                int64_t n_other, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (n_obs < 1 || !other || n_other < 1 || other == state) FAIL("waic_merge: bad arguments");
+  if (int rc = waic_state_check(ctx, "waic_merge", state, n_state)) return rc;
+  if (n_other >= (int64_t)1 << 53) FAIL("waic_merge: the draw count must stay below 2^53");
+  HIPCHK(tu::waic_merge(other, 1, n_other, n_other, state, (double)n_state, n_obs, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int aehmc_waic_final(aehmc_ctx *ctx, int64_t n_obs, const double *state, int64_t n_state, double *lppd,
+                                double *p, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (n_obs < 1 || !state || n_state < 1 || !lppd || !p) FAIL("waic_final: bad arguments (at least one draw)");
+  HIPCHK(tu::waic_final(state, (double)n_state, n_obs, lppd, p, (hipStream_t)stream));
   return 0;
 }
 

@@ -71,6 +71,11 @@ hipError_t sketch_quantiles(const unsigned long long *counts, const double *lo, 
 // constrain.cuh (x [R][D_in] into y [R][D_out], disjoint; table: D_out entries of 40 bytes on the device)
 hipError_t constrain(const double *x, long long R, long long D_in, long long D_out, const void *table, double *y,
                      hipStream_t st);
+// pointwise.cuh (ws: the parts of a fold [parts][4][n_obs]; state [4][n_obs] behind n_state draws)
+hipError_t waic_fold_stored(const double *x, long long R, long long n_obs, double *ws, hipStream_t st);
+hipError_t waic_merge(const double *ws, long long parts, long long part_rows, long long R, double *state, double n_state,
+                      long long n_obs, hipStream_t st);
+hipError_t waic_final(const double *state, double n_state, long long n_obs, double *lppd, double *p, hipStream_t st);
 // rank.cuh (a tile of T coordinates needs rank_work_bytes(R, T) of scratch; rank_tile_width: the widest tile that
 // `bytes` hold, 0 if none; rank_default_tile: what fits under 256 MiB, at least 1)
 size_t rank_work_bytes(long long R, long long T);

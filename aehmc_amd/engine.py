@@ -907,6 +907,71 @@ class Engine:
                     "aehmc_constrain")
         return out
 
+    # ------------------------------------------------------------------ pointwise programs, streaming WAIC
+    def set_pointwise(self, owner, traced):
+        """Bind the pointwise program ``traced`` (``tracing.TracedPointwise``) of ``owner`` beside the target; a no-op
+        while ``owner`` is the one bound.  A source that does not compile raises and leaves the previous program (and the
+        arrays it reads) in place; the sampler's target is never touched."""
+        if self._keep.get("pointwise", (None,))[0] is owner:
+            return
+        import os
+        arrs = [_dev_f64(a, self.device) for a in traced.params]
+        ptrs = (ct.c_void_p * max(len(arrs), 1))(*[a.data_ptr() for a in arrs])
+        inc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
+        src = '#include "dual.cuh"\n' + traced.source
+        self._check(self.lib.aehmc_set_pointwise(self.ctx, src.encode(), int(traced.dim), int(traced.n_out),
+                                                 int(traced.n_head), ptrs, len(arrs), inc.encode()), "aehmc_set_pointwise")
+        self._keep["pointwise"] = (owner, traced, arrs)
+
+    def _rows_f64(self, x, what, width=None):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or not x.is_contiguous() or x.device != self.device \
+                or x.ndim != 2 or (width is not None and x.shape[1] != width):
+            raise ValueError(f"{what} must be a contiguous float64 tensor [R, {width if width is not None else 'n'}] on "
+                             f"{self.device}")
+
+    def pointwise_eval(self, x, out):
+        """out [R, n_out] = the bound pointwise program on the rows x [R, D]."""
+        _, traced, _ = self._keep["pointwise"]
+        self._rows_f64(x, "pointwise_eval: x", traced.dim)
+        self._rows_f64(out, "pointwise_eval: out", traced.n_out)
+        if out.shape[0] != x.shape[0]:
+            raise ValueError("pointwise_eval: x and out differ in their rows")
+        if x.shape[0]:
+            self._check(self.lib.aehmc_pointwise_eval(self.ctx, x.shape[0], x.data_ptr(), out.data_ptr(), self.stream),
+                        "aehmc_pointwise_eval")
+        return out
+
+    def pointwise_waic_fold(self, x, state, n_state):
+        """Fold the bound program's values of the rows x [R, D] into the WAIC state [4, n_out] behind n_state draws."""
+        _, traced, _ = self._keep["pointwise"]
+        self._rows_f64(x, "pointwise_waic_fold: x", traced.dim)
+        self._rows_f64(state, "pointwise_waic_fold: state", traced.n_out)
+        if x.shape[0]:
+            self._check(self.lib.aehmc_pointwise_waic_fold(self.ctx, x.shape[0], x.data_ptr(), state.data_ptr(),
+                                                           int(n_state), self.stream), "aehmc_pointwise_waic_fold")
+
+    def waic_fold(self, x, state, n_state):
+        """Fold the stored block x [R, n_obs] into the WAIC state [4, n_obs] behind n_state draws."""
+        self._rows_f64(state, "waic_fold: state")
+        self._rows_f64(x, "waic_fold: x", state.shape[1])
+        if x.shape[0]:
+            self._check(self.lib.aehmc_waic_fold(self.ctx, x.shape[0], x.shape[1], x.data_ptr(), state.data_ptr(),
+                                                 int(n_state), self.stream), "aehmc_waic_fold")
+
+    def waic_merge(self, state, n_state, other, n_other):
+        self._rows_f64(state, "waic_merge: state")
+        self._rows_f64(other, "waic_merge: other", state.shape[1])
+        self._check(self.lib.aehmc_waic_merge(self.ctx, state.shape[1], state.data_ptr(), int(n_state), other.data_ptr(),
+                                              int(n_other), self.stream), "aehmc_waic_merge")
+
+    def waic_final(self, state, n_state):
+        """(lppd [n_obs], p [n_obs]) of the WAIC state behind n_state >= 1 draws."""
+        self._rows_f64(state, "waic_final: state")
+        lppd, p = (torch.empty(state.shape[1], dtype=torch.float64, device=self.device) for _ in range(2))
+        self._check(self.lib.aehmc_waic_final(self.ctx, state.shape[1], state.data_ptr(), int(n_state), lppd.data_ptr(),
+                                              p.data_ptr(), self.stream), "aehmc_waic_final")
+        return lppd, p
+
     def summary_rank(self, samples, center, mode, _work_bytes=None):
         """out [R, D]: the average rank (mode 0) or the normal score (mode 1) of every draw of samples [R, D] among the
         draws of its coordinate; with center [D], of the folded draws |samples - center|.  ``_work_bytes``: scratch

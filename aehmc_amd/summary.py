@@ -36,7 +36,9 @@ that a beta quantile of the coordinate's own ESS gives; csrc/posterior.cuh), ``m
 And for comparing models, from the pointwise log-likelihood of the stored draws (one observation is one "coordinate"):
 ``psislw`` (Pareto-smoothed importance weights and the Pareto shape k per observation, csrc/psis.cuh, again on the
 sorted columns), ``loo`` (PSIS-LOO: the weights are used where they are formed and never stored), ``relative_eff`` and
-``waic``.
+``waic``.  The array itself comes from the model: ``Pointwise`` (``transforms.Model.pointwise``) is a traced vector
+function of the position, evaluated by one kernel (csrc/pointwise.cuh), and ``WaicAccumulator`` folds it -- or stored
+blocks -- into WAIC without the array ever existing; ``run(..., waic=acc)`` does so while it samples.
 
 Without the stored draws: ``QuantileSketch``, a fixed-grid histogram per coordinate that ``run`` can feed next to its
 ``Accumulator`` (csrc/sketch.cuh) -- ``quantiles``, ``median`` and ``interval`` of the pooled draws to within one bin
@@ -658,6 +660,133 @@ def waic(log_lik, *, batched: bool = True) -> WaicResult:
                       lppd_i=lppd_i.reshape(shape))
 
 
+# csrc/pointwise.cuh: PW_PART -- a WAIC fold cuts its rows into parts of this many; blocks of rows that are multiples of it
+# fold to the bits of one call
+WAIC_PART = 256
+
+
+class Pointwise:
+    """A vector function of one chain's position, ``fn(q, *args)`` -> ``n_out`` entries (a pointwise log-likelihood: one
+    entry per observation), traced once (``tracing.trace_pointwise``: what a traced ``logprob_fn`` may do, with a vector
+    result) and compiled with hipRTC on first use.  ``pw(samples)``: a contiguous float64 device tensor [..., dim] ->
+    [..., n_out], one kernel that writes nothing but its result (csrc/pointwise.cuh).  ``transforms.Model.pointwise``
+    builds one on the constrained scale of a model."""
+
+    def __init__(self, fn, dim, args=(), *, _model=None):
+        from . import tracing
+        self.dim = int(dim)
+        self._model = _model
+        if _model is not None and _model.dim != self.dim:
+            raise ValueError(f"the model has {_model.dim} coordinates, not {self.dim}")
+        self._traced = tracing.trace_pointwise(fn, self.dim if _model is None else _model.constrained_dim, args=args)
+        self.n_out = self._traced.n_out
+
+    def _check(self, samples, what):
+        _check_draws(samples, what)
+        if samples.ndim < 1 or samples.shape[-1] != self.dim:
+            raise ValueError(f"{what} must be [..., {self.dim}], got {tuple(samples.shape)}")
+        eng = get_engine()
+        _on_device(eng, samples)
+        return eng, samples.reshape(-1, self.dim)
+
+    def _block_rows(self):
+        """rows of a constrained block: under MODEL_BLOCK_BYTES, a multiple of WAIC_PART (the folds of consecutive blocks
+        are then the fold of all their rows, bit for bit)"""
+        return max(WAIC_PART, MODEL_BLOCK_BYTES // (8 * self._model.constrained_dim) // WAIC_PART * WAIC_PART)
+
+    def _blocks(self, eng, x, buf=None):
+        """(r0, r1, the rows the program reads) over x [R, dim]: x itself, or its constrained blocks in one reused buffer"""
+        R = x.shape[0]
+        if self._model is None:
+            yield 0, R, x
+            return
+        step, cd = self._block_rows(), self._model.constrained_dim
+        if buf is None:
+            buf = torch.empty(min(step, R) * cd, dtype=torch.float64, device=eng.device)
+        for r0 in range(0, R, step):
+            r1 = min(r0 + step, R)
+            yield r0, r1, self._model._constrain_rows(eng, x[r0:r1], buf[:(r1 - r0) * cd].view(r1 - r0, cd))
+
+    def __call__(self, samples):
+        eng, x = self._check(samples, "samples")
+        out = torch.empty(x.shape[0], self.n_out, dtype=torch.float64, device=eng.device)
+        eng.set_pointwise(self, self._traced)
+        for r0, r1, rows in self._blocks(eng, x):
+            eng.pointwise_eval(rows, out[r0:r1])
+        return out.reshape(tuple(samples.shape[:-1]) + (self.n_out,))
+
+    def _fold(self, eng, x, acc, constrained=None, buf=None):
+        """fold the rows x [R, dim] into ``acc``; ``constrained``: the same rows on the model's constrained scale, where
+        the caller has them already"""
+        eng.set_pointwise(self, self._traced)
+        for r0, r1, rows in ([(0, x.shape[0], constrained)] if constrained is not None else self._blocks(eng, x, buf)):
+            eng.pointwise_waic_fold(rows, acc.state, acc.n_samples)
+            acc.n_samples += r1 - r0
+
+
+class WaicAccumulator:
+    """Streaming WAIC: per observation a running log-sum-exp and a running variance of the pointwise log-likelihood, so
+    that a run whose log-likelihood array cannot be stored (4096 chains x 10^4 observations: 328 MB per draw) still gets
+    a model-comparison number.  ``WaicAccumulator(pw)`` with a ``Pointwise``: ``update(draws)`` folds positions
+    [T, C, dim] or [R, dim] through it without forming their log-likelihood.  ``WaicAccumulator(n_obs)``:
+    ``update_log_lik(x)`` folds stored blocks [..., n_obs] (it works on either).  ``result()``: the ``WaicResult`` of
+    ``waic`` on all folded draws, to rounding; ``n_samples``: how many there are.  ``state`` [4, n_obs] holds the running
+    maximum, sum of exp, mean and sum of squared deviations (csrc/pointwise.cuh has the arithmetic).  Rows are folded
+    in parts of ``WAIC_PART``, cut per call: equal calls give equal bits, another cut of the same draws the same result
+    to rounding.  PSIS-LOO does not stream: it needs every draw of an observation."""
+
+    def __init__(self, pw_or_n_obs):
+        if isinstance(pw_or_n_obs, Pointwise):
+            self.pointwise, self.n_obs = pw_or_n_obs, pw_or_n_obs.n_out
+        else:
+            try:
+                self.pointwise, self.n_obs = None, operator.index(pw_or_n_obs)
+            except TypeError:
+                raise ValueError(f"WaicAccumulator takes a Pointwise or a number of observations, got {pw_or_n_obs!r}") from None
+            if self.n_obs < 1:
+                raise ValueError("the number of observations must be positive")
+        self._eng = get_engine()
+        self.state = torch.zeros(4, self.n_obs, dtype=torch.float64, device=self._eng.device)
+        self.state[0] = -math.inf
+        self.n_samples = 0
+
+    def update(self, draws):
+        if self.pointwise is None:
+            raise ValueError("this accumulator was built from a number of observations: it folds stored blocks "
+                             "(update_log_lik); build it from a Pointwise to fold positions")
+        eng, x = self.pointwise._check(draws, "draws")
+        self.pointwise._fold(eng, x, self)
+        return self
+
+    def update_log_lik(self, x):
+        _check_draws(x, "x")
+        if x.ndim < 1 or x.shape[-1] != self.n_obs:
+            raise ValueError(f"x must be [..., {self.n_obs}], got {tuple(x.shape)}")
+        _on_device(self._eng, x)
+        rows = x.reshape(-1, self.n_obs)
+        self._eng.waic_fold(rows, self.state, self.n_samples)
+        self.n_samples += rows.shape[0]
+        return self
+
+    def merge(self, other):
+        """Add the draws of ``other`` BEHIND this accumulator's (ordered: as if ``other``'s draws had been one more
+        part of a fold)."""
+        if not isinstance(other, WaicAccumulator) or other.n_obs != self.n_obs or other is self:
+            raise ValueError(f"merge takes another WaicAccumulator of {self.n_obs} observations")
+        if other.n_samples:
+            self._eng.waic_merge(self.state, self.n_samples, other.state, other.n_samples)
+            self.n_samples += other.n_samples
+        return self
+
+    def result(self) -> WaicResult:
+        if self.n_samples < 1:
+            raise ValueError("no draw has been folded yet")
+        lppd_i, p_i = self._eng.waic_final(self.state, self.n_samples)
+        elpd_i = lppd_i - p_i
+        return WaicResult(elpd=elpd_i.sum().item(), se=math.sqrt(self.n_obs * torch.var(elpd_i, unbiased=False).item()),
+                          p=p_i.sum().item(), elpd_i=elpd_i, p_i=p_i, lppd_i=lppd_i)
+
+
 # aehmc_hip.h: AEHMC_SUMMARY_SKETCH_MIN_BINS / _MAX_BINS -- the grids of QuantileSketch (a power of two in between)
 MIN_SKETCH_BINS, MAX_SKETCH_BINS = 64, 4096
 
@@ -820,7 +949,7 @@ class QuantileSketch:
 
 def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_integration_steps=None,
         chunk: Optional[int] = None, max_lag: Optional[int] = None, sketch: Optional[QuantileSketch] = None,
-        constrain=None):
+        constrain=None, waic: Optional[WaicAccumulator] = None):
     """Sample ``num_samples`` transitions per chain and summarise them without keeping them: ``kernel.sample`` is
     driven in chunks of ``chunk`` draws into one reused buffer and every chunk is folded into an ``Accumulator``.
     Returns ``(Summary, Diagnostics of the last transition, acceptance history, divergence history)`` -- what
@@ -840,6 +969,12 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
     (``aehmc_constrain``, one pass into a second reused buffer) before it is folded, so the Summary and the sketch are
     those of the model's parameters, shaped ``(model.constrained_dim,)`` -- the mean of sigma, not of log sigma.  The
     two buffers together stay under ``CHUNK_BYTES``; the chain state that is returned stays unconstrained.
+
+    ``waic``: a ``WaicAccumulator`` built from a ``Pointwise`` of the position's length; every chunk's positions are
+    folded into it too (the log-likelihood is evaluated inside the fold and never stored), so ``waic.result()`` is there
+    when the run ends.  What is returned does not change.  A ``Pointwise`` of ``constrain``'s own model reads the
+    constrained buffer of the run; any other model-bound one maps into a buffer of its own, which counts towards
+    ``CHUNK_BYTES``.
 
     An HMC kernel needs ``num_integration_steps`` (as in ``window_adaptation.run``): an int, or one length per
     transition (a sequence of ``num_samples`` entries, as ``kernel.sample`` takes it -- the jittered lengths of
@@ -868,16 +1003,28 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
             raise ValueError(f"constrain must be a transforms.Model, got {type(constrain).__name__}")
         if constrain.dim != D_in:
             raise ValueError(f"constrain maps positions of {constrain.dim} coordinates, the chains have {D_in}")
+    if waic is not None:
+        if not isinstance(waic, WaicAccumulator) or waic.pointwise is None:
+            raise ValueError("waic must be a WaicAccumulator built from a Pointwise")
+        if waic.pointwise.dim != D_in:
+            raise ValueError(f"waic folds positions of {waic.pointwise.dim} coordinates, the chains have {D_in}")
     oshape = shape if constrain is None else (int(constrain.constrained_dim),)
     acc = Accumulator(N, C, oshape, max_lag=max_lag)
     if sketch is not None and not (isinstance(sketch, QuantileSketch) and sketch.num_chains == C
                                    and sketch.shape == acc.shape):
         raise ValueError(f"sketch must be a QuantileSketch of {C} chains and shape {acc.shape}")
     per_draw = C * (D_in if constrain is None else D_in + acc.D) * 8
+    wmodel = None if waic is None else waic.pointwise._model
+    own = wmodel is not None and wmodel is not constrain  # (the fold maps the rows itself, into a buffer of its own)
+    if own:
+        per_draw += C * wmodel.constrained_dim * 8
     chunk = min(N, int(chunk) if chunk is not None else max(1, CHUNK_BYTES // per_draw))
     dev = acc._eng.device
     buf = torch.empty(chunk * C * D_in, dtype=torch.float64, device=dev)
     cbuf = None if constrain is None else torch.empty(chunk * C * acc.D, dtype=torch.float64, device=dev)
+    wbuf = None
+    if own:
+        wbuf = torch.empty(min(chunk * C, waic.pointwise._block_rows()) * wmodel.constrained_dim, dtype=torch.float64, device=dev)
     acc_hist = div_hist = info = total = None
     done = 0
     while done < N:
@@ -885,9 +1032,12 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
         if lengths is not None:
             extra = (lengths[done:done + T],)
         samples, info, a, d = kernel.sample(state, step_size, inverse_mass_matrix, *extra, T, into=buf)
+        positions = samples.reshape(T * C, D_in)
         if constrain is not None:
-            samples = constrain._constrain_rows(acc._eng, samples.reshape(T * C, D_in),
-                                                cbuf[:T * C * acc.D].view(T * C, acc.D))
+            samples = constrain._constrain_rows(acc._eng, positions, cbuf[:T * C * acc.D].view(T * C, acc.D))
+        if waic is not None:
+            waic.pointwise._fold(acc._eng, positions, waic, samples if wmodel is not None and wmodel is constrain else None,
+                                 wbuf)
         acc.update(samples.reshape((T, C) + oshape))
         if sketch is not None:
             sketch.update(samples.reshape((T, C) + oshape))

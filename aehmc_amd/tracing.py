@@ -15,6 +15,9 @@ matrix), ``np.linalg.norm``, ``np.diff``, ``np.clip``, ``np.sign``, ``max`` / ``
 ``np.logaddexp.reduce``, ``.T`` / ``.reshape(-1)`` / ``.copy()`` of a vector; indexing and slicing with static bounds, gathers through a constant integer array (``theta[group]``);
 iteration over a vector.  Anything else -- Python ``if`` on a traced
 value, ``float()``, ``math.exp``, fancy indexing -- raises ``TypeError`` at trace time and says what it was.
+
+``trace_pointwise`` takes a function with a VECTOR result -- a model's pointwise log-likelihood, one entry per
+observation -- and emits it as plain functions of doubles for ``summary.Pointwise`` (csrc/pointwise.cuh).
 """
 from __future__ import annotations
 
@@ -23,7 +26,7 @@ import numbers
 
 import numpy as np
 
-__all__ = ["trace", "where", "softplus", "logsumexp", "TraceError"]
+__all__ = ["trace", "trace_pointwise", "where", "softplus", "logsumexp", "TraceError"]
 
 
 class TraceError(TypeError):
@@ -1466,3 +1469,93 @@ def trace(fn, dim, scalar=False, args=(), reverse="auto"):
         if reverse is True and "#define AEHMC_JOINT_GRAD_SMALL" not in tr.grad_source:
             tr.grad_source += "#define AEHMC_JOINT_GRAD_SMALL 1\n"
     return tr
+
+
+# ------------------------------------------------------------------------------------------------------ vector outputs
+class TracedPointwise:
+    """The result of ``trace_pointwise``: ``source`` (HIP source defining ``aehmc_pointwise_head`` and
+    ``aehmc_pointwise``), ``params`` (the captured arrays, in ``prm[k]`` order), ``dim``, ``n_out`` (entries of the
+    vector) and ``n_head`` (values per row that do not depend on the entry's index, computed once per row)."""
+
+    def __init__(self, source, params, dim, n_out, n_head):
+        self.source, self.params, self.dim, self.n_out, self.n_head = source, params, dim, n_out, n_head
+
+
+def _pointwise_entry(e, what):
+    if not isinstance(e, S):
+        raise TraceError(f"the pointwise function returned {what} that is a {type(e).__name__}: entries must be scalars")
+    if e.b:
+        raise TraceError("the pointwise function returned a comparison result")
+    return e
+
+
+def trace_pointwise(fn, dim, args=()):
+    """Call ``fn`` once on a proxy vector of ``dim`` entries, as ``trace`` does, and emit its VECTOR result (a pointwise
+    log-likelihood: one entry per observation) as two functions of plain doubles -- no derivative code:
+
+        template <class V> __device__ void aehmc_pointwise_head(const V &q, const double *const *prm, double *h);
+        template <class V> __device__ double aehmc_pointwise(const V &q, const double *h, long long j, const double *const *prm);
+
+    ``aehmc_pointwise`` is entry j from the row q and its ``n_head`` head values: the position-dependent sub-expressions
+    that do not read j (``log(sigma)``), which ``aehmc_pointwise_head`` computes once per row.  A vector built from a
+    Python list (at most 64 entries) is a ``switch (j)`` over its entries and has no head; a traced scalar is a vector
+    of one entry."""
+    dim = int(dim)
+    ctx = _Ctx()
+    arg = V(ctx, dim, lambda i: S(ctx, "q", (i,), True))
+    out = fn(arg, *[_lift(ctx, a) if isinstance(a, np.ndarray) else a for a in args])
+    if isinstance(out, (list, tuple)) or (isinstance(out, np.ndarray) and out.dtype == object and out.ndim == 1):
+        if len(out) > 64:
+            raise TraceError(f"the pointwise function returned a list of {len(out)} entries: a vector built from a Python list "
+                             "holds up to 64 (build long vectors from the position by slicing and arithmetic instead)")
+        out = _lift(ctx, list(out))
+    if isinstance(out, S):
+        _pointwise_entry(out, "a value")
+        if not out.t:
+            raise TraceError("the pointwise function returned a value that does not depend on the position")
+        out = V(ctx, 1, lambda i, e=out: e, unroll=True)
+    if not isinstance(out, V):
+        raise TraceError(f"the pointwise function returned a {type(out).__name__} that does not depend on the position")
+    if out.n < 1:
+        raise TraceError("the pointwise function returned an empty vector")
+    head = "template <class V> __device__ void aehmc_pointwise_head(const V &q, const double *const *prm, double *h) {\n  typedef double T;\n"
+    body = "template <class V> __device__ double aehmc_pointwise(const V &q, const double *h, long long j, const double *const *prm) {\n  typedef double T;\n"
+    if out.unroll:
+        if out.n > 64:
+            raise TraceError(f"the pointwise function returned a vector of {out.n} entries built from a Python list: up to 64 "
+                             "(build long vectors from the position by slicing and arithmetic instead)")
+        items = [_pointwise_entry(out.at(Idx(k)), f"entry {k}") for k in range(out.n)]
+        if not any(e.t for e in items):
+            raise TraceError("the pointwise function returned a value that does not depend on the position")
+        counter = [0]
+        cases = []
+        for k, e in enumerate(items):
+            g = _Gen()
+            g.ind = 3
+            tree = _hoist(e, counter)
+            g.count_uses(tree)
+            val = g.ex(tree)
+            pre = [" " * 4 + s for s in g.pre]  # (reductions over captured arrays alone: ahead of the case's statements)
+            cases.append(f"    case {k}: {{\n" + "".join(s + "\n" for s in pre + g.lines) + f"      return T({val});\n    }}\n")
+        src = (head + "}\n" + body + "  switch (j) {\n" + "".join(cases) + "    default: break;\n  }\n  return __builtin_nan(\"\");\n}\n")
+        return TracedPointwise(src, ctx.params, dim, out.n, 0)
+    v = ctx.new_var()
+    entry = _pointwise_entry(out.at(Idx.var(v)), "an entry")
+    if not entry.t:
+        raise TraceError("the pointwise function returned a value that does not depend on the position")
+    tree = _hoist(S(ctx, "sum", (v, out.n, entry), True), [0])  # (a sum over the entry's index: what it hoists is the head)
+    lets, entry = tree.args[3], tree.args[2]
+    gh = _Gen()
+    for _, x in lets:
+        gh.count_uses(x)
+    for slot, (k, x) in enumerate(lets):
+        gh.put(f"h[{slot}] = {gh.ex(x)};")
+    g = _Gen()
+    g.names[v] = "j"
+    for slot, (k, x) in enumerate(lets):
+        g.put(f"const double h{k} = h[{slot}];")
+    g.count_uses(entry)
+    val = g.ex(entry)
+    src = (head + "".join(s + "\n" for s in gh.pre + gh.lines) + "}\n"
+           + body + "".join(s + "\n" for s in g.pre + g.lines) + f"  return T({val});\n}}\n")
+    return TracedPointwise(src, ctx.params, dim, out.n, len(lets))

@@ -426,5 +426,19 @@ class Model:
                                  None if out is None else out.reshape(-1, self.constrained_dim))
         return y.reshape(want)
 
+    # ---------------------------------------------------------------------------------------------- vector functions
+    def pointwise(self, fn):
+        """``fn(**params)`` -- written on the constrained scale, with the names ``logprob`` takes -- as a
+        ``summary.Pointwise`` of the UNCONSTRAINED position (``dim`` is ``model.dim``): the model's pointwise
+        log-likelihood, for ``summary.loo`` / ``waic`` and ``summary.run(..., waic=)``.  It is traced as a function of the
+        constrained vector; when called, the rows go through ``constrain``'s kernel a block at a time, so no transform is
+        evaluated per observation and no full constrained copy is made."""
+        from .summary import Pointwise
+
+        def on_constrained(y):
+            return fn(**{k: y[self._out[k]] if t.shape else y[self._out[k].start] for k, t in self.spec.items()})
+
+        return Pointwise(on_constrained, self.dim, _model=self)
+
     def __repr__(self):
         return f"Model({', '.join(f'{k}: {t!r}' for k, t in self.spec.items())})"

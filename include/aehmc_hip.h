@@ -699,6 +699,52 @@ typedef struct aehmc_constrain_entry {
 int aehmc_constrain(aehmc_ctx *ctx, int64_t R, int64_t D_in, int64_t D_out, const double *x,
                     const aehmc_constrain_entry *table, double *y, void *stream);
 
+/* ---- pointwise log-likelihoods of traced models and streaming WAIC (aehmc_amd/summary.py) ----
+ * A POINTWISE PROGRAM is a vector function of one chain's position, one entry per observation, given as HIP source that
+ * defines (aehmc_amd/tracing.py: trace_pointwise writes it; `#include "dual.cuh"` first for softplus / logistic / square)
+ *   template <class V> __device__ void aehmc_pointwise_head
+ *       (const V &q, const double *const *prm, double *h);
+ *   template <class V> __device__ double aehmc_pointwise
+ *       (const V &q, const double *h, long long j, const double *const *prm);
+ * q[i] are the row's coordinates, prm the parameter arrays; the head writes the n_head values of a row that do not depend
+ * on j (n_head may be 0), and aehmc_pointwise returns entry j from the row and those values.
+ *
+ * set_pointwise compiles the source with hipRTC (the on-disk cache of aehmc_set_rtc_cache serves it too) and binds it
+ * BESIDE the target: the sampler's target, metric and workspace are not touched, so a run can sample with the target
+ * while it folds.  1 <= D <= 10176, 1 <= n_out <= 65535 * 256, 0 <= n_head <= 8192.  params: n_params device arrays (a
+ * host array of device pointers), owned by the caller and alive while the program is bound.  The call is a transaction: a
+ * source that does not compile returns an error, with the compiler's log in aehmc_last_error, and leaves the previously
+ * bound pointwise program in place.
+ *
+ * pointwise_eval: x [R, D] (fp64, device, contiguous) -> out [R, n_out], one kernel; out[r][j] depends on row r alone.
+ *
+ * WAIC state: [4][n_obs] doubles (device) -- per observation the running maximum m, s = sum exp(l - m), the mean and
+ * the sum of squared deviations M2 of the values folded so far -- and the number of draws behind it, n_state, which the
+ * CALLER keeps: 0 and (m, s, mean, M2) = (-inf, 0, 0, 0) to start, then n_state += R after every fold.
+ *   pointwise_waic_fold  folds the program's values of rows x [R, D] into `state` without storing them;
+ *   waic_fold            folds a stored block x [R, n_obs] (precompiled: needs no bound program);
+ *   waic_merge           adds `other` (n_other >= 1 draws, another state, not `state` itself) behind `state`;
+ *   waic_final           lppd[i] = m + log(s) - log(n_state), p[i] = M2 / (n_state - 1)  (n_state >= 1; [n_obs] each).
+ * A fold cuts its R rows into parts of 256 consecutive rows (the last one shorter), folds each part draw by draw in
+ * ascending order -- l > m: s = s exp(m - l) + 1, m = l, else s = s + exp(l - m); Welford's update for mean and M2 --
+ * and adds the parts in ascending order behind the state: max-rescaling for (m, s), the pairwise update of Chan, Golub &
+ * LeVeque (1983) for (mean, M2); csrc/pointwise.cuh states every operation.  The partition depends on R alone, never on
+ * the device; there are no atomics: equal calls give equal bits, and pointwise_waic_fold(x) gives the bits of
+ * waic_fold(pointwise_eval(x)).  How the draws are cut into calls changes the partition, so the result to rounding.
+ * A -inf value adds nothing to s and makes M2 (so p) NaN; a NaN makes the observation NaN; other observations are not
+ * affected.  The parts [ceil(R / 256)][4][n_obs] live in a buffer of the ctx that grows on demand (hipFree / hipMalloc
+ * inside the call when it grows: not during stream capture).  1 <= R <= 2^31 * 256 - 256, n_state < 2^53. */
+int aehmc_set_pointwise(aehmc_ctx *ctx, const char *source, int64_t D, int64_t n_out, int32_t n_head,
+                        const double *const *params, int32_t n_params, const char *include_dir);
+int aehmc_pointwise_eval(aehmc_ctx *ctx, int64_t R, const double *x, double *out, void *stream);
+int aehmc_pointwise_waic_fold(aehmc_ctx *ctx, int64_t R, const double *x, double *state, int64_t n_state, void *stream);
+int aehmc_waic_fold(aehmc_ctx *ctx, int64_t R, int64_t n_obs, const double *x, double *state, int64_t n_state,
+                    void *stream);
+int aehmc_waic_merge(aehmc_ctx *ctx, int64_t n_obs, double *state, int64_t n_state, const double *other,
+                     int64_t n_other, void *stream);
+int aehmc_waic_final(aehmc_ctx *ctx, int64_t n_obs, const double *state, int64_t n_state, double *lppd, double *p,
+                     void *stream);
+
 /* ---- average ranks and normal scores of the stored draws (aehmc_amd/summary.py) ----
  * What the rank-normalised split R-hat and the bulk ESS (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021) are
  * computed from: samples [R, D] as above, out [R, D].  mode 0: out = the average rank of every draw among the R draws
