@@ -930,7 +930,9 @@ def _private_leaves(e):
 def _mixed_owners(e):
     """Does a distributed loop write gradient entries through more than one index map a * i + c?  (x[1:] - x[:-1]: lane i
     owns entry i + 1 for one read and entry i for the other, which is lane i - 1's for the first.)  Then no lane owns an
-    entry and the additions are atomic."""
+    entry and the additions are atomic.  A gather anywhere in the body is an index map of its own (x[parent] - x: the
+    gather's atomic addition into entry j may land between the read and the write of the plain g[j] += of the lane that
+    owns j through the direct read, and is lost); gathers alone stay one map -- they are atomic already."""
     v = e.args[0]
     maps = set()
     seen = set()
@@ -941,7 +943,9 @@ def _mixed_owners(e):
         seen.add(id(x))
         if x.op == "q":
             t = x.args[0].terms
-            if not x.args[0].ind and len(t) == 1 and t[0][0] == v:
+            if x.args[0].ind:
+                maps.add("gather")
+            elif len(t) == 1 and t[0][0] == v:
                 maps.add((t[0][1], x.args[0].c))
         elif x.op == "sum":
             for _, h in x.args[3]:

@@ -571,3 +571,117 @@ def test_random_density_with_shared_reductions_three_ways_on_the_device():
     inside another reduction's body) at 150 coordinates: three passes over the lanes"""
     from test_tracing import random_shared_density
     three_way(random_shared_density(4, 150), 150, 4)
+
+
+# ---------------------------------------------------------------- a gather and a direct read of the position in one loop
+def gather_direct_density(D):
+    """x[parent] - x: every gradient entry is written through the gather (atomically) AND by the lane that owns it through
+    the direct read -- since a gather counts as an index map of its own (tracing._mixed_owners) atomically too"""
+    G = np.random.default_rng(D).integers(0, D, size=D)
+    return G, (lambda q: -0.5 * np.sum((q[G] - q) ** 2) - 0.5 * q @ q)
+
+
+@pytest.fixture(scope="module")
+def gather_direct_targets():
+    """one traced target per size for the module (each is a run-time compile per kernel family)"""
+    from aehmc_amd import targets
+    out = {}
+    for D in (65, 600, 2100):
+        G, fn = gather_direct_density(D)
+        out[D] = (G, targets.from_callable(fn, D, reverse=True), 0.5 * np.random.default_rng(D + 1).normal(size=(5, D)))
+        assert "AEHMC_ATOMIC_ADD(&g[i0]" in out[D][1].source and "g[i0] +=" not in out[D][1].source
+    return out
+
+
+def gather_direct_at_50_digits(G, q):
+    """U = 1/2 sum_i (q[G_i] - q_i)^2 + 1/2 sum_j q_j^2 and dU/dq_j = sum_{i: G_i = j} d_i - d_j + q_j, d_i = q[G_i] - q_i, with
+    mpmath at 50 digits on the doubles of `q`, and what a float64 program may be off by.  Entry j is a sum of m_j + 2
+    products (m_j = #{i: G_i = j} through the gather, the direct term, the prior), each with at most four roundings, so
+    |err_j| <= 2 (m_j + 6) u sum |terms_j|, u = 2^-53: m_j + 1 additions and four roundings per term, each relative to at
+    most the sum of the terms' magnitudes, and a factor 2 for the second-order terms and any order of the additions.  U
+    the same with its 2 D terms.  -> (U, g, allowance of U, allowance of g), the first two as mpmath numbers.
+    (Measured on an MI355X: the largest |err| / allowance is 0.13 - 0.16 on every route and size; the same closed form in
+    plain numpy float64 uses 0.16.)"""
+    import mpmath
+    D, u = len(q), 2.0 ** -53
+    with mpmath.workdps(50):
+        x = [mpmath.mpf(float(v)) for v in q]
+        d = [x[G[i]] - x[i] for i in range(D)]
+        U = mpmath.fsum(0.5 * v * v for v in d) + mpmath.fsum(0.5 * v * v for v in x)   # (every term positive: sum |terms| = U)
+        g = [x[j] - d[j] for j in range(D)]
+        mag = [abs(x[j]) + abs(d[j]) for j in range(D)]
+        for i in range(D):
+            g[G[i]] += d[i]
+            mag[G[i]] += abs(d[i])
+        m = np.bincount(G, minlength=D)
+        return U, g, 2 * (2 * D + 4) * u * float(U), np.array([2 * (int(m[j]) + 6) * u * float(mag[j]) for j in range(D)])
+
+
+def gather_direct_worst(G, state):
+    """the largest |error| / allowance of U and of the gradient entries over the chains of `state`"""
+    import mpmath
+    q, U, g = (t.cpu().numpy() for t in (state.position, state.potential_energy, state.potential_energy_grad))
+    worst = 0.0
+    for c in range(q.shape[0]):
+        U50, g50, bU, bg = gather_direct_at_50_digits(G, q[c])
+        with mpmath.workdps(50):
+            eU = float(abs(mpmath.mpf(float(U[c])) - U50)) / bU
+            eg = max(float(abs(mpmath.mpf(float(g[c, j])) - g50[j])) / bg[j] for j in range(q.shape[1]))
+        worst = max(worst, eU, eg)
+    return worst
+
+
+@pytest.mark.parametrize("D", [65, 600])
+def test_gather_and_direct_read_in_one_loop_on_a_wavefront_per_chain(D, gather_direct_targets):
+    """new_state with joint_wg = 0: the generated program on one wavefront per chain (k_target_joint_rows), a second pass
+    over the lanes at 65 coordinates, ten at 600.
+
+    These three tests pin the atomic path's VALUES, per route, against the closed form at 50 digits within a derived
+    allowance (gather_direct_at_50_digits).  What they cannot do is catch the race that a plain g[i] += beside the
+    gather's atomic addition was: a lost update happens once in many runs, and running this in a loop to provoke one is
+    not a test.  The missing order itself is what tests/test_tracing_lanes.py sees, on the host under ThreadSanitizer."""
+    from aehmc_amd import hmc
+    from aehmc_amd.engine import get_engine
+    G, tgt, q0 = gather_direct_targets[D]
+    eng = get_engine()
+    try:
+        eng.set_option("joint_wg", 0)
+        worst = gather_direct_worst(G, hmc.new_state(dev(q0), tgt))
+    finally:
+        eng.set_option("joint_wg", 1)
+    print(f"gather + direct, D = {D}, wavefront per chain: largest |err| / bound = {worst:.3g}")
+    assert worst < 1.0
+
+
+@pytest.mark.parametrize("D", [65, 600])
+def test_gather_and_direct_read_in_one_loop_on_a_workgroup_per_chain(D, gather_direct_targets):
+    """joint_wg = 2 (forced): new_state, and one HMC transition of one short leapfrog step, which is what runs the
+    program on eight wavefronts below 2048 coordinates (k_hmc_joint_wg; new_state itself keeps the wavefront per chain
+    there) -- the state it returns holds U and the gradient at the NEW position, compared with the closed form there.
+    (Values only, not the race: see the wavefront test's docstring.)"""
+    from aehmc_amd import RandomStream, hmc
+    from aehmc_amd.engine import get_engine
+    G, tgt, q0 = gather_direct_targets[D]
+    eng = get_engine()
+    try:
+        eng.set_option("joint_wg", 2)
+        state = hmc.new_state(dev(q0), tgt)
+        worst0 = gather_direct_worst(G, state)
+        info, _ = hmc.new_kernel(RandomStream(seeds=range(5)), tgt)(state, 0.01, np.ones(D), 1)
+    finally:
+        eng.set_option("joint_wg", 1)
+    moved = (info.state.position != state.position).any(dim=1)
+    assert bool(moved.all())  # (every chain accepted: U and the gradient it holds are the workgroup kernel's)
+    worst = gather_direct_worst(G, info.state)
+    print(f"gather + direct, D = {D}, workgroup per chain: largest |err| / bound = {worst0:.3g} (new_state), {worst:.3g} (after one transition)")
+    assert worst0 < 1.0 and worst < 1.0
+
+
+def test_gather_and_direct_read_in_one_loop_above_2048_coordinates(gather_direct_targets):
+    """D = 2100 on the default route: new_state on a workgroup per chain (k_target_joint_wg), the rows in LDS.
+    (Values only, not the race: see the wavefront test's docstring.)"""
+    from aehmc_amd import hmc
+    G, tgt, q0 = gather_direct_targets[2100]
+    worst = gather_direct_worst(G, hmc.new_state(dev(q0), tgt))
+    print(f"gather + direct, D = 2100, workgroup per chain: largest |err| / bound = {worst:.3g}")
+    assert worst < 1.0
