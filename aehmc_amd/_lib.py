@@ -103,6 +103,8 @@ SYMBOLS = {
     "aehmc_beta_quantile": (_I, [_P, _I64, _P, _P, _P, _P, _P]),
     "aehmc_summary_psis": (_I, [_P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "aehmc_set_option": (_I, [_P, ct.c_char_p, _I64]),
+    "aehmc_set_white_basis": (_I, [_P, _I64, _P, _P, _P]),
+    "aehmc_white_basis_info": (_I, [_P, ct.POINTER(ct.c_int32), ct.POINTER(_D), ct.POINTER(_D), ct.POINTER(_D)]),
     "aehmc_workspace_bytes": (_I64, [_P, _I64, _I64]),
     "aehmc_set_workspace": (_I, [_P, _P, _I64]),
     "aehmc_new_state": (_I, [_P, _I64, _P, _P, _P, _P]),

@@ -225,6 +225,10 @@ __device__ __forceinline__ void target_elem(const EngineArgs &a, long long i, do
       u = q * q;  // U = 0.5 * sum
       g = q;
       break;
+    case AEHMC_T_WHITE_EIGEN:  // (engine.hip, "dense_eigen": lambda_i rides in a.sigma)
+      g = a.sigma[i] * q;
+      u = q * g;  // U = 0.5 * sum
+      break;
 #ifdef AEHMC_CUSTOM_TARGET  // run-time compiled copy of these kernels (aehmc_set_custom_target): the user's function
     case AEHMC_T_CUSTOM:
       aehmc_custom_elem(q, i, a.cparams, u, g);
@@ -265,10 +269,11 @@ __device__ __forceinline__ double target_joint(const EngineArgs &a, int lane, in
 }
 #endif
 __device__ __forceinline__ double target_finish(const EngineArgs &a, double usum) {
-  return (a.tkind == AEHMC_T_ISO_GAUSSIAN || a.tkind == AEHMC_T_DENSE_MVN) ? 0.5 * usum : usum;
+  return (a.tkind == AEHMC_T_ISO_GAUSSIAN || a.tkind == AEHMC_T_DENSE_MVN || a.tkind == AEHMC_T_WHITE_EIGEN) ? 0.5 * usum : usum;
 }
 __device__ __forceinline__ bool target_is_elem(int k) {
-  return k == AEHMC_T_STD_NORMAL || k == AEHMC_T_ISO_GAUSSIAN || k == AEHMC_T_DIAG_GAUSSIAN || k == AEHMC_T_CUSTOM;
+  return k == AEHMC_T_STD_NORMAL || k == AEHMC_T_ISO_GAUSSIAN || k == AEHMC_T_DIAG_GAUSSIAN || k == AEHMC_T_CUSTOM ||
+         k == AEHMC_T_WHITE_EIGEN;
 }
 // diagonal / scalar velocity imm o p (metrics.py:47,51,71)
 __device__ __forceinline__ double vel_diag(const EngineArgs &a, long long c, long long i, double p) {
@@ -1799,6 +1804,40 @@ AEHMC_TU_LOCAL __global__ void k_symmetrize(const double *src, double *dst, long
   const long long i = (long long)blockIdx.y * 32 + threadIdx.y, j = (long long)blockIdx.x * 32 + threadIdx.x;
   if (i >= n || j >= n) return;
   dst[i * n + j] = 0.5 * (src[i * n + j] + src[j * n + i]);
+}
+// eigen route of the whitened mode ("dense_eigen"), start of a transition: g_y = lambda o y on every row
+AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_eigen_grad(EngineArgs a, const double *lam, const double *y, double *g) {
+  AEHMC_CHAIN_OF_WAVE();
+  const size_t row = (size_t)c * a.D;
+  for (long long i = lane; i < a.D; i += 64) g[row + i] = lam[i] * y[row + i];
+}
+// acceptance check of an eigenbasis, once per basis: G = V^T V, R = (H V)^T and Vt = V^T, all [n, n] row-major.
+// out[0] = max |G - I|, out[1] = max |R - diag(lam) Vt|, out[2] = max |lam|, as the bit patterns of non-negative doubles
+// (which order as unsigned integers); a NaN counts as +inf
+AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_basis_check(const double *G, const double *R, const double *Vt, const double *lam,
+                                                     long long n, unsigned long long *out) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  double m0 = 0.0, m1 = 0.0, m2 = 0.0;
+  if (idx < n * n) {
+    const long long i = idx / n, j = idx - i * n;
+    m0 = fabs(G[idx] - (i == j ? 1.0 : 0.0));
+    m1 = fabs(R[idx] - lam[i] * Vt[idx]);
+    if (idx < n) m2 = fabs(lam[idx]);
+    if (!(m0 == m0)) m0 = INFINITY;
+    if (!(m1 == m1)) m1 = INFINITY;
+    if (!(m2 == m2)) m2 = INFINITY;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    m0 = fmax(m0, __shfl_xor(m0, off));
+    m1 = fmax(m1, __shfl_xor(m1, off));
+    m2 = fmax(m2, __shfl_xor(m2, off));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMax(out + 0, (unsigned long long)__double_as_longlong(m0));
+    atomicMax(out + 1, (unsigned long long)__double_as_longlong(m1));
+    if (idx < n) atomicMax(out + 2, (unsigned long long)__double_as_longlong(m2));
+  }
 }
 AEHMC_TU_LOCAL __global__ __launch_bounds__(256) void k_vel_diag(EngineArgs a, const double *p, double *v) {
   AEHMC_CHAIN_OF_WAVE();

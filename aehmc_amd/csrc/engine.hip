@@ -4,9 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
+#include <dlfcn.h>
 #include <unistd.h>
 
 #include <algorithm>
+#include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -238,7 +241,26 @@ struct aehmc_ctx {
     // one binding gives) -- and is dropped otherwise.
     bool pending = false;
     double *old_L = nullptr, *old_Linv = nullptr, *old_H = nullptr, *old_mu = nullptr;
+    bool eig = false;  // the record's z is the eigen route's y
   } carry;
+  // eigen route of the whitened mode ("dense_eigen"): H = V diag(lam) V^T, formed by white_basis on the first
+  // NUTS call that wants it.  Vt = V^T, Tin = V^T L^-1, Tout = L V, Tp = L^-T V, all [D, D] row-major: the B operand of
+  // A B^T in s = V^T r, y = Tin (q - mu), q - mu = Tout y, p = Tp s
+  int opt_dense_eigen = 1;         // 0 off, 1 where the whitened mode applies and D >= EIGEN_MIN_D, 2 wherever it applies
+  bool opt_eigen_solver = true;    // false (tests): the solver's symbols are not found
+  struct {
+    bool tried = false, ready = false;  // tried: white_basis has decided for this operator (state says what)
+    int state = 0;                      // aehmc_white_basis_info
+    double orth = -1.0, resid = -1.0, solver_ms = 0.0;
+    double *Vt = nullptr, *lam = nullptr, *Tin = nullptr, *Tout = nullptr, *Tp = nullptr;
+    double *sup_V = nullptr, *sup_lam = nullptr;  // aehmc_set_white_basis: the caller's V and lam (copies)
+    int64_t sup_D = 0, D = 0;  // (D: the size of the basis in use)
+    // aehmc_set_target / aehmc_set_metric with a basis in use: it is kept aside with a copy of its H, and the next
+    // white_basis takes it back if the new binding's H has those bits (the solver is not paid again by a caller who
+    // binds fresh copies of the same matrices)
+    double *keep_H = nullptr, *keep_Vt = nullptr, *keep_lam = nullptr;
+    int64_t keep_D = 0;
+  } eig;
 };
 
 #define HIPCHK(expr)                                                                     \
@@ -279,7 +301,37 @@ static inline void carry_drop(aehmc_ctx *ctx) {
 // drops the whitened operator (hipFree waits for the launches that still read it)
 // `rebind` (aehmc_set_target, aehmc_set_metric on a dense-MVN binding): a valid carry record becomes pending, see
 // aehmc_ctx::carry
+static void eigen_free_keep(aehmc_ctx *ctx) {
+  for (double **p : {&ctx->eig.keep_H, &ctx->eig.keep_Vt, &ctx->eig.keep_lam}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  ctx->eig.keep_D = 0;
+}
+// drops the basis of the bound operator; `keep`: V^T and lam are kept aside with a copy of H (aehmc_ctx::eig)
+static void eigen_release(aehmc_ctx *ctx, bool keep) {
+  auto &e = ctx->eig;
+  if (keep && e.ready && ctx->wh_H) {
+    eigen_free_keep(ctx);
+    const int64_t D = e.D;
+    if (hipMalloc((void **)&e.keep_H, (size_t)D * D * sizeof(double)) == hipSuccess &&
+        hipMemcpy(e.keep_H, ctx->wh_H, (size_t)D * D * sizeof(double), hipMemcpyDeviceToDevice) == hipSuccess) {
+      e.keep_Vt = e.Vt; e.keep_lam = e.lam; e.keep_D = D;
+      e.Vt = e.lam = nullptr;
+    } else {
+      (void)hipGetLastError();
+      eigen_free_keep(ctx);
+    }
+  }
+  for (double **p : {&e.Vt, &e.lam, &e.Tin, &e.Tout, &e.Tp}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  e.tried = e.ready = false;
+}
 static void white_release(aehmc_ctx *ctx, bool rebind = false) {
+  eigen_release(ctx, rebind);  // (a basis kept aside by an earlier re-binding waits for the next white_basis)
+  if (!rebind) eigen_free_keep(ctx);
   const bool set_aside = rebind && ctx->carry.valid && ctx->wh_ready && ctx->wh_mu;
   const bool keep = set_aside || (rebind && ctx->carry.pending && !ctx->wh_ready);
   if (set_aside) {
@@ -375,6 +427,8 @@ extern "C" int aehmc_destroy(aehmc_ctx *ctx) {
   if (ctx->glm_z) (void)hipFree(ctx->glm_z);
   if (ctx->glm_lsum) (void)hipFree(ctx->glm_lsum);
   white_release(ctx);
+  if (ctx->eig.sup_V) (void)hipFree(ctx->eig.sup_V);
+  if (ctx->eig.sup_lam) (void)hipFree(ctx->eig.sup_lam);
   custom_release(ctx->bound);
   custom_release(ctx->pw);
   if (ctx->pw_work) (void)hipFree(ctx->pw_work);
@@ -1610,6 +1664,21 @@ extern "C" int aehmc_set_option(aehmc_ctx *ctx, const char *name, int64_t value)
     ctx->opt_dense_whiten_ahead = value != 0;
     return 0;
   }
+  if (!strcmp(name, "dense_eigen")) {
+    if (value < 0 || value > 2) FAIL("dense_eigen: 0 (off), 1 (default: D >= 2048), 2 (wherever the whitened mode applies)");
+    if (ctx->opt_dense_eigen != (int)value) carry_drop(ctx);
+    ctx->opt_dense_eigen = (int)value;
+    return 0;
+  }
+  if (!strcmp(name, "dense_eigen_solver")) {
+    if (ctx->opt_eigen_solver != (value != 0)) {
+      carry_drop(ctx);
+      eigen_release(ctx, false);
+      eigen_free_keep(ctx);
+    }
+    ctx->opt_eigen_solver = value != 0;
+    return 0;
+  }
   if (!strcmp(name, "gemm_small_tiles")) {
     ctx->opt_gemm_small = (int)value;
     return 0;
@@ -1659,6 +1728,40 @@ extern "C" int aehmc_set_option(aehmc_ctx *ctx, const char *name, int64_t value)
     return 0;
   }
   FAIL(std::string("unknown option ") + name);
+}
+
+extern "C" int aehmc_set_white_basis(aehmc_ctx *ctx, int64_t D, const double *V, const double *lam, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  if ((V == nullptr) != (lam == nullptr)) FAIL("set_white_basis: V and lam go together");
+  if (V && D < 1) FAIL("set_white_basis: D must be positive");
+  auto &e = ctx->eig;
+  carry_drop(ctx);
+  eigen_release(ctx, false);
+  eigen_free_keep(ctx);
+  for (double **p : {&e.sup_V, &e.sup_lam}) {
+    if (*p) HIPCHK(hipFree(*p));
+    *p = nullptr;
+  }
+  e.sup_D = 0;
+  e.state = 0;
+  if (!V) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMalloc((void **)&e.sup_V, (size_t)D * D * sizeof(double)));
+  HIPCHK(hipMalloc((void **)&e.sup_lam, D * sizeof(double)));
+  e.sup_D = D;
+  HIPCHK(hipMemcpyAsync(e.sup_V, V, (size_t)D * D * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(e.sup_lam, lam, D * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+extern "C" int aehmc_white_basis_info(aehmc_ctx *ctx, int32_t *state, double *orth, double *resid, double *solver_ms) {
+  if (!ctx) return -2;
+  if (state) *state = ctx->eig.state;
+  if (orth) *orth = ctx->eig.orth;
+  if (resid) *resid = ctx->eig.resid;
+  if (solver_ms) *solver_ms = ctx->eig.solver_ms;
+  return 0;
 }
 
 // ------------------------------------------------------------------ workspace ------
@@ -2023,10 +2126,167 @@ static int white_prepare(aehmc_ctx *ctx, hipStream_t st) {
   if (!rc) ctx->wh_ready = true;
   return done(rc);
 }
+
+// ---- eigen route of the whitened mode ("dense_eigen").  H is one matrix for the life of a binding: with
+// H = V diag(lam) V^T and y = V^T z, s = V^T r the whitened problem is a coordinate-wise Gaussian of precisions lam_i
+// under the identity metric, and NUTS is equivariant under the rotation (kinetic energy, U and every U-turn dot product
+// are unchanged; s is the raw normals, rotated).  The leapfrogs then need no product at all.
+constexpr int64_t EIGEN_MIN_D = 2048;  // "dense_eigen" 1: below, the recorded byte-exact cases keep the route they were recorded with
+// Acceptance bounds of a basis (white_basis): ten times the larger of what LAPACK's dsyevd leaves for the operators of
+// tests/test_gpu_dense_eigen.py (D = 513, 700, both spectra: max |V^T V - I| 3.4e-15, residual 2.4e-15) and what
+// rocsolver_dsyevd leaves for the benchmark's operator at D = 10^4 (4.6e-15, 1.9e-15) -- DESIGN §3 has the table
+constexpr double EIGEN_ORTH_MAX = 4.6e-14, EIGEN_RESID_MAX = 2.4e-14;
+static bool eigen_wanted(const aehmc_ctx *ctx, int64_t D) {
+  return ctx->opt_dense_eigen == 2 || (ctx->opt_dense_eigen == 1 && D >= EIGEN_MIN_D);
+}
+// rocsolver_dsyevd and the three rocblas handle calls it needs, looked up once per process.  A process that already holds
+// the libraries (PyTorch loads its own) gets those; otherwise the loader's search path decides.
+struct EigenSolver {
+  int (*create)(void **) = nullptr;
+  int (*destroy)(void *) = nullptr;
+  int (*set_stream)(void *, hipStream_t) = nullptr;
+  int (*dsyevd)(void *, int, int, int, double *, int, double *, double *, int *) = nullptr;
+  bool ok = false;
+};
+static const EigenSolver &eigen_solver() {
+  static const EigenSolver api = [] {
+    EigenSolver s;
+    void *h = nullptr;
+    for (const char *name : {"librocsolver.so.0", "librocsolver.so"}) {
+      if (!h) h = dlopen(name, RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD);
+    }
+    for (const char *name : {"librocsolver.so.0", "librocsolver.so"}) {
+      if (!h) h = dlopen(name, RTLD_NOW | RTLD_LOCAL);
+    }
+    if (!h) return s;
+    s.create = (decltype(s.create))dlsym(h, "rocblas_create_handle");
+    s.destroy = (decltype(s.destroy))dlsym(h, "rocblas_destroy_handle");
+    s.set_stream = (decltype(s.set_stream))dlsym(h, "rocblas_set_stream");
+    s.dsyevd = (decltype(s.dsyevd))dlsym(h, "rocsolver_dsyevd");
+    s.ok = s.create && s.destroy && s.set_stream && s.dsyevd;
+    return s;
+  }();
+  return api;
+}
+// V^T (the columns of the solver's column-major output are the eigenvectors: read row-major it IS V^T) and lam of the
+// symmetric H, in place in `Vt`.  Returns the state: 1, or -1 / -2 (aehmc_white_basis_info)
+static int eigen_solve(aehmc_ctx *ctx, double *Vt, double *lam, int64_t D, hipStream_t st) {
+  const EigenSolver &api = eigen_solver();
+  if (!ctx->opt_eigen_solver || !api.ok || D > INT32_MAX) return -1;
+  double *E = nullptr;
+  int *info = nullptr;
+  void *handle = nullptr;
+  int state = -2, h_info = -1;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (hipMalloc((void **)&E, D * sizeof(double)) == hipSuccess && hipMalloc((void **)&info, sizeof(int)) == hipSuccess &&
+      api.create(&handle) == 0 && api.set_stream(handle, st) == 0 &&
+      api.dsyevd(handle, /*rocblas_evect_original*/ 211, /*rocblas_fill_lower*/ 122, (int)D, Vt, (int)D, lam, E, info) == 0 &&
+      hipMemcpyAsync(&h_info, info, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
+      hipStreamSynchronize(st) == hipSuccess && h_info == 0)
+    state = 1;
+  (void)hipGetLastError();
+  ctx->eig.solver_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (handle) (void)api.destroy(handle);
+  (void)hipFree(E); (void)hipFree(info);
+  return state;
+}
+// The basis of the bound operator (white_prepare has run), once per operator: the caller's (aehmc_set_white_basis), the
+// one kept across a re-binding if H has its bits, or the solver's; checked on the device; then the three transforms by
+// the project's GEMM.  Whatever goes wrong leaves the whitened route: eig.ready says whether the eigen route may run.
+static int white_basis(aehmc_ctx *ctx, hipStream_t st) {
+  auto &e = ctx->eig;
+  if (e.tried) return 0;
+  e.tried = true;
+  e.ready = false;
+  const double kept_orth = e.orth, kept_resid = e.resid, kept_ms = e.solver_ms;  // (of the basis kept aside, if one is)
+  e.orth = e.resid = -1.0;
+  e.solver_ms = 0.0;
+  const int64_t D = ctx->tgt.D;
+  const size_t mb = (size_t)D * D * sizeof(double);
+  double *G = nullptr, *R = nullptr;
+  unsigned long long *chk = nullptr;  // [0..2] k_basis_check, [3] (as int) k_bits_differ
+  const bool prof = ctx->prof;  // (the formation's GEMMs are not the profiled workload's)
+  auto done = [&](int state) {
+    (void)hipFree(G); (void)hipFree(R); (void)hipFree(chk);
+    (void)hipGetLastError();
+    ctx->prof = prof;
+    eigen_free_keep(ctx);
+    e.state = state;
+    if (state > 0) {
+      e.ready = true;
+      e.D = D;
+    } else {
+      for (double **p : {&e.Vt, &e.lam, &e.Tin, &e.Tout, &e.Tp}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+      }
+    }
+    return 0;
+  };
+  if (hipMalloc((void **)&chk, 4 * sizeof(unsigned long long)) != hipSuccess ||
+      hipMemsetAsync(chk, 0, 4 * sizeof(unsigned long long), st) != hipSuccess)
+    return done(-4);
+  int state = 0;
+  const dim3 tgrid((unsigned)((D + 31) / 32), (unsigned)((D + 31) / 32));
+  if (e.sup_V) {
+    if (e.sup_D != D) return done(-3);
+    if (hipMalloc((void **)&e.Vt, mb) != hipSuccess || hipMalloc((void **)&e.lam, D * sizeof(double)) != hipSuccess) return done(-4);
+    hipLaunchKernelGGL(k_transpose, tgrid, dim3(32, 8), 0, st, (const double *)e.sup_V, e.Vt, (long long)D);
+    if (hipMemcpyAsync(e.lam, e.sup_lam, D * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) return done(-4);
+    state = 2;
+  } else {
+    if (e.keep_H && e.keep_D == D) {
+      unsigned long long h_chk[4] = {0, 0, 0, 1};
+      hipLaunchKernelGGL(k_bits_differ, dim3((unsigned)(((size_t)D * D + 255) / 256)), dim3(256), 0, st, (const double *)ctx->wh_H,
+                         (const double *)e.keep_H, (long long)(D * D), (int *)(chk + 3));
+      if (hipMemcpyAsync(h_chk, chk, sizeof(h_chk), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess)
+        return done(-4);
+      if ((int)h_chk[3] == 0) {  // the same operator: its basis was checked against these very bits
+        e.Vt = e.keep_Vt; e.lam = e.keep_lam;
+        e.keep_Vt = e.keep_lam = nullptr;
+        e.orth = kept_orth; e.resid = kept_resid; e.solver_ms = kept_ms;
+        state = 3;
+      }
+    }
+    if (!state) {
+      if (hipMalloc((void **)&e.Vt, mb) != hipSuccess || hipMalloc((void **)&e.lam, D * sizeof(double)) != hipSuccess ||
+          hipMemcpyAsync(e.Vt, ctx->wh_H, mb, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return done(-4);
+      state = eigen_solve(ctx, e.Vt, e.lam, D, st);
+      if (state < 0) return done(state);
+    }
+  }
+  eigen_free_keep(ctx);  // (hipFree waits: the comparison above has run)
+  ctx->prof = false;
+  if (state != 3) {  // acceptance check: G = V^T V, R = (H V)^T (H is symmetric to the bit: its rows are its columns)
+    if (hipMalloc((void **)&G, mb) != hipSuccess || hipMalloc((void **)&R, mb) != hipSuccess) return done(-4);
+    if (gemm(ctx, D, D, D, e.Vt, D, e.Vt, D, G, D, st) || gemm(ctx, D, D, D, e.Vt, D, ctx->wh_H, D, R, D, st)) return done(-4);
+    hipLaunchKernelGGL(k_basis_check, dim3((unsigned)(((size_t)D * D + 255) / 256)), dim3(256), 0, st, (const double *)G, (const double *)R,
+                       (const double *)e.Vt, (const double *)e.lam, (long long)D, chk);
+    double h[4] = {0, 0, 0, 0};
+    if (hipMemcpyAsync(h, chk, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
+        hipGetLastError() != hipSuccess)
+      return done(-4);
+    e.orth = h[0];
+    e.resid = h[2] > 0.0 ? h[1] / h[2] : INFINITY;
+    if (!(e.orth <= EIGEN_ORTH_MAX) || !(e.resid <= EIGEN_RESID_MAX)) return done(-3);
+  }
+  if (hipMalloc((void **)&e.Tin, mb) != hipSuccess || hipMalloc((void **)&e.Tout, mb) != hipSuccess ||
+      hipMalloc((void **)&e.Tp, mb) != hipSuccess)
+    return done(-4);
+  // Tin = V^T L^-1 (L^-1 = sqrt_mass^T: its transpose is the bound array), Tout = L V, Tp = L^-T V = sqrt_mass V
+  if (gemm(ctx, D, D, D, e.Vt, D, ctx->met.sqrt_mass, D, e.Tin, D, st) ||
+      gemm(ctx, D, D, D, ctx->wh_L, D, e.Vt, D, e.Tout, D, st) ||
+      gemm(ctx, D, D, D, ctx->met.sqrt_mass, D, e.Vt, D, e.Tp, D, st))
+    return done(-4);
+  return done(state);
+}
 // state and momentum of the whitened problem in workspace vectors that the dense-metric layout holds and the identity
 // metric leaves unused
 struct WhiteBufs {
   double *z, *hz, *z0, *r, *qn, *gn, *Un, *Uw;
+  bool eig;  // the eigen route: z holds y = V^T z, r holds s = V^T r
 };
 // z0 = L^-1 (q0 - mu), H z0 (the product the leapfrogs form), U0 the caller's (U is invariant); `b` = the whitened
 // problem's arguments: identity metric, mu = 0, precision H
@@ -2035,12 +2295,19 @@ struct WhiteBufs {
 // H z the previous transition ended on.  Decided on the device, per chain, by content.
 // `ahead` (NUTS, "dense_whiten_ahead"): the half-step momentum gets a vector of its own -- vhalf, which only the literal
 // dense mode uses.
-static int white_begin(aehmc_ctx *ctx, const EngineArgs &a, EngineArgs &b, WhiteBufs &w, hipStream_t st, bool ahead = false) {
+// `want_eig` (NUTS, "dense_eigen"): with a basis of H (white_basis) the whitened state is y = V^T z, formed by ONE product
+// with Tin = V^T L^-1, its gradient lam o y elementwise, and `b` a coordinate-wise problem (AEHMC_T_WHITE_EIGEN) for the
+// diagonal lock-step stage; w.eig says that the route was taken.
+static int white_begin(aehmc_ctx *ctx, const EngineArgs &a, EngineArgs &b, WhiteBufs &w, hipStream_t st, bool ahead = false,
+                       bool want_eig = false) {
   if (int rc = white_prepare(ctx, st)) {  // (settles a pending record: valid again, or dropped)
     carry_drop(ctx);
     return rc;
   }
-  const bool had = ctx->carry.valid;
+  if (want_eig) (void)white_basis(ctx, st);
+  const bool eig = want_eig && ctx->eig.ready;
+  w.eig = eig;
+  const bool had = ctx->carry.valid && ctx->carry.eig == eig;  // (a record of the other route holds another vector)
   carry_drop(ctx);  // consumed: white_end records the next one, a call that fails midway none
   const int64_t C = a.C, D = a.D;
   w.z = a.cur_w; w.hz = a.end_w[0]; w.z0 = a.end_w[1]; w.r = a.cur_v; w.qn = a.end_v[0]; w.gn = a.end_v[1];
@@ -2053,13 +2320,22 @@ static int white_begin(aehmc_ctx *ctx, const EngineArgs &a, EngineArgs &b, White
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, st, (const ChainCtl *)a.ctl, (long long)C, a.row_idx, a.n_rows,
                        (int *)nullptr);
     HIPCHK(hipGetLastError());
-    if (gemm(ctx, C, D, D, a.rbuf, D, ctx->wh_Linv, D, w.z, D, st, a.row_idx, a.n_rows, 0, tri_in, true)) return -1;
-    if (gemm(ctx, C, D, D, w.z, D, ctx->wh_H, D, w.hz, D, st, a.row_idx, a.n_rows, 0, 0, true)) return -1;
+    if (eig) {
+      if (gemm(ctx, C, D, D, a.rbuf, D, ctx->eig.Tin, D, w.z, D, st, a.row_idx, a.n_rows, 0, 0, true)) return -1;
+    } else {
+      if (gemm(ctx, C, D, D, a.rbuf, D, ctx->wh_Linv, D, w.z, D, st, a.row_idx, a.n_rows, 0, tri_in, true)) return -1;
+      if (gemm(ctx, C, D, D, w.z, D, ctx->wh_H, D, w.hz, D, st, a.row_idx, a.n_rows, 0, 0, true)) return -1;
+    }
   } else {
     LAUNCH(k_residual, C, st, a, (const double *)a.q, a.rbuf);
-    if (gemm(ctx, C, D, D, a.rbuf, D, ctx->wh_Linv, D, w.z, D, st, nullptr, nullptr, 0, tri_in)) return -1;
-    if (gemm(ctx, C, D, D, w.z, D, ctx->wh_H, D, w.hz, D, st)) return -1;
+    if (eig) {
+      if (gemm(ctx, C, D, D, a.rbuf, D, ctx->eig.Tin, D, w.z, D, st)) return -1;
+    } else {
+      if (gemm(ctx, C, D, D, a.rbuf, D, ctx->wh_Linv, D, w.z, D, st, nullptr, nullptr, 0, tri_in)) return -1;
+      if (gemm(ctx, C, D, D, w.z, D, ctx->wh_H, D, w.hz, D, st)) return -1;
+    }
   }
+  if (eig) LAUNCH(k_eigen_grad, C, st, a, (const double *)ctx->eig.lam, (const double *)w.z, w.hz);  // (every row: the same bits as the record's)
   HIPCHK(hipMemcpyAsync(w.z0, w.z, (size_t)C * D * sizeof(double), hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(w.Uw, a.U, (size_t)C * sizeof(double), hipMemcpyDeviceToDevice, st));
   b = a;
@@ -2074,15 +2350,27 @@ static int white_begin(aehmc_ctx *ctx, const EngineArgs &a, EngineArgs &b, White
   b.q = w.z; b.g = w.hz; b.U = w.Uw;
   b.out.momentum = w.r;
   b.phalf = ahead ? a.vhalf : nullptr;
+  if (eig) {
+    b.tkind = AEHMC_T_WHITE_EIGEN;
+    b.sigma = ctx->eig.lam;
+    b.white_prec = nullptr;
+    b.phalf = nullptr;
+  }
   return 0;
 }
 // p = L^-T r (today's momentum product), q = mu + L z, then (U, g) evaluated afresh at q as aehmc_new_state does; a
 // chain whose returned point is its initial one keeps the caller's (q0, U0, g0)
 static int white_end(aehmc_ctx *ctx, const EngineArgs &a, const WhiteBufs &w, hipStream_t st) {
   const int64_t C = a.C, D = a.D;
-  if (a.out.momentum)
-    if (metric_mul(ctx, C, w.r, ctx->met.sqrt_mass, a.out.momentum, st, nullptr, nullptr, ctx->wh_tri ? 2 : 0)) return -1;
-  if (gemm(ctx, C, D, D, w.z, D, ctx->wh_L, D, w.qn, D, st, nullptr, nullptr, 0, 1)) return -1;
+  if (w.eig) {  // p = (L^-T V) s, q - mu = (L V) y
+    if (a.out.momentum)
+      if (gemm(ctx, C, D, D, w.r, D, ctx->eig.Tp, D, a.out.momentum, D, st)) return -1;
+    if (gemm(ctx, C, D, D, w.z, D, ctx->eig.Tout, D, w.qn, D, st)) return -1;
+  } else {
+    if (a.out.momentum)
+      if (metric_mul(ctx, C, w.r, ctx->met.sqrt_mass, a.out.momentum, st, nullptr, nullptr, ctx->wh_tri ? 2 : 0)) return -1;
+    if (gemm(ctx, C, D, D, w.z, D, ctx->wh_L, D, w.qn, D, st, nullptr, nullptr, 0, 1)) return -1;
+  }
   LAUNCH(k_white_q, C, st, a, (const double *)w.qn, w.qn, a.rbuf);
   if (gemm(ctx, C, D, D, a.rbuf, D, ctx->tgt.prec, D, w.gn, D, st)) return -1;
   LAUNCH(k_half_dot, C, st, a, (const double *)a.rbuf, (const double *)w.gn, w.Un);
@@ -2091,6 +2379,7 @@ static int white_end(aehmc_ctx *ctx, const EngineArgs &a, const WhiteBufs &w, hi
     ctx->carry.valid = true;
     ctx->carry.C = C; ctx->carry.D = D;
     ctx->carry.z = w.z; ctx->carry.hz = w.hz; ctx->carry.qn = w.qn; ctx->carry.gn = w.gn;
+    ctx->carry.eig = w.eig;
   }
   return 0;
 }
@@ -2459,15 +2748,20 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
   EngineArgs wa;  // whitened mode: the transition runs on the whitened problem (white_begin), mapped back at the end
   WhiteBufs wb{};
   if (white)
-    if (int rc = white_begin(ctx, a, wa, wb, st, ctx->opt_dense_whiten_ahead)) return rc;
+    if (int rc = white_begin(ctx, a, wa, wb, st, ctx->opt_dense_whiten_ahead, eigen_wanted(ctx, a.D))) return rc;
   EngineArgs &e = white ? wa : a;
+  const bool eig = white && wb.eig;  // a coordinate-wise problem from here on: the diagonal stage, nothing to compact
   const bool ahead = white && e.phalf;
-  ctx->fuse_pre = a.linear != 0 || white;
+  ctx->fuse_pre = !eig && (a.linear != 0 || white);
   ctx->pre_done = false;
-  if (int rc = launch_begin(ctx, e, true, st)) return rc;
+  if (eig) {  // the raw normals as every route draws them, s = V^T r, then the chain's init on the rotated momentum
+    LAUNCH(k_nuts_draw<true>, C, st, e);
+    if (gemm(ctx, C, a.D, a.D, e.zbuf, a.D, ctx->eig.Vt, a.D, e.cur_p, a.D, st)) return -1;
+    LAUNCH(k_nuts_init<false>, C, st, e);
+  } else if (int rc = launch_begin(ctx, e, true, st)) return rc;
   long long maxsteps = 0;
   for (int j = 0; j < max_num_expansions; j++) maxsteps += (1LL << j) + 1;  // 2**j + 1 per expansion
-  const bool compact = ctx->opt_compact && (a.met_ndim == 2 || a.tkind == AEHMC_T_DENSE_MVN || a.tkind == AEHMC_T_GLM || a.tkind == AEHMC_T_JOINT);
+  const bool compact = !eig && ctx->opt_compact && (a.met_ndim == 2 || a.tkind == AEHMC_T_DENSE_MVN || a.tkind == AEHMC_T_GLM || a.tkind == AEHMC_T_JOINT);
   const int *ri = compact ? a.row_idx : nullptr, *nr = compact ? a.n_rows : nullptr;
   if (compact) {
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, st, (const ChainCtl *)a.ctl, (long long)C,

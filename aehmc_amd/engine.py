@@ -220,8 +220,13 @@ class Engine:
             c.N = p["X"].numel()
         self._check(self.lib.aehmc_set_target(self.ctx, ct.byref(c)), "aehmc_set_target")
         self._keep["target"] = (target, p)
+        # a target of the same kind and size has the workspace layout of the one it replaces: the buffer stays bound, and
+        # with it what the engine keeps there (the whitened carry record, which the engine itself drops unless the new
+        # arrays hold the old content)
+        same_layout = self._target_key is not None and self._target_key[:2] == key[:2] and len(key) == 3
         self._target_key, self.D = key, D
-        self._ws = None
+        if not same_layout:
+            self._ws = None
 
     def set_metric(self, inverse_mass_matrix, D: int, force: bool = False, sqrt_mass=None):
         """gaussian_metric(inverse_mass_matrix) -- aehmc/metrics.py:44-63.  ``sqrt_mass``: the caller's own device array
@@ -373,6 +378,28 @@ class Engine:
 
     def set_option(self, name: str, value: int):
         self._check(self.lib.aehmc_set_option(self.ctx, name.encode(), int(value)), "aehmc_set_option")
+
+    def set_white_basis(self, V=None, lam=None):
+        """ "dense_eigen": the caller's eigenbasis of the whitened operator H = L^T P L (``V`` [D, D], its columns the
+        eigenvectors, ``lam`` [D]) in place of the solver's; ``None`` clears it.  Checked on the device when the next
+        NUTS call forms the route; a basis that does not fit is rejected and the whitened route runs."""
+        if V is None:
+            self._check(self.lib.aehmc_set_white_basis(self.ctx, 0, None, None, self.stream), "aehmc_set_white_basis")
+            return
+        V, lam = _dev_f64(V, self.device).contiguous(), _dev_f64(lam, self.device).reshape(-1).contiguous()
+        D = lam.numel()
+        if tuple(V.shape) != (D, D):
+            raise ValueError(f"white basis: V must be [{D},{D}], got {tuple(V.shape)}")
+        self._check(self.lib.aehmc_set_white_basis(self.ctx, D, V.data_ptr(), lam.data_ptr(), self.stream),
+                    "aehmc_set_white_basis")
+
+    def white_basis_info(self):
+        """What the last whitened NUTS call decided about the eigen route: dict(state, orth, resid, solver_ms) --
+        include/aehmc_hip.h: aehmc_white_basis_info.  state > 0: the route runs."""
+        state, orth, resid, ms = ct.c_int32(0), ct.c_double(0), ct.c_double(0), ct.c_double(0)
+        self._check(self.lib.aehmc_white_basis_info(self.ctx, ct.byref(state), ct.byref(orth), ct.byref(resid),
+                                                    ct.byref(ms)), "aehmc_white_basis_info")
+        return dict(state=state.value, orth=orth.value, resid=resid.value, solver_ms=ms.value)
 
     # ------------------------------------------------------------------ calls
     def new_state(self, q):

@@ -53,8 +53,10 @@ enum aehmc_target_kind {
   AEHMC_T_LINREG = 4,       /* examples/LinearRegression.ipynb:126-166, q = [w, log n] */
   AEHMC_T_CUSTOM = 5,       /* user-defined coordinate-wise target, compiled at run time: aehmc_set_custom_target */
   AEHMC_T_GLM = 6,          /* user-defined row-reduction target over a data matrix: aehmc_set_custom_glm_target */
-  AEHMC_T_JOINT = 7         /* user-defined JOINT (non-separable) log-density, D <= 2048 (10176 with a reverse-mode
+  AEHMC_T_JOINT = 7,        /* user-defined JOINT (non-separable) log-density, D <= 2048 (10176 with a reverse-mode
                                program), differentiated by the engine: aehmc_set_custom_joint_target */
+  AEHMC_T_WHITE_EIGEN = 8   /* the engine's own: dU/dy_i = lambda_i y_i, U = 0.5 sum y_i dU/dy_i -- a whitened dense MVN in
+                               the eigenbasis of its operator ("dense_eigen").  Not accepted by aehmc_set_target */
 };
 
 typedef struct {
@@ -281,6 +283,20 @@ int aehmc_set_metric(aehmc_ctx *ctx, const aehmc_metric *metric);
  *                   second pass that reads them back; a chain that turns round forms it from its new rows.  The same
  *                   operations on the same bits: every output and the generator states equal 0's bit for bit.
  *                   0 = the two-pass stage
+ *  "dense_eigen" 1  whitened mode, NUTS: H = L^T P L is the same matrix in every leapfrog of every call while target
+ *                   and metric stay bound, so it is factored ONCE, H = V diag(lambda) V^T, and the transition runs in
+ *                   y = V^T z, s = V^T r -- a coordinate-wise Gaussian of precisions lambda_i under the identity
+ *                   metric, on the diagonal lock-step stage: no product inside the loop.  A transition keeps its
+ *                   boundary products: s = V^T r (r: the raw normals, drawn as before), y0 = V^T L^-1 (q0 - mu) on the
+ *                   chains the carry record does not cover, and at the end q = mu + (L V) y, p = (L^-T V) s, and
+ *                   (U, dU/dq) afresh at q.  Same discrete outputs and generator states, reals equal up to rounding.
+ *                   1 = wherever the whitened mode applies and D >= 2048; 2 = wherever it applies (D > 512); 0 = off.
+ *                   The basis comes from rocsolver_dsyevd, looked up at run time (no link-time dependency), or from
+ *                   the caller (aehmc_set_white_basis); either is checked on the device before use (max |V^T V - I|,
+ *                   max |H V - V diag(lambda)| / max |lambda|).  Without a solver, or with a basis that fails the
+ *                   check, the whitened route runs: aehmc_white_basis_info says which.  The basis is kept across a
+ *                   re-binding whose H has the old bits.  HMC stays on the whitened route.
+ *  "dense_eigen_solver" 1  0 = the look-up of the solver fails (for tests of the fall-back); a change drops the basis
  *  "gemm_small_tiles" 1  fp64 GEMM of a mid-size problem (fewer than 256 tiles of 128 x 128, N <= 2048):
  *                   1 = 64 x 128, 64 x 64 or 32 x 64 tiles, the largest that gives every CU two
  *                   workgroups (bitwise the results of the 128 x 128 kernel); 2 / 3 / 4 force
@@ -336,6 +352,19 @@ int aehmc_set_metric(aehmc_ctx *ctx, const aehmc_metric *metric);
  *                   128 registers per lane), 3 (one, 168 registers); 0 = four unless the program then keeps more than
  *                   320 bytes per lane in scratch.  Same results either way */
 int aehmc_set_option(aehmc_ctx *ctx, const char *name, int64_t value);
+
+/* "dense_eigen": the caller's own eigenbasis of the whitened operator H = L^T P L of the bound target and metric, in
+ * place of the solver's.  V [D, D] row-major, its COLUMNS the eigenvectors; lam [D] the eigenvalues (device arrays,
+ * copied).  It is checked like the solver's when the next NUTS call forms the route, and stays the ctx's choice until
+ * it is cleared with V = lam = NULL: a basis that does not fit the operator then bound is rejected, and the whitened
+ * route runs.  Drops the current basis and the carry record. */
+int aehmc_set_white_basis(aehmc_ctx *ctx, int64_t D, const double *V, const double *lam, void *stream);
+/* What the last whitened NUTS call decided.  state: 1 the solver's basis is in use, 2 the caller's, 3 one kept across a
+ * re-binding; 0 none was asked for yet; -1 the solver (library or symbol) is missing, -2 it reported info != 0 or
+ * failed, -3 the basis failed the acceptance check, -4 no memory for it.  orth = max |V^T V - I| and resid =
+ * max |H V - V diag(lam)| / max |lam| as measured (-1: not measured), solver_ms the wall time of the factorisation.
+ * Any pointer may be NULL. */
+int aehmc_white_basis_info(aehmc_ctx *ctx, int32_t *state, double *orth, double *resid, double *solver_ms);
 
 /* workspace the caller must provide to the step calls for C chains */
 int64_t aehmc_workspace_bytes(const aehmc_ctx *ctx, int64_t C, int64_t max_num_expansions);
