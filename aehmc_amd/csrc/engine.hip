@@ -247,6 +247,7 @@ struct aehmc_ctx {
   // NUTS call that wants it.  Vt = V^T, Tin = V^T L^-1, Tout = L V, Tp = L^-T V, all [D, D] row-major: the B operand of
   // A B^T in s = V^T r, y = Tin (q - mu), q - mu = Tout y, p = Tp s
   int opt_dense_eigen = 1;         // 0 off, 1 where the whitened mode applies and D >= EIGEN_MIN_D, 2 wherever it applies
+  int opt_dense_eigen_wide = 1;    // the route's NUTS loop: 1 one k_nuts_wide launch where 512 < D <= 10176, 0 the lock-step stage
   bool opt_eigen_solver = true;    // false (tests): the solver's symbols are not found
   struct {
     bool tried = false, ready = false;  // tried: white_basis has decided for this operator (state says what)
@@ -1670,6 +1671,11 @@ extern "C" int aehmc_set_option(aehmc_ctx *ctx, const char *name, int64_t value)
     ctx->opt_dense_eigen = (int)value;
     return 0;
   }
+  if (!strcmp(name, "dense_eigen_wide")) {
+    if (ctx->opt_dense_eigen_wide != (value != 0)) carry_drop(ctx);
+    ctx->opt_dense_eigen_wide = value != 0;
+    return 0;
+  }
   if (!strcmp(name, "dense_eigen_solver")) {
     if (ctx->opt_eigen_solver != (value != 0)) {
       carry_drop(ctx);
@@ -2754,6 +2760,23 @@ static int nuts_run(aehmc_ctx *ctx, int64_t C, uint64_t *rng, double step_size,
   const bool ahead = white && e.phalf;
   ctx->fuse_pre = !eig && (a.linear != 0 || white);
   ctx->pre_done = false;
+  if (eig && ctx->opt_dense_eigen_wide && nuts_wide_eigen_supported(a.D)) {
+    // "dense_eigen_wide": the coordinate-wise problem is k_nuts_wide's -- one workgroup carries a chain through its whole
+    // tree, lambda where the isotropic instantiation keeps imm.  The raw normals as every route draws them (rows of D in
+    // cur_p, which the kernel leaves alone), s = V^T r into zbuf with the kernel's row stride (its idle slots read the
+    // padding columns as their momentum: zeroed), one launch.  The kernel's work vectors (ckp, cks, slot_*, end_q/p/g,
+    // psum, zbuf) and WhiteBufs' (cur_w, end_w, cur_v, end_v, ckv: the dense-metric block of ws_layout) are disjoint.
+    const int64_t D = a.D, ldw = nuts_wide_ld(D);
+    hipLaunchKernelGGL(k_draw_momentum, chain_grid(C), dim3(256), 0, st, e.rng, e.nsites, (long long)C, (long long)D,
+                       e.sqrt_mass, (long long)e.imm_cs, e.met_ndim, e.cur_p, (long long)D, 1);
+    HIPCHK(hipGetLastError());
+    if (ldw > D)
+      HIPCHK(hipMemset2DAsync(e.zbuf + D, (size_t)ldw * sizeof(double), 0, (size_t)(ldw - D) * sizeof(double), (size_t)C, st));
+    if (gemm(ctx, C, D, D, e.cur_p, D, ctx->eig.Vt, D, e.zbuf, ldw, st)) return -1;
+    e.ldw = ldw;
+    HIPCHK(tu::nuts_wide(e, st));
+    return white_end(ctx, a, wb, st);
+  }
   if (eig) {  // the raw normals as every route draws them, s = V^T r, then the chain's init on the rotated momentum
     LAUNCH(k_nuts_draw<true>, C, st, e);
     if (gemm(ctx, C, a.D, a.D, e.zbuf, a.D, ctx->eig.Vt, a.D, e.cur_p, a.D, st)) return -1;

@@ -75,6 +75,10 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
   static_assert(!JT || QGL, "a joint density reads the position row from LDS");
   constexpr bool DG = TK == AEHMC_T_DIAG_GAUSSIAN || CU || JT;  // otherwise dU/dq == q: no separate copy
   constexpr bool ISO = TK == AEHMC_T_ISO_GAUSSIAN;
+  // TK == AEHMC_T_WHITE_EIGEN (engine.hip, "dense_eigen"): dU/dq_i = lambda_i q_i under the identity metric, the momentum
+  // preset in a.zbuf.  The isotropic instantiation with lambda (a.sigma) in the place of imm -- registers or the second LDS
+  // half -- and the velocity p itself; no dU/dq array: the gradient is formed where it is used, by target_elem's product.
+  constexpr bool WE = TK == AEHMC_T_WHITE_EIGEN;
   constexpr bool PAR_REG = R <= 8;          // per-element parameters live in VGPRs
   constexpr bool IM_LDS = !PAR_REG && !DG;  // imm in the LDS half that dU/dq does not need
   constexpr bool STREAM = !PAR_REG && DG;   // parameters streamed from L2 every pass
@@ -159,7 +163,7 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
     Par x;
     const unsigned i = EC(r);
     const bool on = ON(r);
-    const double im = imrow[im_scalar ? 0u : i];
+    const double im = WE ? a.sigma[i] : imrow[im_scalar ? 0u : i];
     x.im = on ? im : 1.0;
     if (DG && !CU && !JT) {
       const double mu = a.mu[i], sd = a.sigma[i], ls = a.log_sigma[i];
@@ -182,6 +186,8 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
 #define GSET(r, v) do { if (DG) { if (QGL) sg[EL(r)] = (v); else g[(QGL || !DG) ? 0 : (r)] = (v); } } while (0)
 // imm of slot r outside the streamed pass (registers / LDS / L2)
 #define IMOF(r) (PAR_REG ? preg[PAR_REG ? (r) : 0].im : IM_LDS ? sim[EL(r)] : (ON(r) ? imrow[im_scalar ? 0u : EC(r)] : 1.0))
+// the metric's factor of slot r (the eigen route: exactly 1, the place of imm holds lambda)
+#define IMK(r) (WE ? 1.0 : IMOF(r))
 
   // Where the states that are NOT on chip live.  The initial state (q0 = a.q, p0 = a.zbuf,
   // dU/dq0 = a.g; the caller's arrays stay intact until the transition's outputs are written) is
@@ -204,8 +210,9 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
       const bool on = ON(r);
       const double qv = on ? UA(a.q, r) : 0.0, gv = DG ? (on ? UA(a.g, r) : 0.0) : qv, pv = WA(a.zbuf, r);
       if (PAR_REG) preg[PAR_REG ? r : 0] = par_load(r);
-      const double im = on ? imrow[im_scalar ? 0u : EC(r)] : 1.0;
-      if (IM_LDS) sim[EL(r)] = im;
+      const double par = on ? (WE ? a.sigma[EC(r)] : imrow[im_scalar ? 0u : EC(r)]) : 1.0;
+      const double im = WE ? 1.0 : par;
+      if (IM_LDS) sim[EL(r)] = par;
       p[r] = pv;
       QSET(r, qv);
       GSET(r, gv);
@@ -284,9 +291,12 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
           if (r < nslots) {
             Par x = PAR_REG ? preg[PAR_REG ? r : 0] : cur[u];
             if (IM_LDS) x.im = sim[EL(r)];
+            const double lam = x.im;  // (eigen route)
+            if (WE) x.im = 1.0;
             const double p_old = p[r], pb_old = pb[r];
-            double pp = p_old - b * GGET(r);               // integrators.py:59-60
-            const double qq = QGET(r) + aa * (x.im * pp);  // integrators.py:62-64
+            const double q_old = QGET(r);
+            double pp = p_old - b * (WE ? lam * q_old : GGET(r));  // integrators.py:59-60
+            const double qq = q_old + aa * (x.im * pp);            // integrators.py:62-64
             double uu, gg;
             if (TK == AEHMC_T_STD_NORMAL) {
               uu = 0.5 * (qq * qq) + AEHMC_LOG_SQRT_2PI;
@@ -294,6 +304,9 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
             } else if (ISO) {
               uu = qq * qq;
               gg = qq;
+            } else if (WE) {  // engine.cuh target_elem
+              gg = lam * qq;
+              uu = qq * gg;
             } else if (CU) {
 #ifdef AEHMC_CUSTOM_TARGET
               aehmc_custom_elem(qq, (long long)EC(r), a.cparams, uu, gg);
@@ -313,7 +326,7 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
             const double v = x.im * pp;
             const double s = pb_old + pp;  // trajectory.py:243 (the sum restarts from 0 at step 0, :278)
             pb[r] = s;
-            usum += (ISO || ON(r)) ? uu : 0.0;  // (a slot past D adds the target's constant only)
+            usum += (ISO || WE || ON(r)) ? uu : 0.0;  // (a slot past D adds the target's constant only)
             kd += v * pp;
             if (FWD) {  // termination.py:160-173 for level idx_max, from registers
               const double pl = p_old, vl = x.im * pl;
@@ -418,7 +431,7 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
     AEHMC_TICK(1);  // prefetch issue
     sum4(usum, kd, d_l, d_r);
     AEHMC_TICK(2);  // reduction + barrier
-    ct.U_cur = ISO ? 0.5 * usum : usum;
+    ct.U_cur = (ISO || WE) ? 0.5 * usum : usum;
     ct.tmin = tmin;
     ct.tmax = tmax;
 
@@ -450,7 +463,7 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
 #pragma unroll
             for (int r = 0; r < R; r++) {
               if (r < nslots) {
-                const double im = IMOF(r);
+                const double im = IMK(r);
                 const double pl = pre_kp[r], pr = p[r];
                 const double vl = im * pl, vr = im * pr;
                 const double sub = pb[r] - pre_ks[r] + pl;
@@ -508,7 +521,7 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
 #pragma unroll
       for (int r = 0; r < R; r++) {
         if (r < nslots) {
-          const double im = IMOF(r);
+          const double im = IMK(r);
           const double pc = p[r], po = pov[r];
           const double vc = im * pc, vo = im * po;
           const double s = psv[r] + pb[r];
@@ -541,7 +554,7 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
               if (prop_buf != 2) {
                 const double qv = WA(oq, r);
                 UA(a.q, r) = qv;
-                UA(a.g, r) = DG ? WA(og, r) : qv;
+                UA(a.g, r) = DG ? WA(og, r) : WE ? IMOF(r) * qv : qv;
               }
               if (a.out.momentum) UA(a.out.momentum, r) = pv;
             }
@@ -625,6 +638,7 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
 #undef GGET
 #undef GSET
 #undef IMOF
+#undef IMK
 }
 
 #ifndef __HIPCC_RTC__  // (host side)
@@ -677,11 +691,15 @@ inline hipError_t launch_nuts_wide_tr(const EngineArgs &a, const NutsWidePlan &p
   switch (a.tkind) {
     case AEHMC_T_STD_NORMAL: AEHMC_WIDE_LAUNCH(AEHMC_T_STD_NORMAL); break;
     case AEHMC_T_ISO_GAUSSIAN: AEHMC_WIDE_LAUNCH(AEHMC_T_ISO_GAUSSIAN); break;
+    case AEHMC_T_WHITE_EIGEN: AEHMC_WIDE_LAUNCH(AEHMC_T_WHITE_EIGEN); break;
     default: AEHMC_WIDE_LAUNCH(AEHMC_T_DIAG_GAUSSIAN);
   }
 #undef AEHMC_WIDE_LAUNCH
   return hipGetLastError();
 }
+// the eigen route of the whitened dense mode (engine.hip, "dense_eigen_wide"): the AEHMC_T_WHITE_EIGEN instantiations, whose
+// LDS need is the isotropic one's
+inline bool nuts_wide_eigen_supported(long long D) { return D > 512 && D <= 10176; }
 // row stride of the engine's work arrays on this path (a multiple of every team size)
 inline long long nuts_wide_ld(long long D) { return (D + 511) / 512 * 512; }
 // the engine's workspace has rows of nuts_wide_ld(D) -- what this kernel indexes -- only above D = 512 (ws_layout)

@@ -296,6 +296,11 @@ int aehmc_set_metric(aehmc_ctx *ctx, const aehmc_metric *metric);
  *                   max |H V - V diag(lambda)| / max |lambda|).  Without a solver, or with a basis that fails the
  *                   check, the whitened route runs: aehmc_white_basis_info says which.  The basis is kept across a
  *                   re-binding whose H has the old bits.  HMC stays on the whitened route.
+ *  "dense_eigen_wide" 1  eigen route, 512 < D <= 10176: the loop between the boundary products is ONE launch of the
+ *                   workgroup-per-chain NUTS kernel (its isotropic instantiation with lambda in the place of the metric,
+ *                   the rotated momentum s preset) instead of the diagonal lock-step stage with its launch per lock-step
+ *                   and its host polls.  Same discrete outputs and generator states, reals equal up to rounding.
+ *                   0 = the lock-step stage (what D > 10176 takes); a change drops the carry record
  *  "dense_eigen_solver" 1  0 = the look-up of the solver fails (for tests of the fall-back); a change drops the basis
  *  "gemm_small_tiles" 1  fp64 GEMM of a mid-size problem (fewer than 256 tiles of 128 x 128, N <= 2048):
  *                   1 = 64 x 128, 64 x 64 or 32 x 64 tiles, the largest that gives every CU two
