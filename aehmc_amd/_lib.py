@@ -84,6 +84,7 @@ SYMBOLS = {
     "aehmc_summary_lag_update": (_I, [_P, _I64, _I64, _I64, _I64, _I64, ct.c_int32, _I64, _P, _P, _P, _P, _P, _P, _P,
                                       _P]),
     "aehmc_summary_lag_group": (_I64, [_I64]),
+    "aehmc_nested_update": (_I, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
     "aehmc_summary_quantile_work": (_I64, [_I64, _I64, _I64]),
     "aehmc_summary_order_stats": (_I, [_P, _I64, _I64, _I64, _P, ct.POINTER(_I64), _P, _P, _I64, _P]),
     "aehmc_summary_quantiles": (_I, [_P, _I64, _I64, _I64, _P, ct.POINTER(_D), _P, _P, _I64, _P]),

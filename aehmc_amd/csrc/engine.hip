@@ -1289,6 +1289,28 @@ extern "C" int aehmc_summary_lag_update(aehmc_ctx *ctx, int64_t T, int64_t C, in
 }
 extern "C" int64_t aehmc_summary_lag_group(int64_t K) { return K < 2 ? 0 : tu::summary_lag_group(K); }
 
+// Nested R-hat of many short chains (nested.cuh): caller-owned buffers only, as the summaries above.  Its own shape
+// check: a window may be a single draw, which summary_shape refuses.
+extern "C" int aehmc_nested_update(aehmc_ctx *ctx, int64_t T, int64_t C, int64_t D, int64_t t0, int64_t num_draws,
+                                   int64_t window, int64_t chains_per_superchain, const double *samples, double *mean,
+                                   double *m2, double *out, void *stream) {
+  if (!ctx) return -2;
+  HIPCHK(hipSetDevice(ctx->device));
+  const int64_t M = chains_per_superchain;
+  if (num_draws <= 0 || C <= 0 || D <= 0 || T <= 0 || t0 < 0 || t0 + T > num_draws || !samples || !mean || !m2 || !out)
+    FAIL("nested_update: bad arguments");
+  if (window < 1 || num_draws % window) FAIL("nested_update: num_draws must be a multiple of window >= 1");
+  if (M < 1 || C % M || C / M < 2) FAIL("nested_update: C must be at least 2 superchains of chains_per_superchain chains");
+  if (window == 1 && M == 1)
+    FAIL("nested_update: a window of one draw with one chain per superchain leaves nothing to estimate inside a superchain");
+  if (C * D > (int64_t)1 << 38) FAIL("nested_update: C * D is too large");
+  const int64_t nwin = (t0 + T) / window - t0 / window;
+  if (nwin * tu::nested_blocks(D) >= (int64_t)1 << 31)
+    FAIL("nested_update: more than 2^31 workgroups, fold fewer windows a call");
+  HIPCHK(tu::nested_update(samples, T, C, D, t0, window, M, mean, m2, out, (hipStream_t)stream));
+  return 0;
+}
+
 // Order statistics and quantiles of the stored draws (quantile.cuh): the same conventions -- caller-owned buffers only.
 static int quantile_shape(aehmc_ctx *ctx, const char *what, int64_t R, int64_t D, int64_t M, const void *samples,
                           const void *host, const void *out, const void *work, int64_t work_bytes) {

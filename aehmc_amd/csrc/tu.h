@@ -55,6 +55,10 @@ hipError_t summary_lag_update(const double *x, long long T, long long C, long lo
                               long long K, int CG, double *shift, double *sums, double *ring, double *head,
                               double *prod, double *acov, hipStream_t st);
 int summary_lag_group(long long K);
+// nested.cuh (windows of w draws, superchains of M chains; nested_blocks: workgroups per window that ends in a chunk)
+hipError_t nested_update(const double *x, long long T, long long C, long long D, long long t0, long long w, long long M,
+                         double *mean, double *m2, double *out, hipStream_t st);
+long long nested_blocks(long long D);
 // quantile.cuh (work: the caller's scratch of quantile_work_bytes(D, M); the statistics land in its stats rows)
 size_t quantile_work_bytes(long long D, long long M);
 hipError_t quantile_stats(const double *x, long long R, long long D, int U, const long long *ranks, void *work,

@@ -849,6 +849,15 @@ class Engine:
                                                       acov.data_ptr(), self.stream),
                     "aehmc_summary_lag_update")
 
+    def nested_update(self, chunk, t0, num_draws, window, chains_per_superchain, mean, m2, out):
+        """Fold draws t0 ... t0 + T - 1 (chunk [T, C, D]) into the nested R-hat rows out [num_draws / window, 5, D];
+        mean, m2 [C, D] carry the chains' moments of the window that stays open."""
+        T, C, D = chunk.shape
+        self._check(self.lib.aehmc_nested_update(self.ctx, T, C, D, int(t0), int(num_draws), int(window),
+                                                 int(chains_per_superchain), chunk.data_ptr(), mean.data_ptr(),
+                                                 m2.data_ptr(), out.data_ptr(), self.stream),
+                    "aehmc_nested_update")
+
     def summary_final(self, num_draws, n_segments, mean, m2, acov=None):
         """out [7, D] (mean, sd, rhat, ess, mcse, ess_chains, mcse_chains) and lag_truncated [D] (None without acov)."""
         _, C, D = mean.shape

@@ -44,6 +44,12 @@ Without the stored draws: ``QuantileSketch``, a fixed-grid histogram per coordin
 ``Accumulator`` (csrc/sketch.cuh) -- ``quantiles``, ``median`` and ``interval`` of the pooled draws to within one bin
 width, with ``resolved`` to say where that bound holds.
 
+For many chains that each run for a short time -- the regime of the pooled warm-up, ChEES and MEADS, where the
+estimators above have too few draws per chain --: ``nested_rhat`` / ``NestedAccumulator`` (the nested R-hat of Margossian,
+Hoffman, Sountsov, Riou-Durand, Vehtari and Gelman; csrc/nested.cuh).  The chains are started as superchains that share a
+point (``superchain_positions``), the spread of the superchain means is compared with the spread inside superchains, for
+any number of draws from one, per window of draws if asked; ``run(..., nested=acc)`` feeds one while it samples.
+
 fp64, deterministic: two calls on the same draws, and any chunking of them, give the same bits.  No CPU fallback."""
 from __future__ import annotations
 
@@ -947,9 +953,136 @@ class QuantileSketch:
         return int(self.counts[0].sum().item())
 
 
+class NestedRhat(NamedTuple):
+    """Nested R-hat per coordinate (device tensors shaped like one chain's position; with ``window=w`` each has a
+    leading axis of ``num_draws // w`` windows): ``between`` is the variance of the superchain means, ``within`` the
+    mean over superchains of (the variance of the chain means inside the superchain + the mean of the chains' own
+    variances over the window), ``nested_rhat = sqrt(1 + between / within)``; ``mean`` is the mean of the superchain
+    means and ``mcse_superchains = sqrt(between / num_superchains)`` its standard error from independent superchains
+    (no autocorrelation estimate).  ``within = between = 0`` gives NaN, ``within = 0 < between`` +inf,
+    ``between = 0 < within`` exactly 1."""
+    nested_rhat: torch.Tensor
+    between: torch.Tensor
+    within: torch.Tensor
+    mean: torch.Tensor
+    mcse_superchains: torch.Tensor
+    num_draws: int
+    num_chains: int
+    num_superchains: int
+    window: Optional[int]
+
+
+def superchain_positions(starts, chains_per_superchain: int):
+    """Initial positions of ``K * chains_per_superchain`` chains in K superchains: ``starts`` [K, D] or [K], every row
+    repeated ``chains_per_superchain`` times in place -- chain c starts at ``starts[c // chains_per_superchain]``, the
+    contiguous grouping ``nested_rhat`` assumes (and ``parallel.shard_chains`` keeps whole when K divides by the world
+    size)."""
+    if not isinstance(starts, torch.Tensor):
+        raise ValueError(f"starts must be a torch tensor [K, D] or [K], got {type(starts).__name__}")
+    if starts.ndim not in (1, 2) or starts.shape[0] < 1:
+        raise ValueError(f"starts must be [K, D] or [K], got {tuple(starts.shape)}")
+    try:
+        M = operator.index(chains_per_superchain)
+    except TypeError:
+        raise ValueError(f"chains_per_superchain must be an integer, got {chains_per_superchain!r}") from None
+    if M < 1:
+        raise ValueError("chains_per_superchain must be at least 1")
+    return starts.repeat_interleave(M, dim=0).contiguous()
+
+
+def _check_nested(num_draws, num_chains, shape, num_superchains, window):
+    """(num_draws, num_chains, shape, K, M, window or None) of a nested R-hat run, or its ValueError."""
+    num_draws, num_chains, shape = int(num_draws), int(num_chains), tuple(int(s) for s in shape)
+    if len(shape) > 1:
+        raise ValueError(f"a chain's position must be a scalar or a vector, got shape {shape}")
+    if num_chains < 1 or (len(shape) == 1 and shape[0] < 1):
+        raise ValueError("num_chains and the position's length must be positive")
+    if num_draws < 1:
+        raise ValueError(f"nested R-hat needs at least 1 draw, got {num_draws}")
+    try:
+        K = operator.index(num_superchains)
+    except TypeError:
+        raise ValueError(f"num_superchains must be an integer, got {num_superchains!r}") from None
+    if K < 2:
+        raise ValueError(f"nested R-hat compares superchains: num_superchains must be at least 2, got {K}")
+    if num_chains % K:
+        raise ValueError(f"{num_chains} chains do not divide into {K} superchains of equal size")
+    M = num_chains // K
+    if window is not None:
+        try:
+            window = operator.index(window)
+        except TypeError:
+            raise ValueError(f"window must be an integer or None, got {window!r}") from None
+        if window < 1:
+            raise ValueError(f"window must be at least 1, got {window}")
+        if num_draws % window:
+            raise ValueError(f"num_draws must be a multiple of window: {num_draws} draws, windows of {window}")
+    if M == 1 and (num_draws if window is None else window) == 1:
+        raise ValueError("a window of one draw with one chain per superchain leaves nothing to estimate inside a "
+                         "superchain: take more chains per superchain or a longer window")
+    return num_draws, num_chains, shape, K, M, window
+
+
+class NestedAccumulator:
+    """Streaming nested R-hat (Margossian et al.) of a run of ``num_draws`` draws of ``num_chains`` chains whose
+    position has shape ``shape``: the chains are ``num_superchains`` superchains of consecutive chains that share a
+    starting point (``superchain_positions``).  ``update(chunk)`` folds the next draws [T, num_chains, *shape], in order,
+    ``result()`` gives the ``NestedRhat`` once all have arrived.  ``window=None``: one window of all draws, fields shaped
+    like a position; ``window=w`` (``num_draws % w == 0``): one row per window of w draws, a trace that shows when the
+    chains forgot their starting points.  Any number of draws from 1.  The state is the chains' running moments of the
+    window in progress (``mean``, ``m2`` [num_chains, D]) and the rows written so far (``out`` [windows, 5, D]);
+    at most two kernel launches per ``update`` whatever the chunk holds, and where the chunks are cut, inside a window or
+    one draw at a time, does not change a bit (``aehmc_nested_update``, csrc/nested.cuh)."""
+
+    def __init__(self, num_draws: int, num_chains: int, shape, num_superchains: int, window: Optional[int] = None):
+        (self.num_draws, self.num_chains, self.shape, self.num_superchains, self.chains_per_superchain,
+         self.window) = _check_nested(num_draws, num_chains, shape, num_superchains, window)
+        self.D = self.shape[0] if self.shape else 1
+        self._w = self.num_draws if self.window is None else self.window
+        self._eng = get_engine()
+        dev = self._eng.device
+        self.mean = torch.zeros(self.num_chains, self.D, dtype=torch.float64, device=dev)
+        self.m2 = torch.zeros_like(self.mean)
+        self.out = torch.zeros(self.num_draws // self._w, 5, self.D, dtype=torch.float64, device=dev)
+        self.seen = 0
+
+    def update(self, chunk):
+        return self._fold(_chunk_rows(self._eng, chunk, self.num_chains, self.shape, "chunk"))
+
+    def _fold(self, x):  # x: [T, C, D]
+        if self.seen + x.shape[0] > self.num_draws:
+            raise ValueError(f"{self.seen} draws folded, {x.shape[0]} more exceed the run's {self.num_draws}")
+        self._eng.nested_update(x, self.seen, self.num_draws, self._w, self.chains_per_superchain, self.mean, self.m2,
+                                self.out)
+        self.seen += x.shape[0]
+        return self
+
+    def result(self) -> NestedRhat:
+        if self.seen != self.num_draws:
+            raise ValueError(f"{self.seen} of {self.num_draws} draws folded")
+        view = self.shape if self.window is None else (self.out.shape[0],) + self.shape
+        f = [self.out[:, i].reshape(view) for i in range(5)]
+        return NestedRhat(nested_rhat=f[0], between=f[1], within=f[2], mean=f[3], mcse_superchains=f[4],
+                          num_draws=self.num_draws, num_chains=self.num_chains, num_superchains=self.num_superchains,
+                          window=self.window)
+
+
+def nested_rhat(samples, num_superchains: int, *, window: Optional[int] = None, batched: bool = True) -> NestedRhat:
+    """``NestedRhat`` of stored draws ``samples`` as ``summarize`` takes them ([N, C] or [N, C, D] with ``batched``),
+    the C chains in ``num_superchains`` superchains of consecutive chains.  ``window`` as in ``NestedAccumulator``.  One
+    chain (``batched=False``) cannot hold two superchains and is refused."""
+    _check_draws(samples, "samples")
+    lo = 2 if batched else 1
+    if samples.ndim not in (lo, lo + 1):
+        raise ValueError(f"samples must be [N, C] or [N, C, D] (batched) or [N] / [N, D], got {tuple(samples.shape)}")
+    C = samples.shape[1] if batched else 1
+    acc = NestedAccumulator(samples.shape[0], C, tuple(samples.shape[lo:]), num_superchains, window)
+    return acc.update(samples).result()
+
+
 def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_integration_steps=None,
         chunk: Optional[int] = None, max_lag: Optional[int] = None, sketch: Optional[QuantileSketch] = None,
-        constrain=None, waic: Optional[WaicAccumulator] = None):
+        constrain=None, waic: Optional[WaicAccumulator] = None, nested: Optional[NestedAccumulator] = None):
     """Sample ``num_samples`` transitions per chain and summarise them without keeping them: ``kernel.sample`` is
     driven in chunks of ``chunk`` draws into one reused buffer and every chunk is folded into an ``Accumulator``.
     Returns ``(Summary, Diagnostics of the last transition, acceptance history, divergence history)`` -- what
@@ -975,6 +1108,11 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
     when the run ends.  What is returned does not change.  A ``Pointwise`` of ``constrain``'s own model reads the
     constrained buffer of the run; any other model-bound one maps into a buffer of its own, which counts towards
     ``CHUNK_BYTES``.
+
+    ``nested``: a ``NestedAccumulator`` of the run's chains and position shape (the constrained one with ``constrain``)
+    that still expects at least ``num_samples`` draws; every chunk is folded into it too, so the nested R-hat of chains
+    started with ``superchain_positions`` -- or its trace over windows -- is there when the run ends
+    (``nested.result()`` once all its draws have arrived).  What is returned does not change.
 
     An HMC kernel needs ``num_integration_steps`` (as in ``window_adaptation.run``): an int, or one length per
     transition (a sequence of ``num_samples`` entries, as ``kernel.sample`` takes it -- the jittered lengths of
@@ -1009,6 +1147,11 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
         if waic.pointwise.dim != D_in:
             raise ValueError(f"waic folds positions of {waic.pointwise.dim} coordinates, the chains have {D_in}")
     oshape = shape if constrain is None else (int(constrain.constrained_dim),)
+    if nested is not None:
+        if not (isinstance(nested, NestedAccumulator) and nested.num_chains == C and nested.shape == tuple(oshape)):
+            raise ValueError(f"nested must be a NestedAccumulator of {C} chains and shape {tuple(oshape)}")
+        if nested.seen + N > nested.num_draws:
+            raise ValueError(f"nested has folded {nested.seen} of its {nested.num_draws} draws, {N} more exceed them")
     acc = Accumulator(N, C, oshape, max_lag=max_lag)
     if sketch is not None and not (isinstance(sketch, QuantileSketch) and sketch.num_chains == C
                                    and sketch.shape == acc.shape):
@@ -1041,6 +1184,8 @@ def run(kernel, state, step_size, inverse_mass_matrix, num_samples: int, *, num_
         acc.update(samples.reshape((T, C) + oshape))
         if sketch is not None:
             sketch.update(samples.reshape((T, C) + oshape))
+        if nested is not None:
+            nested.update(samples.reshape((T, C) + oshape))
         if acc_hist is None:
             acc_hist = torch.empty((N,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
             div_hist = torch.empty((N,) + tuple(d.shape[1:]), dtype=d.dtype, device=d.device)

@@ -630,6 +630,34 @@ int aehmc_summary_lag_update(aehmc_ctx *ctx, int64_t T, int64_t C, int64_t D, in
                              double *ring, double *head, double *work, double *acov, void *stream);
 int64_t aehmc_summary_lag_group(int64_t K);
 
+/* ---- nested R-hat for many short chains (aehmc_amd/summary.py) ----
+ * The convergence check of the many-chain regime (Margossian, Hoffman, Sountsov, Riou-Durand, Vehtari & Gelman, "Nested
+ * R-hat"): the C chains are K = C / chains_per_superchain superchains of M = chains_per_superchain CONSECUTIVE chains
+ * (chain c belongs to superchain c / M) that share a starting point, and the run of num_draws draws is cut into
+ * num_draws / window windows of `window` draws.  Per window and coordinate, with a_c the mean and s2_c the variance
+ * (divisor window - 1; 0 for a window of one draw) of chain c over the window:
+ *   abar_k  = mean of a_c over the chains of superchain k,        abar = mean of the abar_k,
+ *   between = sum_k (abar_k - abar)^2 / (K - 1),
+ *   within  = mean over k of [ sum_{c in k} (a_c - abar_k)^2 / (M - 1)  (0 when M = 1)  +  mean of s2_c over c in k ],
+ *   nested_rhat = sqrt(1 + between / within),   mcse_superchains = sqrt(between / K).
+ * within = between = 0 gives NaN, within = 0 < between +inf, between = 0 < within exactly 1; a non-finite draw makes its
+ * own coordinate and window non-finite and changes nothing else.  K >= 2, M >= 1, window >= 1 -- but not M = 1 with
+ * window = 1, which leaves nothing inside a superchain --, C * D <= 2^38.
+ *
+ * nested_update: folds the chunk samples [T, C, D] -- draws t0 ... t0 + T - 1 of the run, chunks in order -- and writes
+ * the rows of every window whose last draw the chunk holds: out [num_draws / window, 5, D] = nested_rhat, between,
+ * within, mean (abar), mcse_superchains.  State between the calls, the caller's and not to be touched in between:
+ * mean, m2 [C, D], the chains' running moments of the window that is still open (they need no initial value), and out.
+ * Nothing else is allocated, whatever T and the number of windows.  At most two kernel launches a call, whatever T and
+ * however many windows end in the chunk.  fp64, no floating-point atomics; every sum runs in an order fixed by
+ * (C, D, K, M, window): a chain's draws in ascending t, a superchain's chains in ascending c, the superchains k, k + L,
+ * ... of each of the L = 256 / min(16, D rounded up to a power of two) lanes of a coordinate in ascending k, the lanes
+ * in a fixed tree (pairwise combination of count, mean and sum of squares).  Where the chunks are cut -- inside a window,
+ * chunks of one draw -- does not change a bit. */
+int aehmc_nested_update(aehmc_ctx *ctx, int64_t T, int64_t C, int64_t D, int64_t t0, int64_t num_draws, int64_t window,
+                        int64_t chains_per_superchain, const double *samples, double *mean, double *m2, double *out,
+                        void *stream);
+
 /* ---- order statistics and quantiles of the stored draws (aehmc_amd/summary.py) ----
  * What the reference's users take from arviz on the host (the 5 % / 50 % / 95 % columns of a posterior table), on the
  * device and without a sort: samples [R, D] is the [num_draws, C, D] array of the sampling calls viewed flat, R = N C
