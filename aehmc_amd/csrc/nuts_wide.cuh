@@ -85,6 +85,11 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
   constexpr int BR = STREAM ? 2 : ((R % 4 == 0) ? 4 : R);  // elements per batch (streamed parameters: two, so that
   //                                                           the batch in use and the one on its way stay at 32 registers)
   constexpr int NB = R / BR;
+  // elements of a batch whose LDS reads are issued together (the pass below): the whole batch where q lives in LDS, except
+  // where the streamed parameters leave no registers for it (diagonal Gaussian at R = 20: with 2, 11 VGPRs more and
+  // 16 B / lane of scratch).  With q in registers there is nothing to read ahead: element by element, as written before
+  // (the batched form cost <256, 4> of the standard normal its 96th-register occupancy step).
+  constexpr int LB = (!QGL || (STREAM && R > 16)) ? 1 : BR;
   static_assert(R % BR == 0, "R must be a multiple of the batch size");
   static_assert(QGL || PAR_REG, "more than 8 elements per thread: q lives in LDS");
   __shared__ double red[2][4 * NW];
@@ -279,64 +284,105 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
 #pragma unroll
         for (int u = 0; u < BR; u++) cur[u] = par_load(u);
       }
+      // One batch of BR elements in three phases (per LB of them, above): every LDS read, the arithmetic (element by element,
+      // the sums in ascending element order), every LDS write.  Written element by element, the write of element r may alias
+      // the read of element r + 1 (both clamp to the dummy entry D), so each element waited for its own read and ran its
+      // dependent chain alone; with the reads first they are in flight together and the chains can interleave.  A batch
+      // whose BR slots all exist (FULL, one uniform branch; LDS plans) has no per-element guard, any other keeps it.  Lanes
+      // past D inside an existing slot still clamp (EL / EC / ON); two padded slots of a thread may both read and write
+      // entry D in one batch: it reads 0 and is written 0.
+      auto batch = [&](const int b0, auto full_tag) {
+        constexpr bool FULL = decltype(full_tag)::value;
+        double q_in[BR], g_in[DG ? BR : 1], im_in[IM_LDS ? BR : 1], q_out[BR], g_out[DG ? BR : 1];
+        auto load = [&](const int u) {
+          const int r = b0 * BR + u;
+          q_in[u] = QGET(r);
+          if (DG) g_in[DG ? u : 0] = GGET(r);
+          if (IM_LDS) im_in[IM_LDS ? u : 0] = sim[EL(r)];
+        };
+        auto compute = [&](const int u) {
+          const int r = b0 * BR + u;
+          Par x = PAR_REG ? preg[PAR_REG ? r : 0] : cur[u];
+          if (IM_LDS) x.im = im_in[IM_LDS ? u : 0];
+          const double lam = x.im;  // (eigen route)
+          if (WE) x.im = 1.0;
+          const double p_old = p[r], pb_old = pb[r];
+          const double q_old = q_in[u];
+          double pp = p_old - b * (WE ? lam * q_old : DG ? g_in[DG ? u : 0] : q_old);  // integrators.py:59-60
+          const double qq = q_old + aa * (x.im * pp);                                 // integrators.py:62-64
+          double uu, gg;
+          if (TK == AEHMC_T_STD_NORMAL) {
+            uu = 0.5 * (qq * qq) + AEHMC_LOG_SQRT_2PI;
+            gg = qq;
+          } else if (ISO) {
+            uu = qq * qq;
+            gg = qq;
+          } else if (WE) {  // engine.cuh target_elem
+            gg = lam * qq;
+            uu = qq * gg;
+          } else if (CU) {
+#ifdef AEHMC_CUSTOM_TARGET
+            aehmc_custom_elem(qq, (long long)EC(r), a.cparams, uu, gg);
+#else
+            uu = gg = 0.0;
+#endif
+            gg = ON(r) ? gg : 0.0;  // (a slot past D stays at the fixed point q = p = 0)
+          } else {
+            const double z = (qq - x.mu) / x.sd;
+            uu = 0.5 * (z * z) + x.ls + AEHMC_LOG_SQRT_2PI;
+            gg = z / x.sd;
+          }
+          pp = pp - b * gg;                               // integrators.py:67-69
+          q_out[u] = qq;
+          if (DG) g_out[DG ? u : 0] = gg;
+          p[r] = pp;
+          const double v = x.im * pp;
+          const double s = pb_old + pp;  // trajectory.py:243 (the sum restarts from 0 at step 0, :278)
+          pb[r] = s;
+          usum += (ISO || WE || ON(r)) ? uu : 0.0;  // (a slot past D adds the target's constant only)
+          kd += v * pp;
+          if (FWD) {  // termination.py:160-173 for level idx_max, from registers
+            const double pl = p_old, vl = x.im * pl;
+            const double sub = s - pb_old + pl;
+            const double rho = sub - (pp + pl) / 2;
+            d_l += vl * rho;
+            d_r += v * rho;
+          }
+        };
+        auto store = [&](const int u) {
+          QSET(b0 * BR + u, q_out[u]);
+          GSET(b0 * BR + u, g_out[DG ? u : 0]);
+        };
+        auto here = [&](const int u) { return FULL || b0 * BR + u < nslots; };
+#pragma unroll
+        for (int u0 = 0; u0 < BR; u0 += LB) {
+          if (LB == 1) {  // (element by element: one guard around all three)
+            if (here(u0)) {
+              load(u0);
+              compute(u0);
+              store(u0);
+            }
+          } else {
+#pragma unroll
+            for (int u = u0; u < u0 + LB; u++)
+              if (here(u)) load(u);
+#pragma unroll
+            for (int u = u0; u < u0 + LB; u++)
+              if (here(u)) compute(u);
+#pragma unroll
+            for (int u = u0; u < u0 + LB; u++)
+              if (here(u)) store(u);
+          }
+        }
+      };
 #pragma unroll
       for (int b0 = 0; b0 < NB; b0++) {
         if (STREAM && b0 + 1 < NB) {
 #pragma unroll
           for (int u = 0; u < BR; u++) nxt[u] = par_load((b0 + 1) * BR + u);
         }
-#pragma unroll
-        for (int u = 0; u < BR; u++) {
-          const int r = b0 * BR + u;
-          if (r < nslots) {
-            Par x = PAR_REG ? preg[PAR_REG ? r : 0] : cur[u];
-            if (IM_LDS) x.im = sim[EL(r)];
-            const double lam = x.im;  // (eigen route)
-            if (WE) x.im = 1.0;
-            const double p_old = p[r], pb_old = pb[r];
-            const double q_old = QGET(r);
-            double pp = p_old - b * (WE ? lam * q_old : GGET(r));  // integrators.py:59-60
-            const double qq = q_old + aa * (x.im * pp);            // integrators.py:62-64
-            double uu, gg;
-            if (TK == AEHMC_T_STD_NORMAL) {
-              uu = 0.5 * (qq * qq) + AEHMC_LOG_SQRT_2PI;
-              gg = qq;
-            } else if (ISO) {
-              uu = qq * qq;
-              gg = qq;
-            } else if (WE) {  // engine.cuh target_elem
-              gg = lam * qq;
-              uu = qq * gg;
-            } else if (CU) {
-#ifdef AEHMC_CUSTOM_TARGET
-              aehmc_custom_elem(qq, (long long)EC(r), a.cparams, uu, gg);
-#else
-              uu = gg = 0.0;
-#endif
-              gg = ON(r) ? gg : 0.0;  // (a slot past D stays at the fixed point q = p = 0)
-            } else {
-              const double z = (qq - x.mu) / x.sd;
-              uu = 0.5 * (z * z) + x.ls + AEHMC_LOG_SQRT_2PI;
-              gg = z / x.sd;
-            }
-            pp = pp - b * gg;                               // integrators.py:67-69
-            QSET(r, qq);
-            GSET(r, gg);
-            p[r] = pp;
-            const double v = x.im * pp;
-            const double s = pb_old + pp;  // trajectory.py:243 (the sum restarts from 0 at step 0, :278)
-            pb[r] = s;
-            usum += (ISO || WE || ON(r)) ? uu : 0.0;  // (a slot past D adds the target's constant only)
-            kd += v * pp;
-            if (FWD) {  // termination.py:160-173 for level idx_max, from registers
-              const double pl = p_old, vl = x.im * pl;
-              const double sub = s - pb_old + pl;
-              const double rho = sub - (pp + pl) / 2;
-              d_l += vl * rho;
-              d_r += v * rho;
-            }
-          }
-        }
+        if (QGL && (b0 + 1) * BR <= nslots) batch(b0, WideTagTrue{});
+        else batch(b0, WideTagFalse{});
         if (STREAM && b0 + 1 < NB) {
 #pragma unroll
           for (int u = 0; u < BR; u++) cur[u] = nxt[u];
@@ -489,12 +535,24 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
       AEHMC_FRESH_TT();
       double *const dq = pick2(a.slot_q, sub_buf), *const dp = pick2(a.slot_p, sub_buf),
                    *const dg = pick2(a.slot_g, sub_buf);
+      // (the LDS reads of a batch before its stores, as in the pass: a read that feeds a store directly waits alone.  A
+      //  slot past nslots reads the dummy entry D -- no guard -- and stores nothing.)
 #pragma unroll
-      for (int r = 0; r < R; r++) {
-        if (r < nslots) {
-          WA(dq, r) = QGET(r);
-          WA(dp, r) = p[r];
-          if (DG) WA(dg, r) = GGET(r);
+      for (int b0 = 0; b0 < NB; b0++) {
+        double qv[BR], gv[DG ? BR : 1];
+#pragma unroll
+        for (int u = 0; u < BR; u++) {
+          qv[u] = QGET(b0 * BR + u);
+          if (DG) gv[DG ? u : 0] = GGET(b0 * BR + u);
+        }
+#pragma unroll
+        for (int u = 0; u < BR; u++) {
+          const int r = b0 * BR + u;
+          if (r < nslots) {
+            WA(dq, r) = qv[u];
+            WA(dp, r) = p[r];
+            if (DG) WA(dg, r) = gv[DG ? u : 0];
+          }
         }
       }
       put2(ct.U_slot, sub_buf, ct.U_cur);
@@ -547,16 +605,25 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
         const double *const oq = pick2(a.slot_q, prop_buf & 1), *const og = pick2(a.slot_g, prop_buf & 1);
         const double *const op = prop_buf == 2 ? a.zbuf : pick2(a.slot_p, prop_buf);
 #pragma unroll
-        for (int r = 0; r < R; r++) {
-          if (r < nslots) {
-            const double pv = WA(op, r);
-            if (ON(r)) {
+        for (int b0 = 0; b0 < NB; b0++) {  // (every read of a batch, from memory and -- lambda -- from LDS, before its stores)
+          double pv[BR], qv[BR], gv[BR];
+#pragma unroll
+          for (int u = 0; u < BR; u++) {
+            const int r = b0 * BR + u;
+            const bool in = r < nslots, copy = in && prop_buf != 2;
+            pv[u] = in ? WA(op, r) : 0.0;
+            qv[u] = copy ? WA(oq, r) : 0.0;
+            gv[u] = DG ? (copy ? WA(og, r) : 0.0) : WE ? IMOF(r) : 1.0;
+          }
+#pragma unroll
+          for (int u = 0; u < BR; u++) {
+            const int r = b0 * BR + u;
+            if (r < nslots && ON(r)) {
               if (prop_buf != 2) {
-                const double qv = WA(oq, r);
-                UA(a.q, r) = qv;
-                UA(a.g, r) = DG ? WA(og, r) : WE ? IMOF(r) * qv : qv;
+                UA(a.q, r) = qv[u];
+                UA(a.g, r) = DG ? gv[u] : WE ? gv[u] * qv[u] : qv[u];
               }
-              if (a.out.momentum) UA(a.out.momentum, r) = pv;
+              if (a.out.momentum) UA(a.out.momentum, r) = pv[u];
             }
           }
         }
@@ -580,32 +647,42 @@ __global__ __launch_bounds__(T) void k_nuts_wide(EngineArgs a) {
         ct.step = 0;
         if (go_right != dir) {  // continue from the other end: park this end, fetch that one
           const bool src_init = go_right ? end_init1 : end_init0;
-          double nq[R], np_[R], ng[DG ? R : 1];
+          // (the momentum of that end is pov, loaded above for the U-turn sum of this expansion: the same array -- go_right is
+          //  `oth`, its init flag has not changed -- and nothing has been stored to it since)
+          double nq[R], ng[DG ? R : 1];
           if (src_init) {  // the caller's (unpadded) arrays
 #pragma unroll
             for (int r = 0; r < R; r++) {
               const bool on = r < nslots && ON(r);
               nq[r] = on ? UA(a.q, r) : 0.0;
               if (DG) ng[DG ? r : 0] = on ? UA(a.g, r) : 0.0;
-              np_[r] = r < nslots ? WA(a.zbuf, r) : 0.0;
             }
           } else {
 #pragma unroll
             for (int r = 0; r < R; r++) {
               nq[r] = r < nslots ? WA(pick2(a.end_q, go_right), r) : 0.0;
               if (DG) ng[DG ? r : 0] = r < nslots ? WA(pick2(a.end_g, go_right), r) : 0.0;
-              np_[r] = r < nslots ? WA(pick2(a.end_p, go_right), r) : 0.0;
             }
           }
 #pragma unroll
-          for (int r = 0; r < R; r++) {
-            if (r < nslots) {
-              WA(pick2(a.end_q, dir), r) = QGET(r);
-              WA(pick2(a.end_p, dir), r) = p[r];
-              if (DG) WA(pick2(a.end_g, dir), r) = GGET(r);
-              p[r] = np_[r];
-              QSET(r, nq[r]);
-              GSET(r, DG ? ng[DG ? r : 0] : nq[r]);
+          for (int b0 = 0; b0 < NB; b0++) {  // (LDS reads of a batch first, as in the copy on accept)
+            double qv[BR], gv[DG ? BR : 1];
+#pragma unroll
+            for (int u = 0; u < BR; u++) {
+              qv[u] = QGET(b0 * BR + u);
+              if (DG) gv[DG ? u : 0] = GGET(b0 * BR + u);
+            }
+#pragma unroll
+            for (int u = 0; u < BR; u++) {
+              const int r = b0 * BR + u;
+              if (r < nslots) {
+                WA(pick2(a.end_q, dir), r) = qv[u];
+                WA(pick2(a.end_p, dir), r) = p[r];
+                if (DG) WA(pick2(a.end_g, dir), r) = gv[DG ? u : 0];
+                p[r] = pov[r];
+                QSET(r, nq[r]);
+                GSET(r, DG ? ng[DG ? r : 0] : nq[r]);
+              }
             }
           }
           if (dir) end_init1 = false;
